@@ -45,6 +45,12 @@ Rank 0 prints ONE JSON line (schema in the task contract) including
                   mvsim_comm_allreduce_sum_f64; per-rank slab / all-reduce / finish times and the halo-recompute share
   small_views  -- N = 1: the sizes the reference itself runs (128^3 x 8, 289^3 / 51^3 / inc 3 x 7, 256^3 x 8): sequential views against ONE
                   mvsim_simulate_views_dev call (views stacked), bit-identity checked
+Every record above except `value` and its own timing runs only with `--full` (roofline: with `--full`, or from the timed steps
+themselves under --serial and on the N > 1 data path); a plain run sets up, warms up, times `--steps` steps and prints the line,
+with `value_dense` null.  With N > 1 the broadcast forms' A/B stays in a plain run: `value` is the fastest form's.
+
+`--dump-outputs DIR` writes, after the timed steps, the acquisitions of their last step (dump_outputs below) for comparing builds
+output for output: the inputs are the same in every run with the same arguments.
 """
 from __future__ import annotations
 
@@ -137,7 +143,17 @@ def parse_args():
                          "never run with more than one rank)")
     ap.add_argument("--serial-broadcast", action="store_true",
                     help="N > 1: broadcast the ground truth at the start of each step instead of one step ahead")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every record beside the line of record (serial leg and roofline, no_empty_space, poisson_queue, "
+                         "main_iteration, two_streams, end_to_end, size_1024, small_views, the N > 1 legs at twice the edge, "
+                         "cpu_baseline); without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step computed -- every view's acquisition (a fixed, seeded "
+                         "sample of it where the view is larger than its share of the budget) -- as DIR/acq_view<v>.npy, float32")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args) -> int:
@@ -987,6 +1003,37 @@ def ordered_line(out: dict) -> str:
     lead = {k: (round(v, 4) if isinstance(v, float) and k.endswith("frac") else v) for k, v in lead.items()}
     return json.dumps({**lead, **{k: v for k, v in out.items() if k not in lead}})
 
+
+DUMP_VALUES = 8 << 20     # float32 values over all views of a dataset: 32 MiB on disk
+DUMP_SEED = 20240611
+
+
+def dump_outputs(run, out_dir: str) -> list:
+    """`--dump-outputs DIR`: what the timed path computed in its last step, as its caller receives it -- this rank's views' acquisitions
+    (Poisson counts, float32, (n - 1) // inc + 1 planes of n x n) -- as DIR/acq_view<v>.npy, v the view's index in the dataset.  A view
+    larger than its share of DUMP_VALUES is written as a sample: the same sorted voxel indices (np.random.default_rng(DUMP_SEED), no
+    repeats) for every view and every run with the same arguments, so that two builds compare value for value; a smaller view is
+    written whole, shaped (planes, n, n)."""
+    torch = run.env.torch
+    run.sync()
+    os.makedirs(out_dir, exist_ok=True)
+    n, nzo = run.n, run.nzo
+    total = n * n * nzo
+    share = max(1, DUMP_VALUES // max(1, run.total_views))
+    idx = None
+    if total > share:
+        pick = np.random.default_rng(DUMP_SEED).choice(total, size=share, replace=False)
+        idx = torch.from_numpy(np.sort(pick).astype(np.int64)).to(run.env.dev)
+    written = []
+    for i, v in enumerate(run.my_views):
+        a = run.acq[i]
+        host = (a.index_select(0, idx) if idx is not None else a.view(nzo, n, n)).to(torch.float32).cpu().numpy()
+        path = os.path.join(out_dir, f"acq_view{v}.npy")
+        np.save(path, host)
+        written.append(path)
+    return written
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1111,9 +1158,12 @@ def main():
             stage = read_stage()
         for c in ctxs:
             c.enable_timing(False)
+    if args.dump_outputs:
+        dump_outputs(run, args.dump_outputs)          # every rank: its own views (the last timed step's acquisitions)
 
+    full = args.full
     serial_leg = None
-    if rank == 0 and not multi and not args.serial and my_views:
+    if rank == 0 and full and not multi and not args.serial and my_views:
         # the roofline's source: the same K steps with both overlaps off -- one kernel at a time on the context's stream, HIP
         # events around every stage (on that stream), so that stage times are the kernels' own durations
         set_overlap(False)
@@ -1133,10 +1183,10 @@ def main():
                       "note": "options tail_overlap = psf_overlap = 0 (kernels strictly one at a time): the leg `roofline` is read from"}
         set_overlap(True)
 
-    plane_stats = ctx.plane_stats() if (rank == 0 and my_views) else None      # of the leg `roofline` is read from (before the dense leg)
-    queue_stats = ctx.queue_stats() if (rank == 0 and my_views and args.snr >= 0) else None     # the sampler's work queue after the timed steps
+    plane_stats = ctx.plane_stats() if (rank == 0 and my_views and stage) else None      # of the leg `roofline` is read from (before the dense leg)
+    queue_stats = ctx.queue_stats() if (rank == 0 and full and my_views and args.snr >= 0) else None     # the sampler's work queue after the timed steps
     no_empty = None
-    if rank == 0 and not multi and my_views and args.conv_method == 1 and not args.no_dense_leg:
+    if rank == 0 and full and not multi and my_views and args.conv_method == 1 and not args.no_dense_leg:
         # The rotate + attenuate + x-transform kernel skips the fp64 blends and the transforms of rows that hold no non-zero voxel
         # (exact; the phantom, like the reference's drawSpheres volume, is empty outside the specimen).  How much of `value` is
         # owed to that: the same K serial steps on the SAME phantom plus 1e-6 everywhere -- no empty row left, the same intensity
@@ -1248,7 +1298,7 @@ def main():
             out["roofline"] = roofline_record(mvs, stage, nvox, n * n * nzo, n, args.psf, args.conv_method, traffic, note,
                                               view_wall_ms=wall_view, overlapped=stage_overlapped, plane_stats=plane_stats)
             out["kernel_sha"] = kernel_sha
-    if rank == 0 and not multi and len(ctxs) == 1 and not args.no_main_iteration and args.conv_method == 1 and my_views:
+    if rank == 0 and full and not multi and len(ctxs) == 1 and not args.no_main_iteration and args.conv_method == 1 and my_views:
         # The whole body of `main`'s view loop (SimulateMultiViewDataset.java:567-613): the view, then makeIsotropic and the
         # rotate-backs of the isotropic view, the weight image and the PSF (mvsim_simulate_iteration_dev), all outputs in HBM.
         try:
@@ -1275,7 +1325,7 @@ def main():
             del extra
         except Exception as e:
             out["main_iteration"] = {"failed": repr(e)}
-    if rank == 0 and not multi and len(ctxs) == 1 and not args.no_two_streams and args.conv_method == 1:
+    if rank == 0 and full and not multi and len(ctxs) == 1 and not args.no_two_streams and args.conv_method == 1:
         # two contexts on the GPU: views alternate between them (reported beside `value`)
         def timed_steps():
             for _ in range(max(1, args.warmup)):
@@ -1347,7 +1397,7 @@ def main():
         # The legs below are collectives over every rank: a rank that dies inside one leaves the others waiting.  The line of record
         # exists already; if the legs have not come back after five minutes, rank 0 prints it without them and ends the job.
         watchdog = start_watchdog(out, 300.0, "the legs behind the line of record")
-    if multi and args.conv_method == 1 and n <= 512 and not legs_error:
+    if full and multi and args.conv_method == 1 and n <= 512 and not legs_error:
         # the other sizes north_star names, on the N > 1 data path: 1024^3 views sharded v % N (`size_1024`) and BASELINE configs[3] as
         # stated -- every 1024^3 view cut into N z slabs (`tiled_1024`).  Every rank takes part; rank 0 reports.  (The legs run at twice
         # the main line's edge: 1024 for the 512^3 line of record, 512 for the tests' 256^3 rehearsals.)
@@ -1391,24 +1441,24 @@ def main():
     if rank == 0:
         out.update(legs)
     if rank == 0:
-        if not multi and not args.no_end_to_end and args.conv_method == 1:
+        if full and not multi and not args.no_end_to_end and args.conv_method == 1:
             try:
                 out["end_to_end"] = end_to_end_record(mvs, dev_index, gt_host, [psf_raw], angles, args.inc, args.snr)
             except Exception as e:  # reported extras never cost the GPU line
                 out["end_to_end"] = {"failed": repr(e)}
-        if not multi and not args.no_size_1024 and n == 512 and args.conv_method == 1:
+        if full and not multi and not args.no_size_1024 and n == 512 and args.conv_method == 1:
             try:
                 g512 = torch.from_numpy(gt_host.reshape(-1)).to(dev)
                 out["size_1024"] = size_1024_record(mvs, torch, dev, dev_index, g512, psf_raw, args.inc, args.snr)
                 del g512
             except Exception as e:
                 out["size_1024"] = {"failed": repr(e)}
-        if not multi and not args.no_small_views and args.conv_method == 1:
+        if full and not multi and not args.no_small_views and args.conv_method == 1:
             try:
                 out["small_views"] = small_views_record(mvs, synth, dev_index)
             except Exception as e:
                 out["small_views"] = {"failed": repr(e)}
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(gt_host, psf_raw, angles[0], args.inc, args.snr, args.cpu_slab, args.cpu_poisson_planes)
             except Exception as e:  # the baseline is a reported extra; never lose the GPU line over it

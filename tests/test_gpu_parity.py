@@ -1990,7 +1990,7 @@ def test_bench_rehearses_the_multi_gpu_data_path(tmp_path):
     for extra in (["--broadcast", "scatter_allgather", "--no-broadcast-ab"], ["--broadcast", "ring", "--serial", "--no-broadcast-ab"],
                   ["--broadcast", "peer_copy", "--no-broadcast-ab"], ["--broadcast", "pipelined", "--no-broadcast-ab"], []):
         r = subprocess.run([sys.executable, bench, "--rehearse-multi", "--size", "256", "--psf", "15", "--steps", "2", "--warmup", "1",
-                            "--no-cpu-baseline"] + extra, capture_output=True, text=True, timeout=600)
+                            "--no-cpu-baseline", "--full"] + extra, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
         d = json.loads(line)
@@ -2135,7 +2135,7 @@ def test_split_y_lines_in_place_behind_the_padded_z_transform(mvs, synth, orc):
 
 
 def test_bench_line_carries_the_contract_keys():
-    """bench.py's one JSON line (small volume, so that the test stays short): the contract keys, `value` on the library
+    """bench.py --full's one JSON line (small volume, so that the test stays short): the contract keys, `value` on the library
     defaults with a serial leg beside it, a roofline whose fused-byte fractions never exceed 1 and that says where the x
     transform ran, a two-mode CPU baseline labelled as a port; and with --conv-method 2 the direct stencil against the fp32
     vector peak."""
@@ -2144,7 +2144,7 @@ def test_bench_line_carries_the_contract_keys():
     import sys
     bench = os.path.join(ROOT, "bench.py")
     r = subprocess.run([sys.executable, bench, "--size", "256", "--psf", "15", "--steps", "2", "--warmup", "1", "--cpu-slab", "8",
-                        "--no-end-to-end", "--no-two-streams"], capture_output=True, text=True, timeout=900,
+                        "--no-end-to-end", "--no-two-streams", "--full"], capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, MVSIM_OPTIONS="fused_fftx=1"))       # (auto takes the fused kernel from 131072 columns up)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -2169,6 +2169,46 @@ def test_bench_line_carries_the_contract_keys():
     assert rl["flop"] == 2.0 * 15 ** 3 * 128 ** 3 and rl["stencil_geometry"]["blocks_per_cu"] == 2
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """bench.py without --full: the line of record and nothing beside it (no serial leg, roofline, CPU baseline or other record), over
+    exactly --steps timed steps; --dump-outputs writes the acquisitions of the last timed step as float32 .npy files, and two runs with
+    the same arguments write the same arrays.  Views larger than their share of the dump's budget are written as a fixed sample."""
+    import json
+    import subprocess
+    import sys
+    bench = os.path.join(ROOT, "bench.py")
+
+    def run(size, steps, out_dir):
+        r = subprocess.run([sys.executable, bench, "--size", str(size), "--psf", "15", "--steps", str(steps), "--warmup", "1",
+                            "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    dumps = []
+    for k in range(2):
+        d = run(64, 3, tmp_path / f"whole{k}")
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["higher_is_better"] is True and d["value_dense"] is None
+        assert abs(d["value"] - 8 * 64 ** 3 / d["ms_per_step"] / 1e3) <= 1e-9 * d["value"]
+        for key in ("serial", "roofline", "cpu_baseline", "no_empty_space", "poisson_queue", "main_iteration", "two_streams",
+                    "end_to_end", "size_1024", "small_views"):
+            assert key not in d, key
+        files = sorted(os.listdir(tmp_path / f"whole{k}"))
+        assert files == sorted(f"acq_view{v}.npy" for v in range(8))
+        arrs = {f: np.load(tmp_path / f"whole{k}" / f) for f in files}
+        for a in arrs.values():
+            assert a.dtype == np.float32 and a.shape == (64, 64, 64) and float(a.max()) > 0      # 2^18 voxels: whole views
+        dumps.append(arrs)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+    run(128, 1, tmp_path / "sampled")                 # 2^21 voxels a view, 2^20 of them written
+    paths = [tmp_path / "sampled" / f"acq_view{v}.npy" for v in range(8)]
+    assert sum(os.path.getsize(p) for p in paths) <= 64 << 20
+    for p in paths:
+        a = np.load(p)
+        assert a.dtype == np.float32 and a.shape == (1 << 20,) and float(a.max()) > 0
+
+
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher around it: bench.py starts the two ranks itself (children with RANK /
     WORLD_SIZE / MASTER_* set, before anything touches the GPU in the parent) and rank 0's line says n_gpus 2 with both
@@ -2181,7 +2221,7 @@ def test_bench_launches_its_own_ranks():
     bench = os.path.join(ROOT, "bench.py")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, bench, "--gpus", "2", "--backend", "gloo", "--size", "256", "--psf", "15", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
+                        "--warmup", "1", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["config"]["ranks_seen"]["torch"] == 2

@@ -162,12 +162,12 @@ def test_tiff_reader_and_imagej_writer_round_trip(mvs, synth, tmp_path):
 def test_reference_psf_stacks_through_tiffio(synth):
     """The only data the reference holds for the path: the 18 measured PSF stacks `src/main/resources/Angle*.tif`, loaded through
     `Tools.open(file, true)` = read + makeSquare (Tools.java:297-349) at SimulateMultiViewDataset.java:579.  The files are GPL data
-    and stay in /root/reference; `tests/golden/psf_tiff_facts.json` holds FACTS about them derived through this repository's reader
-    (`tests/golden/make_psf_tiff_facts.py`).  Where the reference is present (the build container) every fact is re-derived from the
-    files and must equal the JSON -- including that `tiffio.save_tiff` reproduces all 18 files BYTE FOR BYTE from the decoded pixels
-    and the description's display range (the writer = Tools.save, Tools.java:88-105) and that an independent numpy decode agrees with
-    `tiffio.open_tiff`.  Everywhere (the GPU box has no /root/reference) the JSON must be self-consistent, and the synthetic stand-in
-    the tests use instead of the files must lie inside the range the real stacks span."""
+    and stay with the reference; `tests/golden/psf_tiff_facts.json` holds FACTS about them derived through this repository's reader
+    (`tests/golden/make_psf_tiff_facts.py`, whose `--check` re-derives every fact from the files where a checkout of the reference is
+    at hand -- including that `tiffio.save_tiff` reproduces all 18 files BYTE FOR BYTE from the decoded pixels and the description's
+    display range (the writer = Tools.save, Tools.java:88-105) and that an independent numpy decode agrees with `tiffio.open_tiff`).
+    This test reads nothing outside the repository: the JSON must be self-consistent, and the synthetic stand-in the tests use
+    instead of the files must lie inside the range the real stacks span."""
     import json
     gold = os.path.join(ROOT, "tests", "golden")
     rec = json.load(open(os.path.join(gold, "psf_tiff_facts.json")))
@@ -200,8 +200,6 @@ def test_reference_psf_stacks_through_tiffio(synth):
     assert r["rank1_energy"][0] <= facts._rank1_energy(g) <= r["rank1_energy"][1]
     for ax, key in enumerate(("sigma_x", "sigma_y", "sigma_z")):
         assert r[key][0] * 0.99 <= sig[ax] <= r[key][1] * 1.01, (key, sig[ax], r[key])
-    if os.path.isdir(facts.REF_DIR):
-        assert json.loads(json.dumps(facts.collect())) == rec          # every fact again, from the reference's own files
 
 
 def test_tiff_reader_little_endian_multi_strip_and_rejections(mvs, tmp_path):
@@ -282,6 +280,28 @@ def test_bench_self_launcher_starts_its_ranks():
     mism = subprocess.run([sys.executable, bench, "--gpus", "8", "--dry-run-launch"], capture_output=True, text=True, timeout=120,
                           env=dict(_bench_env(), WORLD_SIZE="1", RANK="0"))
     assert mism.returncode != 0 and "WORLD_SIZE=1" in mism.stderr
+
+
+def test_bench_options_of_the_plain_run():
+    """--full and --dump-outputs exist and are off by default; --steps sets the timed steps, so fewer than one is refused before anything
+    starts."""
+    import subprocess
+    import sys
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py"]
+        a = bench.parse_args()
+        assert a.full is False and a.dump_outputs is None and a.steps >= 1
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "d", "--steps", "7"]
+        a = bench.parse_args()
+        assert a.full is True and a.dump_outputs == "d" and a.steps == 7
+    finally:
+        sys.argv = argv
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dry-run-launch"], capture_output=True, text=True,
+                       timeout=120, env=_bench_env())
+    assert r.returncode != 0 and "--steps" in r.stderr
 
 
 def test_bench_control_plane_defaults_to_gloo_and_the_fastest_broadcast_wins():

@@ -1,15 +1,17 @@
 # A/B harness for experiments on the GPU box: bash tools/ab.sh "<pytest -k expr>" "<opt string 1>" "<opt string 2>" ...
 set -e
+export OUT=${OUT:-tool_out}   # output directory (logs, profiler output, kept libraries)
+mkdir -p "$OUT"
 K="$1"; shift
 if [ -n "$K" ]; then
-  python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "$K" > gpurun_out/ab_tests.log 2>&1 || { tail -40 gpurun_out/ab_tests.log; exit 1; }
-  tail -1 gpurun_out/ab_tests.log
+  python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "$K" > $OUT/ab_tests.log 2>&1 || { tail -40 $OUT/ab_tests.log; exit 1; }
+  tail -1 $OUT/ab_tests.log
 fi
 i=0
 for o in "$@"; do
   i=$((i+1))
-  MVSIM_OPTIONS="$o" python bench.py --no-cpu-baseline --no-end-to-end --no-size-1024 --no-two-streams --no-compact-queue-leg > gpurun_out/ab_$i.log 2>&1 || { tail -5 gpurun_out/ab_$i.log; exit 1; }
-  python - "$o" gpurun_out/ab_$i.log <<'PY'
+  MVSIM_OPTIONS="$o" python bench.py --full --no-cpu-baseline --no-end-to-end --no-size-1024 --no-two-streams --no-compact-queue-leg > $OUT/ab_$i.log 2>&1 || { tail -5 $OUT/ab_$i.log; exit 1; }
+  python - "$o" $OUT/ab_$i.log <<'PY'
 import json, sys
 for l in open(sys.argv[2]):
     if l.startswith("{"):

@@ -1,7 +1,9 @@
 # A/B on environment settings with the default bench line: bash tools/ab_env.sh "VAR=1 OTHER=2" "VAR=0" ...
 set -e
+export OUT=${OUT:-tool_out}   # output directory (logs, profiler output, kept libraries)
+mkdir -p "$OUT"
 for e in "$@"; do
-  env $e python bench.py --no-cpu-baseline --no-end-to-end --no-size-1024 --no-two-streams 2>gpurun_out/ab_env.err | python -c "
+  env $e python bench.py --full --no-cpu-baseline --no-end-to-end --no-size-1024 --no-two-streams 2>$OUT/ab_env.err | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

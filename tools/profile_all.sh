@@ -23,7 +23,7 @@ rocprofv3 --pmc WRITE_SIZE -d $O/write1k -o run -- python3 $V1024 > $O/write1k.l
 python3 tools/pmc_traffic.py $O/fetch1k $O/write1k 6 --json $O/traffic_1024.json --size 1024 --psf 31 --inc 1 --workload "1024^3, one view at a time (6 launches), 31^3 PSF, inc 1, the 512^3 phantom up-sampled 2x" --command "python3 $V1024" > $O/pmc_hbm_traffic_1024.txt
 rm -rf $O/fetch1k $O/write1k
 echo "traffic 1024 done"
-MVSIM_TRAFFIC_JSON=$O/traffic.json MVSIM_TRAFFIC_JSON_1024=$O/traffic_1024.json python3 bench.py > $O/bench.json 2> $O/bench.err
+MVSIM_TRAFFIC_JSON=$O/traffic.json MVSIM_TRAFFIC_JSON_1024=$O/traffic_1024.json python3 bench.py --full > $O/bench.json 2> $O/bench.err
 echo "bench done"
 rocprofv3 --kernel-trace --stats -d $O/trace -o run -- python3 $BENCH > $O/trace.log 2>&1
 python3 tools/kstats.py $O/trace 20 $O/kernel_stats.csv > $O/kernel_stats.txt
@@ -34,7 +34,7 @@ echo "counters done"
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS -d $O/sq -o run -- python3 $BENCH --steps 1 --warmup 1 > $O/sq.log 2>&1
 python3 tools/pmc_sq_report.py $O/sq > $O/sq_counters.txt
 # the whole iteration of main's loop (mvsim_simulate_iteration_dev): the rotate-back kernels and makeIsotropic
-rocprofv3 --kernel-trace --stats -d $O/trace_it -o run -- python3 bench.py --serial --no-cpu-baseline --no-end-to-end --no-size-1024 --no-two-streams --no-dense-leg --no-small-views --no-compact-queue-leg > $O/trace_it.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/trace_it -o run -- python3 bench.py --full --serial --no-cpu-baseline --no-end-to-end --no-size-1024 --no-two-streams --no-dense-leg --no-small-views --no-compact-queue-leg > $O/trace_it.log 2>&1
 python3 tools/kstats.py $O/trace_it 24 $O/main_iteration_kernel_stats.csv > $O/main_iteration_kernel_stats.txt
 echo "iteration trace done"
 # HBM traffic of the views of BASELINE configs[3] and configs[4]: same two counter passes, one view at a time
