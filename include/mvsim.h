@@ -73,7 +73,8 @@ int  mvsim_join(mvsim_ctx* ctx);
  * extract + Poisson phase 1 in the epilogue of the convolution's last pass), "fused_fftx" = auto|1|0 (per-view pipeline: rotate + attenuate + the x transform of
  * the FFT convolution as one kernel, so that the attenuated volume crosses HBM only when requested; auto = from 131072
  * columns up), "attenuate" = serial|scan (mvsim_attenuate3d
- * as a wavefront-level prefix scan along the illumination axis: parallel in y, not bit-identical to the serial walk).
+ * as a wavefront-level prefix scan along the illumination axis: parallel in y, not bit-identical to the serial walk), "beads_pair_cap" =
+ * 1024..2^31 ((brick, bead) pairs the bead renderer bins at once; larger calls run in chunks with identical results).
  * MVSIM_OPTIONS="name=value;name=value" sets any of them process-wide.  Unknown names or values: MVSIM_EINVAL. */
 int  mvsim_set_option(mvsim_ctx* ctx, const char* name, const char* value);
 /* Release cached FFT plans / workspaces / PSF spectra held by the context. */
@@ -156,6 +157,37 @@ int mvsim_splat_spheres(mvsim_ctx* ctx, float* img, const int64_t dim[3], const 
 int mvsim_splat_spheres_dev(mvsim_ctx* ctx, float* img_dev, const int64_t dim[3], const mvsim_sphere* spheres_host, int64_t n);
 /* SMVD:394-424 downSample2x: out has dim[d]/2 - 1 samples per dimension. */
 int mvsim_downsample2x(mvsim_ctx* ctx, const float* in, const int64_t dim[3], float* out);
+
+/* ---- bead images: net.preibisch.simulation.SimulateBeads / SimulateBeads2 -------------------------------------------------
+ *   SB  = src/main/java/net/preibisch/simulation/SimulateBeads.java
+ * SB:151-166 randomPoints(numPoints, range, rnd): for each point, d = 0, 1, 2: rnd.nextDouble() * (max[d] - min[d]) + min[d]
+ * (the difference of two longs, as a double).  rnd_state is the 48-bit state of the caller's java.util.Random, advanced
+ * exactly as the reference advances it (both bead classes seed `new Random(535)`).  xyz receives n * 3 doubles, x first. */
+int mvsim_beads_random_points(uint64_t* rnd_state, int64_t n, const int64_t min[3], const int64_t max[3], double* xyz);
+/* SB:97-118 renderPoints + SB:168-205 addGaussian for nviews views in one call.  The image of every view has
+ * dim[d] = max[d] - min[d] voxels (one less than the interval, as the reference allocates it; x fastest).
+ *   view_offsets == NULL: every view renders the same n points; else view v renders points [view_offsets[v], view_offsets[v+1]).
+ *   m12 == NULL: the points as given (renderPoints of lists that are already transformed); else nviews row-major 3x4 matrices
+ *   applied first in fp64, ((x m00 + y m01) + z m02) + m03 per row (AffineModel3D / AffineTransform3D.apply).
+ * Then isInsideAdjust (SB:120-130: p[d] -= min[d], kept iff 0 <= p[d] <= dim[d]) and, per kept bead IN LIST ORDER, every voxel of
+ * its box (getSuggestedKernelDiameter(sigma) * 2 voxels per axis around (int)Math.round(p), clipped to the image) becomes
+ * voxel + (float)(prod_d exp(-(x_d * x_d) / (2 sigma_d sigma_d))) * 1000.0f in float: bit for bit the reference's sequential sum.
+ * out_f32[v] (float) and / or out_u16[v] (LegacySimulatedBeadsImgLoader.getImage: Math.round(float), then the low 16 bits) receive the
+ * images; either list may be NULL, not both.  Deliberate deviations: sigma must be finite and > 0 (the reference would produce NaN
+ * or degenerate boxes), and a bead whose transformed coordinates are NaN is dropped (the reference would write NaN over its box).
+ * MVSIM_EINVAL also for an image dimension < 1, inconsistent view offsets and matrices with non-finite entries.
+ * Host buffers, synchronous. */
+int mvsim_render_beads(mvsim_ctx* ctx, const double* xyz, const int64_t* view_offsets, int64_t n, const double* m12, int nviews,
+                       const int64_t min[3], const int64_t max[3], const double sigma[3], float* const* out_f32, uint16_t* const* out_u16);
+/* The same with DEVICE outputs (the point list, offsets and matrices stay host arrays): returns once the lists are on the device,
+ * the kernels run asynchronously on the context stream -- the images can feed the other *_dev entry points directly. */
+int mvsim_render_beads_dev(mvsim_ctx* ctx, const double* xyz, const int64_t* view_offsets, int64_t n, const double* m12, int nviews,
+                           const int64_t min[3], const int64_t max[3], const double sigma[3], float* const* out_f32,
+                           uint16_t* const* out_u16);
+/* LegacySimulatedBeadsImgLoader.normalize (:120-136), in place over n floats: float min / max, then (v - min) / (max - min) in
+ * float (a constant image gives NaN, as in the reference). */
+int mvsim_beads_normalize(mvsim_ctx* ctx, float* img, int64_t n);
+int mvsim_beads_normalize_dev(mvsim_ctx* ctx, float* img_dev, int64_t n);
 
 /* ---- stage operators, device-resident buffers (asynchronous on the context stream) ------ */
 /* (mvsim_draw_spheres_dev returns after the host walk; the compositing kernels are asynchronous.) */

@@ -212,6 +212,71 @@ JNIEXPORT void JNICALL JNI_FN(axisRotation)(JNIEnv* env, jclass, jlongArray dim,
     env->SetDoubleArrayRegion(m12, 0, 12, m);
 }
 
+// ---- bead images (mvsim_render_beads) -----------------------------------------------------------------------------------
+namespace {
+// host pointer of a direct buffer (any element type) holding at least `need` elements; nullptr (+ exception) otherwise
+void* any_ptr(JNIEnv* env, jobject buf, int64_t need, const char* what)
+{
+    if (env->ExceptionCheck()) return nullptr;
+    if (!buf) { throw_new(env, "java/lang/IllegalArgumentException", what); return nullptr; }
+    void* p = env->GetDirectBufferAddress(buf);
+    const jlong cap = env->GetDirectBufferCapacity(buf);
+    if (!p || cap < need) { throw_new(env, "java/lang/IllegalArgumentException", what); return nullptr; }
+    return p;
+}
+}  // namespace
+
+JNIEXPORT void JNICALL JNI_FN(renderBeads)(JNIEnv* env, jclass, jlong h, jobject xyz, jlong n, jlongArray view_offsets, jobject m12,
+                                           jint nviews, jlongArray interval, jdouble sx, jdouble sy, jdouble sz, jobjectArray out_f32,
+                                           jobjectArray out_u16)
+{
+    if (nviews < 1 || n < 0) { throw_new(env, "java/lang/IllegalArgumentException", "renderBeads: nviews >= 1 and n >= 0 expected"); return; }
+    if (!interval || env->GetArrayLength(interval) < 6) { throw_new(env, "java/lang/IllegalArgumentException", "renderBeads: long[6] interval expected"); return; }
+    jlong iv[6];
+    env->GetLongArrayRegion(interval, 0, 6, iv);
+    if (env->ExceptionCheck()) return;
+    int64_t mn[3] = {iv[0], iv[1], iv[2]}, mx[3] = {iv[3], iv[4], iv[5]};
+    for (int d = 0; d < 3; ++d)
+        if (mx[d] - mn[d] < 1) { throw_new(env, "java/lang/IllegalArgumentException", "renderBeads: image dimension (max - min) must be >= 1"); return; }
+    const int64_t nv = (mx[0] - mn[0]) * (mx[1] - mn[1]) * (mx[2] - mn[2]);
+    const double* pts = nullptr;
+    if (n > 0) {
+        pts = static_cast<const double*>(any_ptr(env, xyz, 3 * n, "renderBeads: point buffer smaller than 3 n doubles"));
+        if (!pts) return;
+    }
+    std::vector<int64_t> offs;
+    if (view_offsets) {
+        if (env->GetArrayLength(view_offsets) != nviews + 1) { throw_new(env, "java/lang/IllegalArgumentException", "renderBeads: nviews + 1 offsets expected"); return; }
+        offs.resize(static_cast<size_t>(nviews) + 1);
+        std::vector<jlong> tmp(offs.size());
+        env->GetLongArrayRegion(view_offsets, 0, nviews + 1, tmp.data());
+        if (env->ExceptionCheck()) return;
+        for (size_t i = 0; i < tmp.size(); ++i) offs[i] = tmp[i];
+    }
+    const double* m = nullptr;
+    if (m12) {
+        m = static_cast<const double*>(any_ptr(env, m12, 12 * static_cast<int64_t>(nviews), "renderBeads: matrix buffer smaller than 12 nviews doubles"));
+        if (!m) return;
+    }
+    std::vector<float*> f;
+    std::vector<uint16_t*> u;
+    for (int k = 0; k < 2; ++k) {
+        jobjectArray list = k == 0 ? out_f32 : out_u16;
+        if (!list) continue;
+        if (env->GetArrayLength(list) != nviews) { throw_new(env, "java/lang/IllegalArgumentException", "renderBeads: one output buffer per view expected"); return; }
+        for (jint v = 0; v < nviews; ++v) {
+            jobject b = env->GetObjectArrayElement(list, v);
+            if (env->ExceptionCheck()) return;
+            void* p = any_ptr(env, b, nv, "renderBeads: output buffer smaller than the image");
+            if (!p) return;
+            if (k == 0) f.push_back(static_cast<float*>(p)); else u.push_back(static_cast<uint16_t*>(p));
+        }
+    }
+    const double sigma[3] = {sx, sy, sz};
+    throw_for(env, mvsim_render_beads(ctx_of(h), pts, view_offsets ? offs.data() : nullptr, n, m, nviews, mn, mx, sigma,
+                                      out_f32 ? f.data() : nullptr, out_u16 ? u.data() : nullptr));
+}
+
 // ---- per-stage operators with z-slab lists (mvsim_*_zslabs) ----------------------------------------------------------
 namespace {
 // the host pointers and plane counts of a FloatBuffer[] / long[] pair; every buffer is checked against plane * nz[i] floats

@@ -31,6 +31,11 @@ final class MvsimNative
 	static native void makeIsotropic( long ctx, FloatBuffer in, long[] dim, int inc, FloatBuffer out );
 	static native void computeWeightImage( long ctx, long[] dim, FloatBuffer out );
 	static native void axisRotation( long[] dim, int axis, int degrees, double[] m12 );
+	// SimulateBeads.renderPoints for nviews views (mvsim_render_beads): xyz = n * 3 doubles, viewOffsets = nviews + 1 entries or null
+	// (every view renders all points), m12 = nviews row-major 3x4 matrices or null (points as given), interval = {min x, y, z, max x, y, z};
+	// images of (max - min) voxels per axis; either output list may be null
+	static native void renderBeads( long ctx, java.nio.DoubleBuffer xyz, long n, long[] viewOffsets, java.nio.DoubleBuffer m12, int nviews,
+			long[] interval, double sigmaX, double sigmaY, double sigmaZ, FloatBuffer[] outF32, java.nio.ShortBuffer[] outU16 );
 
 	// the per-stage operators with volumes as z-slab lists (mvsim_*_zslabs): in[i] holds inNz[i] planes, out[j] receives outNz[j];
 	// this is how images beyond one 2 GiB direct buffer (2^29 voxels) cross the boundary -- a 512^3 image is a list of one

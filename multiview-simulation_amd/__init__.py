@@ -25,7 +25,7 @@ import numpy as np
 from . import _lib
 from ._lib import MvsimError, MvsimNoDeviceError, Sphere, Timings, ViewOutputs, ViewParams  # noqa: F401
 
-__all__ = ["Context", "Group", "JavaRandom", "SimulateMultiViewDataset", "Tools", "broadcast_plan", "default_context", "MvsimError",
+__all__ = ["AffineTransform3D", "Context", "Group", "JavaRandom", "SimulateBeads", "SimulateBeads2", "SimulateMultiViewDataset", "Tools", "broadcast_plan", "default_context", "MvsimError",
            "MvsimNoDeviceError", "ViewParams", "shard_views", "version"]
 
 
@@ -284,6 +284,63 @@ class Context:
         _check_inplace(img)
         arr = (Sphere * len(spheres))(*[Sphere(int(cx), int(cy), int(cz), int(r), float(v)) for cx, cy, cz, r, v in spheres])
         _lib.check(self._L.mvsim_splat_spheres(self._h, _ptr(img), _dim(img), arr, len(spheres)))
+
+    # -- bead images (SimulateBeads.java:97-205, beads.hip)
+    @staticmethod
+    def _beads_args(points, interval, sigma, matrices, view_offsets):
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        (mn, mx) = interval
+        mn = (C.c_int64 * 3)(*[int(v) for v in mn])
+        mx = (C.c_int64 * 3)(*[int(v) for v in mx])
+        sig = (C.c_double * 3)(*[float(v) for v in sigma])
+        m = None
+        if matrices is not None:
+            m = np.ascontiguousarray(matrices, dtype=np.float64).reshape(-1, 12)
+        offs = None
+        if view_offsets is not None:
+            offs = np.ascontiguousarray(view_offsets, dtype=np.int64)
+        nviews = len(m) if m is not None else (len(offs) - 1 if offs is not None else 1)
+        if m is not None and offs is not None and len(offs) != nviews + 1:
+            raise ValueError("view_offsets must have one entry more than there are matrices")
+        shape = tuple(int(mx[d] - mn[d]) for d in (2, 1, 0))
+        return pts, mn, mx, sig, m, offs, nviews, shape
+
+    @staticmethod
+    def _dptr(a):
+        return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+
+    def render_beads(self, points, interval, sigma, matrices=None, view_offsets=None, f32: bool = True, u16: bool = False) -> dict:
+        """SimulateBeads.renderPoints for every view in one call: ``points`` (n, 3) x first; ``interval`` = ((min x, y, z), (max x, y, z));
+        ``matrices`` (V, 3, 4) applied first (None: the points as given); ``view_offsets`` (V + 1): view v renders points
+        [off[v], off[v+1]) (None: all points for every view).  Returns {"f32": [...], "u16": [...]} of (Nz, Ny, Nx) images, Nd = max - min."""
+        pts, mn, mx, sig, m, offs, nviews, shape = self._beads_args(points, interval, sigma, matrices, view_offsets)
+        if min(shape) < 1:
+            raise ValueError("image dimension (interval max - min) must be >= 1")
+        out = {}
+        lists = {}
+        for kind, dt, want in (("f32", np.float32, f32), ("u16", np.uint16, u16)):
+            if want:
+                out[kind] = [np.empty(shape, dtype=dt) for _ in range(nviews)]
+                lists[kind] = (C.c_void_p * nviews)(*[a.ctypes.data for a in out[kind]])
+        _lib.check(self._L.mvsim_render_beads(self._h, self._dptr(pts), None if offs is None else offs.ctypes.data_as(C.POINTER(C.c_int64)),
+                                              len(pts), self._dptr(m), nviews, mn, mx, sig, lists.get("f32"), lists.get("u16")))
+        return out
+
+    def render_beads_dev(self, points, interval, sigma, f32_dptrs=None, u16_dptrs=None, matrices=None, view_offsets=None) -> None:
+        """The same into device images (lists of device pointers, one per view; either may be None), asynchronous on the stream."""
+        pts, mn, mx, sig, m, offs, nviews, _ = self._beads_args(points, interval, sigma, matrices, view_offsets)
+        lf = None if f32_dptrs is None else (C.c_void_p * nviews)(*[int(p) for p in f32_dptrs])
+        lu = None if u16_dptrs is None else (C.c_void_p * nviews)(*[int(p) for p in u16_dptrs])
+        _lib.check(self._L.mvsim_render_beads_dev(self._h, self._dptr(pts), None if offs is None else offs.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                  len(pts), self._dptr(m), nviews, mn, mx, sig, lf, lu))
+
+    def beads_normalize(self, img: np.ndarray) -> None:
+        """LegacySimulatedBeadsImgLoader.normalize, in place on a contiguous float32 image."""
+        _check_inplace(img)
+        _lib.check(self._L.mvsim_beads_normalize(self._h, _ptr(img), img.size))
+
+    def beads_normalize_dev(self, dptr: int, n: int) -> None:
+        _lib.check(self._L.mvsim_beads_normalize_dev(self._h, C.c_void_p(dptr), n))
 
     def downsample2x(self, img) -> np.ndarray:
         v = _as_volume(img)
@@ -985,3 +1042,6 @@ class SimulateTileStitching:
             t[1] -= 0.5
         t[2] /= self.lightsheetSpacing
         return t
+
+
+from .beads import AffineTransform3D, SimulateBeads, SimulateBeads2  # noqa: E402

@@ -162,6 +162,13 @@ SIGNATURES = {
     "mvsim_group_broadcast_volume": (C.c_int, [_vp, _vp, _i64p]),
     "mvsim_group_simulate_views": (C.c_int, [_vp, C.POINTER(_vp), _i64p, C.POINTER(ViewParams), C.c_int, C.POINTER(_vp)]),
     "mvsim_shard_views": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "mvsim_beads_random_points": (C.c_int, [C.POINTER(C.c_uint64), C.c_int64, _i64p, _i64p, C.POINTER(C.c_double)]),
+    "mvsim_render_beads": (C.c_int, [_vp, C.POINTER(C.c_double), _i64p, C.c_int64, C.POINTER(C.c_double), C.c_int, _i64p, _i64p,
+                                     C.POINTER(C.c_double), C.POINTER(_vp), C.POINTER(_vp)]),
+    "mvsim_render_beads_dev": (C.c_int, [_vp, C.POINTER(C.c_double), _i64p, C.c_int64, C.POINTER(C.c_double), C.c_int, _i64p, _i64p,
+                                         C.POINTER(C.c_double), C.POINTER(_vp), C.POINTER(_vp)]),
+    "mvsim_beads_normalize": (C.c_int, [_vp, _vp, C.c_int64]),
+    "mvsim_beads_normalize_dev": (C.c_int, [_vp, _vp, C.c_int64]),
 }
 
 _lib = None

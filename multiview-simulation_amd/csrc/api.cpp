@@ -75,6 +75,13 @@ int parse_option(Options& o, const char* name, const char* value)
         o.exp = k;
         return MVSIM_OK;
     }
+    if (n == "beads_pair_cap") {                       // pairs per chunk of the bead renderer: 1024 .. 2^31
+        if (v.empty() || v.size() > 10 || v.find_first_not_of("0123456789") != std::string::npos) return MVSIM_EINVAL;
+        const long long k = atoll(v.c_str());
+        if (k < 1024 || k > (1LL << 31)) return MVSIM_EINVAL;
+        o.beads_pair_cap = k;
+        return MVSIM_OK;
+    }
     if (n == "fuse_tail") return flag(&o.fuse_tail);
     if (n == "psf_overlap") return flag(&o.psf_overlap);
     if (n == "fused_fftx") {
@@ -570,7 +577,7 @@ int mvsim_destroy(mvsim_ctx* ctx)
     view_graphs_release(ctx);
     fft_release(ctx);
     ctx->vol_a.release(); ctx->vol_b.release(); ctx->vol_c.release(); ctx->out_buf.release();
-    ctx->psf_dev.release(); ctx->view_tab.release(); ctx->sync_u16.release(); ctx->stencil_psf.release(); ctx->partials.release(); ctx->partials_e.release(); ctx->pqueue.release(); ctx->sphere_list.release(); ctx->weight_img.release(); ctx->weight_dim[0] = 0; ctx->plane_flags.release();
+    ctx->psf_dev.release(); ctx->view_tab.release(); ctx->sync_u16.release(); ctx->stencil_psf.release(); ctx->partials.release(); ctx->partials_e.release(); ctx->pqueue.release(); ctx->sphere_list.release(); beads_release(ctx); ctx->weight_img.release(); ctx->weight_dim[0] = 0; ctx->plane_flags.release();
     ctx->host_gt.release(); ctx->host_rot.release(); ctx->host_att.release(); ctx->host_con.release();
     ctx->pinned.release_all();
     if (ctx->ev_created)
@@ -625,7 +632,7 @@ int mvsim_release_caches(mvsim_ctx* ctx)
     view_graphs_release(ctx);                             // captured launches point into the workspaces released below
     fft_release(ctx);
     ctx->vol_a.release(); ctx->vol_b.release(); ctx->vol_c.release(); ctx->out_buf.release();
-    ctx->pqueue.release(); ctx->psf_dev.release(); ctx->view_tab.release(); ctx->sync_u16.release(); ctx->stencil_psf.release(); ctx->sphere_list.release(); ctx->weight_img.release(); ctx->weight_dim[0] = 0; ctx->plane_flags.release();
+    ctx->pqueue.release(); ctx->psf_dev.release(); ctx->view_tab.release(); ctx->sync_u16.release(); ctx->stencil_psf.release(); ctx->sphere_list.release(); beads_release(ctx); ctx->weight_img.release(); ctx->weight_dim[0] = 0; ctx->plane_flags.release();
     ctx->host_gt.release(); ctx->host_rot.release(); ctx->host_att.release(); ctx->host_con.release();
     if (ctx->sync_u16_host) { (void)hipHostFree(ctx->sync_u16_host); ctx->sync_u16_host = nullptr; ctx->sync_u16_host_bytes = 0; }
     return MVSIM_OK;
@@ -1852,6 +1859,108 @@ int mvsim_splat_spheres(mvsim_ctx* ctx, float* img, const int64_t dim[3], const 
     const size_t bytes = (size_t)nvox(dim) * sizeof(float);
     MVSIM_TRY(up(ctx, ctx->vol_a, img, bytes));
     MVSIM_TRY(splat_spheres_dev(ctx, ctx->vol_a.as<float>(), dim, spheres, n));
+    return down(ctx, img, ctx->vol_a.p, bytes);
+}
+
+// ---- bead images: SimulateBeads / SimulateBeads2 (beads.hip) ----------------------------------------------------------
+int mvsim_beads_random_points(uint64_t* rnd_state, int64_t n, const int64_t min[3], const int64_t max[3], double* xyz)
+{
+    MVSIM_CHECK_ARG(rnd_state && min && max && (xyz || n == 0), "null pointer");
+    MVSIM_CHECK_ARG(n >= 0, "negative number of points");
+    uint64_t s = *rnd_state & ((1ULL << 48) - 1);
+    auto next = [&s](int bits) {
+        s = (s * 0x5DEECE66DULL + 0xBULL) & ((1ULL << 48) - 1);
+        return (int64_t)(int32_t)(s >> (48 - bits));
+    };
+    for (int64_t i = 0; i < n; ++i)
+        for (int d = 0; d < 3; ++d) {                                  // SimulateBeads.java:159-160
+            const int64_t hi = next(26) << 27;
+            const double u = (double)(hi + next(27)) * 0x1.0p-53;   // nextDouble()
+            xyz[3 * i + d] = u * (double)(max[d] - min[d]) + (double)min[d];
+        }
+    *rnd_state = s;
+    return MVSIM_OK;
+}
+
+static int beads_check(const double* xyz, const int64_t* view_offsets, int64_t n, const double* m12, int nviews, const int64_t min[3],
+                       const int64_t max[3], const double sigma[3], const void* out_f32, const void* out_u16, int64_t dim[3])
+{
+    MVSIM_CHECK_ARG(min && max && sigma, "null interval or sigma");
+    MVSIM_CHECK_ARG(n >= 0 && (xyz || n == 0), "null point list or negative count");
+    MVSIM_CHECK_ARG(nviews >= 1, "renderBeads needs at least one view");
+    MVSIM_CHECK_ARG(out_f32 || out_u16, "renderBeads: no output list");
+    for (int d = 0; d < 3; ++d) {
+        dim[d] = max[d] - min[d];                                      // SimulateBeads.java:105-106: one voxel less than the interval
+        MVSIM_CHECK_ARG(dim[d] >= 1, "image dimension (interval max - min) must be >= 1");
+        MVSIM_CHECK_ARG(std::isfinite(sigma[d]) && sigma[d] > 0.0, "sigma must be finite and > 0");
+        MVSIM_CHECK_ARG(sigma[d] <= 1.0e4, "sigma must be <= 1e4");
+    }
+    MVSIM_CHECK_ARG(dim[0] <= (1 << 24) && dim[1] <= (1 << 24) && dim[2] <= (1 << 24), "image dimension too large");
+    if (view_offsets) {
+        MVSIM_CHECK_ARG(view_offsets[0] >= 0 && view_offsets[nviews] <= n, "view_offsets outside the point list");
+        for (int v = 0; v < nviews; ++v) MVSIM_CHECK_ARG(view_offsets[v] <= view_offsets[v + 1], "view_offsets must not decrease");
+    }
+    if (m12)
+        for (int64_t k = 0; k < 12 * (int64_t)nviews; ++k) MVSIM_CHECK_ARG(std::isfinite(m12[k]), "transform with a non-finite entry");
+    return MVSIM_OK;
+}
+
+int mvsim_render_beads_dev(mvsim_ctx* ctx, const double* xyz, const int64_t* view_offsets, int64_t n, const double* m12, int nviews,
+                           const int64_t min[3], const int64_t max[3], const double sigma[3], float* const* out_f32,
+                           uint16_t* const* out_u16)
+{
+    int64_t dim[3];                                          // the arguments first: their errors need no device
+    MVSIM_TRY(beads_check(xyz, view_offsets, n, m12, nviews, min, max, sigma, out_f32, out_u16, dim));
+    for (int v = 0; v < nviews; ++v)
+        MVSIM_CHECK_ARG((!out_f32 || out_f32[v]) && (!out_u16 || out_u16[v]), "renderBeads: null image in an output list");
+    MVSIM_TRY(set_device(ctx));
+    return render_beads_dev(ctx, xyz, view_offsets, n, m12, nviews, dim, min, sigma, out_f32, out_u16);
+}
+
+int mvsim_render_beads(mvsim_ctx* ctx, const double* xyz, const int64_t* view_offsets, int64_t n, const double* m12, int nviews,
+                       const int64_t min[3], const int64_t max[3], const double sigma[3], float* const* out_f32, uint16_t* const* out_u16)
+{
+    int64_t dim[3];                                          // the arguments first: their errors need no device
+    MVSIM_TRY(beads_check(xyz, view_offsets, n, m12, nviews, min, max, sigma, out_f32, out_u16, dim));
+    for (int v = 0; v < nviews; ++v)
+        MVSIM_CHECK_ARG((!out_f32 || out_f32[v]) && (!out_u16 || out_u16[v]), "renderBeads: null image in an output list");
+    MVSIM_TRY(set_device(ctx));
+    // device twins of the outputs: every view's float image in vol_a, its uint16 image in vol_b
+    const size_t nv = (size_t)(dim[0] * dim[1] * dim[2]);
+    std::vector<float*> df(nviews, nullptr);
+    std::vector<uint16_t*> du(nviews, nullptr);
+    if (out_f32) {
+        MVSIM_TRY(ctx->vol_a.reserve(nv * sizeof(float) * nviews));
+        for (int v = 0; v < nviews; ++v) df[v] = ctx->vol_a.as<float>() + nv * v;
+    }
+    if (out_u16) {
+        MVSIM_TRY(ctx->vol_b.reserve(nv * sizeof(uint16_t) * nviews));
+        for (int v = 0; v < nviews; ++v) du[v] = reinterpret_cast<uint16_t*>(ctx->vol_b.p) + nv * v;
+    }
+    MVSIM_TRY(render_beads_dev(ctx, xyz, view_offsets, n, m12, nviews, dim, min, sigma, out_f32 ? df.data() : nullptr,
+                               out_u16 ? du.data() : nullptr));
+    for (int v = 0; v < nviews; ++v) {
+        if (out_f32) MVSIM_HIP(hipMemcpyAsync(out_f32[v], df[v], nv * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        if (out_u16) MVSIM_HIP(hipMemcpyAsync(out_u16[v], du[v], nv * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    MVSIM_HIP(hipStreamSynchronize(ctx->stream));
+    return MVSIM_OK;
+}
+
+int mvsim_beads_normalize_dev(mvsim_ctx* ctx, float* img, int64_t n)
+{
+    MVSIM_TRY(set_device(ctx));
+    MVSIM_CHECK_ARG(img && n >= 1, "null image or empty count");
+    return beads_normalize_dev(ctx, img, n);
+}
+
+int mvsim_beads_normalize(mvsim_ctx* ctx, float* img, int64_t n)
+{
+    MVSIM_TRY(set_device(ctx));
+    MVSIM_CHECK_ARG(img && n >= 1, "null image or empty count");
+    const size_t bytes = (size_t)n * sizeof(float);
+    MVSIM_TRY(up(ctx, ctx->vol_a, img, bytes));
+    MVSIM_TRY(beads_normalize_dev(ctx, ctx->vol_a.as<float>(), n));
     return down(ctx, img, ctx->vol_a.p, bytes);
 }
 

@@ -170,6 +170,7 @@ struct Options {
                                        // the pieces that have arrived among themselves (mvsim_comm_broadcast_plan; comm.cpp: bcast_pipelined)
     int64_t fft_pad[3] = {0, 0, 0};    // explicit padded sizes on the rocFFT path (0: choose)
     bool    skip_empty = true;         // convolution passes skip planes the fused rotate kernel found empty (exact; option for A/B runs)
+    int64_t beads_pair_cap = (int64_t)1 << 28;   // bead renderer: (brick, bead) pairs one chunk may bin; larger calls run in chunks (beads.hip)
 };
 // How launch_extract samples.  share 0: one launch, no work queue.  1..16: work queue whose per-block segments hold that many sixteenths
 // of the block's voxels.  QUEUE_SHARE_AUTO + L (L = 0..16): the library's choice -- every voxel for queues of up to 64 MiB, else
@@ -212,6 +213,7 @@ struct mvsim_ctx {
     mvsim::DevBuf fft_work;
     mvsim::DevBuf pqueue;                   // Poisson work queue: [count][items]
     mvsim::DevBuf sphere_list;              // phantom generator: (centre, radius, value) items
+    mvsim::DevBuf beads_buf[8];             // bead renderer (beads.hip): points, jobs, per-bead records, pair keys / values, sort temp, scratch
     mvsim::DevBuf plane_flags;              // per-plane non-zero flags of the current view (rotate_fft.hip -> the convolution passes)
     int*          empty_hint = nullptr;     // page-locked word the device writes: empty planes of the last view that carried flags (-1: none yet)
     unsigned int* queue_hint = nullptr;     // page-locked word the device raises: sixteenths of a block's voxels the fullest refused queue segment needed
@@ -363,6 +365,11 @@ int launch_downsample2x(hipStream_t s, const float* in, const int64_t dim[3], fl
 int draw_spheres_dev(mvsim_ctx* ctx, float* img, const int64_t dim[3], double min_value, double max_value, int scale,
                      int half_pixel_offset, uint64_t* rnd_state, int64_t* n_spheres);
 int splat_spheres_dev(mvsim_ctx* ctx, float* img, const int64_t dim[3], const mvsim_sphere* spheres, int64_t n);
+// SimulateBeads.renderPoints on device outputs (beads.hip); arguments validated by the caller (api.cpp)
+int render_beads_dev(mvsim_ctx* ctx, const double* xyz, const int64_t* view_offsets, int64_t n, const double* m12, int nviews,
+                     const int64_t dim[3], const int64_t imin[3], const double sigma[3], float* const* out_f32, uint16_t* const* out_u16);
+int beads_normalize_dev(mvsim_ctx* ctx, float* img, int64_t n);
+void beads_release(mvsim_ctx* ctx);
 int launch_weight_image(hipStream_t s, float* out, const int64_t dim[3]);
 int launch_weights(hipStream_t s, float* const* views, int nv, int64_t n, const float* sum_in, float* sum_out,
                    float osem, bool sum_only);
