@@ -360,6 +360,19 @@ int mvsim_fft_geometry(const int64_t dim[3], const int64_t kdim[3], int64_t geom
  * tile serves, LDS bytes per block, blocks per CU}.  Any PSF of 1..64 taps per axis is accepted (SimulateMultiViewDataset.java:579
  * loads 51^3 stacks); beyond that MVSIM_EINVAL (use the FFT method). */
 int mvsim_stencil_geometry(const int64_t kdim[3], int64_t geometry[5]);
+/* The extract + Poisson sampler form one launch takes for nzo = (dim[2] - 1) / inc + 1 acquired planes of dim[0] x dim[1] voxels, the RNG
+ * counter of plane k's voxel i being index_offset + k * index_inc * plane + i (index_inc 0: inc).  aligned16: both buffers allow 16-byte
+ * accesses; queue_share: 0 = no work queue, else 1..16 sixteenths of a block's voxels its segment holds (the share option resolved; small
+ * volumes resolve "auto" to 16).  path = {kernel: 0 one voxel per lane, 1 four voxels per lane, 2 two-launch vector form, 3 two-launch
+ * group-by-group form; 1 if queue segments can refuse voxels; blocks; items per segment (0: no queue)}.  Host only, no context. */
+int mvsim_extract_path(const int64_t dim[3], int inc, int index_inc, uint64_t index_offset, int aligned16, int queue_share, int64_t path[4]);
+/* The sampler form of the last extract + Poisson this context enqueued: {kernel as mvsim_extract_path, or 4 for the fused tail of the
+ * convolution; 1 if queue segments can refuse voxels; blocks; items per segment; views in the launch (> 1: the stacked-view tables)}.
+ * Recorded on the host when the work is enqueued; kernel -1 before the first. */
+int mvsim_get_extract_path(mvsim_ctx* ctx, int64_t path[5]);
+/* {blocks, items per segment} of the fused tail (the convolution's last pass adjusts, extracts and samples) for a noisy view of this
+ * volume / PSF under the context's options, with (want_con) or without the adjusted volume; MVSIM_EINVAL when it would not be fused. */
+int mvsim_fused_tail_geometry(mvsim_ctx* ctx, const int64_t dim[3], const int64_t kdim[3], int inc, int want_con, int64_t out[2]);
 /* Planes the convolution passes of the last FLAGGED view skipped (option "skip_empty"; exact: the spectrum of an empty attenuated plane
  * is zero): stats = {planes of the view, planes whose attenuated image is empty (pass B does not transform them, the z pass does not
  * read them), planes of the z pass's output that are empty (passes D and E skip them)}.  Read from a page-locked word the device

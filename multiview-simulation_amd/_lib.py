@@ -135,6 +135,9 @@ SIGNATURES = {
     "mvsim_extract_slices_zslabs": (C.c_int, [_vp, C.POINTER(_vp), _i64p, C.c_int, _i64p, C.c_int, C.c_float, C.c_uint64, C.c_uint32,
                                               C.POINTER(_vp), _i64p, C.c_int]),
     "mvsim_stencil_geometry": (C.c_int, [_i64p, _i64p]),
+    "mvsim_extract_path": (C.c_int, [_i64p, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, _i64p]),
+    "mvsim_fused_tail_geometry": (C.c_int, [_vp, _i64p, _i64p, C.c_int, C.c_int, _i64p]),
+    "mvsim_get_extract_path": (C.c_int, [_vp, _i64p]),
     "mvsim_enable_timing": (C.c_int, [_vp, C.c_int]),
     "mvsim_get_timings": (C.c_int, [_vp, C.POINTER(Timings)]),
     "mvsim_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte)]),

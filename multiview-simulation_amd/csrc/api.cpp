@@ -835,7 +835,7 @@ int mvsim_extract_slices_dev(mvsim_ctx* ctx, const float* in, const int64_t dim[
     if (noise) { MVSIM_TRY(ctx->pqueue.reserve(poisson_queue_bytes_planes(dim[0] * dim[1], mvsim_extract_nz(dim[2], inc), qm.share))); qws = ctx->pqueue.p; }
     ev_begin(ctx, ST_EXTRACT);
     MVSIM_TRY(launch_extract(ctx->stream, in, out, dim, inc, false, nullptr, 0.0f, noise,
-                             mvsim_poisson_mul((double)snr), seed, stream, 0, qws, qm));
+                             mvsim_poisson_mul((double)snr), seed, stream, 0, qws, qm, 0, ctx->extract_path));
     ev_end(ctx, ST_EXTRACT);
     return MVSIM_OK;
 }
@@ -1004,7 +1004,14 @@ static int view_enqueue(mvsim_ctx* ctx, const float* gt, const int64_t dim[3], c
         }
     }
     MVSIM_TRY(convolve_dev_impl(ctx, att, dim, kdim, method, con, &tail));
-    if (tail.fused) return MVSIM_OK;   // pass E adjusted, extracted and sampled (phase 1); the resolver is enqueued behind it
+    if (tail.fused) {                  // pass E adjusted, extracted and sampled (phase 1); the resolver is enqueued behind it
+        long long fb = 0;
+        unsigned int fs = 0;
+        (void)fused_tail_geometry(dim, kdim, p->inc, materialise, ctx->opt, &fb, &fs);
+        const int64_t fused[5] = {EXTRACT_FUSED_TAIL, 0, fb, noise ? (int64_t)fs : 0, 1};
+        std::memcpy(ctx->extract_path, fused, sizeof(fused));
+        return MVSIM_OK;
+    }
 
     ev_begin(ctx, ST_ADJUST);
     if (method == 2) MVSIM_TRY(launch_sum(ctx->stream, con, n, partial, scal));   // FFT path sums in its crop epilogue
@@ -1039,10 +1046,10 @@ static int view_enqueue(mvsim_ctx* ctx, const float* gt, const int64_t dim[3], c
         // `con` holds the acquired planes only: read them in order, count the RNG in source planes
         const int64_t cdim[3] = {dim[0], dim[1], mvsim_extract_nz(dim[2], p->inc)};
         MVSIM_TRY(launch_extract(ctx->stream, con, o->acq, cdim, 1, true, scal, p->min_value, noise,
-                                 mvsim_poisson_mul((double)p->snr), p->seed, p->stream, 0, qws, qm, p->inc));
+                                 mvsim_poisson_mul((double)p->snr), p->seed, p->stream, 0, qws, qm, p->inc, ctx->extract_path));
     } else {
         MVSIM_TRY(launch_extract(ctx->stream, con, o->acq, dim, p->inc, !materialise, scal, p->min_value, noise,
-                                 mvsim_poisson_mul((double)p->snr), p->seed, p->stream, 0, qws, qm));
+                                 mvsim_poisson_mul((double)p->snr), p->seed, p->stream, 0, qws, qm, 0, ctx->extract_path));
     }
     ev_end(ctx, ST_EXTRACT);
     if (overlap_ok) {
@@ -1311,10 +1318,10 @@ static int views_enqueue_batched(mvsim_ctx* ctx, const float* gt, const int64_t 
     if (zstride > 1) {
         const int64_t cdim[3] = {dim[0], dim[1], nzo};                                  // `con` holds the acquired planes only
         MVSIM_TRY(launch_extract_views(ctx->stream, cdim, 1, true, p0.min_value, noise, mvsim_poisson_mul((double)p0.snr), qm,
-                                       p0.inc, V, evt, vec_all));
+                                       p0.inc, V, evt, vec_all, ctx->extract_path));
     } else {
         MVSIM_TRY(launch_extract_views(ctx->stream, dim, p0.inc, true, p0.min_value, noise, mvsim_poisson_mul((double)p0.snr), qm,
-                                       0, V, evt, vec_all));
+                                       0, V, evt, vec_all, ctx->extract_path));
     }
     ev_end(ctx, ST_EXTRACT);
     return MVSIM_OK;
@@ -1569,7 +1576,7 @@ static int slab_finish_enqueue(mvsim_ctx* ctx, const int64_t dim[3], const mvsim
         void* q = nullptr;
         if (noise_c) { MVSIM_TRY(ctx->pqueue.reserve(poisson_queue_bytes_planes(plane, k1 - k0, qm.share))); q = ctx->pqueue.p; }
         return launch_extract(ctx->stream, ctx->vol_a.as<float>(), acq, cdim, 1, true, scal, p->min_value, noise_c, mvsim_poisson_mul((double)p->snr),
-                              p->seed, p->stream, (uint64_t)(z0 * plane), q, qm, p->inc);
+                              p->seed, p->stream, (uint64_t)(z0 * plane), q, qm, p->inc, ctx->extract_path);
     }
     const int64_t first = k0 * p->inc;                      // global index of the first acquired source plane
     const int64_t ldim[3] = {dim[0], dim[1], z1 - first};
@@ -1581,7 +1588,7 @@ static int slab_finish_enqueue(mvsim_ctx* ctx, const int64_t dim[3], const mvsim
     }
     return launch_extract(ctx->stream, ctx->vol_a.as<float>() + plane * (first - z0), acq, ldim, p->inc, true, scal,
                           p->min_value, noise, mvsim_poisson_mul((double)p->snr), p->seed, p->stream,
-                          (uint64_t)(first * plane), qws, qm);
+                          (uint64_t)(first * plane), qws, qm, 0, ctx->extract_path);
 }
 
 // One tiled view's slab in ONE call, nothing through the host (round 6): the slab's share of adjustImage's sum stays on the device, is
@@ -1737,7 +1744,7 @@ int mvsim_poisson_process(mvsim_ctx* ctx, float* img, int64_t n, double snr, uin
     MVSIM_TRY(ctx->pqueue.reserve(poisson_queue_bytes_planes(n, 1, qm.share)));
     ev_begin(ctx, ST_EXTRACT);
     MVSIM_TRY(launch_extract(ctx->stream, ctx->vol_a.as<float>(), ctx->out_buf.as<float>(), dim, 1, false, nullptr,
-                             0.0f, true, mvsim_poisson_mul(snr), seed, stream, index_offset, ctx->pqueue.p, qm));
+                             0.0f, true, mvsim_poisson_mul(snr), seed, stream, index_offset, ctx->pqueue.p, qm, 0, ctx->extract_path));
     ev_end(ctx, ST_EXTRACT);
     return down_counts(ctx, img, ctx->out_buf.as<float>(), n, true);
 }
@@ -2399,6 +2406,40 @@ int mvsim_stencil_geometry(const int64_t kdim[3], int64_t geometry[5])
         set_error("direct stencil: PSF outside 1..64 taps per axis");
         return MVSIM_EINVAL;
     }
+    return MVSIM_OK;
+}
+
+int mvsim_extract_path(const int64_t dim[3], int inc, int index_inc, uint64_t index_offset, int aligned16, int queue_share, int64_t path[4])
+{
+    if (!dim || !path) { set_error("invalid argument: null pointer"); return MVSIM_EINVAL; }
+    MVSIM_TRY(check_dim(dim));
+    MVSIM_CHECK_ARG(inc >= 1 && index_inc >= 0, "inc must be >= 1 and index_inc >= 0");
+    MVSIM_CHECK_ARG(0 <= queue_share && queue_share <= 16, "queue_share must be 0 (no queue) or 1..16 sixteenths");
+    extract_path(dim, inc, index_inc, index_offset, aligned16 != 0, queue_share, path);
+    return MVSIM_OK;
+}
+
+int mvsim_get_extract_path(mvsim_ctx* ctx, int64_t path[5])
+{
+    MVSIM_CHECK_ARG(ctx != nullptr && path != nullptr, "null pointer");
+    std::memcpy(path, ctx->extract_path, sizeof(ctx->extract_path));
+    return MVSIM_OK;
+}
+
+int mvsim_fused_tail_geometry(mvsim_ctx* ctx, const int64_t dim[3], const int64_t kdim[3], int inc, int want_con, int64_t out[2])
+{
+    MVSIM_CHECK_ARG(ctx != nullptr && dim && kdim && out, "null pointer");
+    MVSIM_TRY(check_dim(dim));
+    MVSIM_CHECK_ARG(inc >= 1, "inc must be >= 1");
+    long long blocks = 0;
+    unsigned int segcap = 0;
+    // what view_enqueue asks of a noisy view before it offers the convolution its tail
+    if (!ctx->opt.fuse_tail || ctx->opt.poisson_queue != 1 || !fused_tail_geometry(dim, kdim, inc, want_con != 0, ctx->opt, &blocks, &segcap)) {
+        set_error("this view would not take the fused tail");
+        return MVSIM_EINVAL;
+    }
+    out[0] = blocks;
+    out[1] = segcap;
     return MVSIM_OK;
 }
 

@@ -218,6 +218,7 @@ struct mvsim_ctx {
     int*          empty_hint = nullptr;     // page-locked word the device writes: empty planes of the last view that carried flags (-1: none yet)
     unsigned int* queue_hint = nullptr;     // page-locked word the device raises: sixteenths of a block's voxels the fullest refused queue segment needed
     int           queue_share_learned = 0;  // ... as the host has seen it so far (auto share: queue_mode_next)
+    int64_t       extract_path[5] = {-1, 0, 0, 0, 0};   // the sampler form of the last extract this context enqueued (mvsim_get_extract_path)
     int           views_since_flags = 0;    // views run WITHOUT flags since (a volume without empty planes pays nothing for the bookkeeping)
     mvsim::DevBuf weight_img;               // computeWeightImage of the last volume size (mvsim_simulate_iteration_dev)
     int64_t       weight_dim[3] = {0, 0, 0};
@@ -340,7 +341,12 @@ int launch_norm_apply(hipStream_t s, float* img, int64_t n, const double* scal);
 // extract (+ optional adjust using scal[1]) (+ optional Poisson).  in: Nx*Ny*Nz, out: Nx*Ny*nzo
 int launch_extract(hipStream_t s, const float* in, float* out, const int64_t dim[3], int inc, bool adjust,
                    const double* scal, float min_value, bool noise, double mul, uint64_t seed,
-                   uint32_t stream, uint64_t index_offset, void* queue_ws, QueueMode queue_mode, int index_inc = 0);
+                   uint32_t stream, uint64_t index_offset, void* queue_ws, QueueMode queue_mode, int index_inc = 0,
+                   int64_t* path_out = nullptr);   // path_out: {extract_path's four words, views in the launch}
+// The sampler form launch_extract takes (kernels.hip: extract_path; mvsim_extract_path): path = {EXTRACT_K_*, segments can refuse,
+// blocks, items per segment}.  qshare: 0 = no work queue, else 1..16 sixteenths.
+enum { EXTRACT_K_SCALAR = 0, EXTRACT_K_VEC = 1, EXTRACT_K_NOISE2 = 2, EXTRACT_K_NOISE2_ANY = 3, EXTRACT_FUSED_TAIL = 4 };
+void extract_path(const int64_t dim[3], int inc, int index_inc, uint64_t index_offset, bool aligned16, int qshare, int64_t path[4]);
 // bytes of the Poisson work queue (HBM) for nzo planes of `plane` voxels whichever sampler kernel takes them (planes that are no
 // multiple of four voxels or unaligned buffers go group by group through k_extract_noise2_any, whose wave slots are padded per plane)
 size_t poisson_queue_bytes_planes(long long plane, long long nzo, int share);
@@ -357,7 +363,7 @@ struct ExtractView {              // per-view operands of the extract + Poisson 
 int launch_rotate_attenuate_views(hipStream_t s, const float* in, float* att, const int64_t dim[3], const Affine* atab_dev, int nviews, double delta);
 void poisson_queue_split(void* queue_ws, void** queue_items, unsigned int** qcount);
 int launch_extract_views(hipStream_t s, const int64_t dim[3], int inc, bool adjust, float min_value, bool noise, double mul,
-                         QueueMode queue_mode, int index_inc, int nviews, const ExtractView* vt_dev, bool vec_all);
+                         QueueMode queue_mode, int index_inc, int nviews, const ExtractView* vt_dev, bool vec_all, int64_t* path_out = nullptr);
 int launch_pack_u16(hipStream_t s, const float* in, unsigned short* out16, int64_t n, unsigned int* flag);
 int launch_make_isotropic(hipStream_t s, const float* in, float* out, const int64_t dim[3], int inc);
 // phantom generator (phantom.hip)
@@ -451,6 +457,9 @@ int  custom_fft_convolve_slab(mvsim_ctx* ctx, const float* img, const int64_t di
                               const int64_t kdim[3], const int64_t P[3], const SlabRange& slab, float* out, ConvTail* tail);
 void custom_fft_release(mvsim_ctx* ctx);
 bool custom_fft_geometry(const int64_t dim[3], const int64_t kdim[3], int64_t g[5], const Options& opt);
+// {blocks, items per segment} of the fused tail (pass E adjusts, extracts and samples); false when the view would not be fused
+bool fused_tail_geometry(const int64_t dim[3], const int64_t kdim[3], int inc, bool con_wanted, const Options& opt, long long* blocks,
+                         unsigned int* segcap);
 // true when views of this geometry can run stacked through the hand-written passes (ConvTail::views > 1): direct z pass, early sum,
 // pass B reading the mirrored y halo from its mirror images, no inline-FFT z pass, no fused tail
 bool custom_fft_batchable(const mvsim_ctx* ctx, const int64_t dim[3], const int64_t kdim[3]);

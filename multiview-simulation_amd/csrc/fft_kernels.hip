@@ -1840,7 +1840,7 @@ static int ensure_box_weights(mvsim_ctx* ctx, int N, int P, int len, bool half, 
 }
 
 // Geometry of the fused tail: pass E blocks own queue segments that can hold every voxel of their rows.
-static bool fused_tail_geometry(const int64_t dim[3], const int64_t kdim[3], int inc, bool con_wanted, const Options& opt,
+bool fused_tail_geometry(const int64_t dim[3], const int64_t kdim[3], int inc, bool con_wanted, const Options& opt,
                                 long long* blocks, unsigned int* segcap)
 {
     int64_t P[3];

@@ -760,7 +760,7 @@ __global__ __launch_bounds__(256) void k_extract(const float* __restrict__ in, f
 // Philox group.  Requires plane % 4 == 0, index_offset % 4 == 0 and 16-B aligned buffers.
 template <bool ADJUST, bool NOISE>
 __global__ __launch_bounds__(256) void k_extract4(const float* __restrict__ in, float* __restrict__ out,
-                                                  long long plane4, long long nzo, int inc,
+                                                  long long plane4, long long nzo, int inc, int idx_inc,
                                                   const double* __restrict__ scal, float min_value, double mul,
                                                   uint32_t k0, uint32_t k1, uint32_t stream,
                                                   unsigned long long index_offset, const ExtractView* __restrict__ vt)
@@ -774,10 +774,11 @@ __global__ __launch_bounds__(256) void k_extract4(const float* __restrict__ in, 
     float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
     const bool small32 = total4 < (1ll << 32);
     for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < total4; o += nthreads) {
-        long long src4 = o;
-        if (inc != 1) {
+        long long src4 = o, idx4 = o;                 // where the voxels are read / what the RNG counter says they are
+        if (inc != 1 || idx_inc != 1) {
             const long long k = small32 ? (long long)((unsigned)o / (unsigned)plane4) : o / plane4;
             src4 = k * inc * plane4 + (o - k * plane4);
+            idx4 = k * idx_inc * plane4 + (o - k * plane4);
         }
         float4 v = in4[src4];
         if (ADJUST) {
@@ -788,7 +789,7 @@ __global__ __launch_bounds__(256) void k_extract4(const float* __restrict__ in, 
         }
         if (NOISE)
             v = poisson_counter4((double)v.x * mul, (double)v.y * mul, (double)v.z * mul, (double)v.w * mul, k0, k1,
-                                 stream, index_offset + 4ull * (unsigned long long)src4);
+                                 stream, index_offset + 4ull * (unsigned long long)idx4);
         out4[o] = v;
     }
 }
@@ -1102,116 +1103,146 @@ int poisson_queue_read_stats(const void* queue_ws, size_t bytes, long long stats
     return MVSIM_OK;
 }
 
+// Which sampler form takes nzo = (dim[2] - 1) / inc + 1 acquired planes (mvsim_extract_path; launch_extract_impl decides through this
+// and nothing else).  index_inc: plane stride of the RNG counter (0 = inc); aligned16: both buffers allow 16-byte accesses; qshare: 0 =
+// no work queue, else the sixteenths share_for resolved.  path = {EXTRACT_K_*, segments can refuse, blocks, items per segment (0: no queue)}.
+void extract_path(const int64_t dim[3], int inc, int index_inc, uint64_t index_offset, bool aligned16, int qshare, int64_t path[4])
+{
+    if (index_inc <= 0) index_inc = inc;
+    const long long plane = (long long)dim[0] * dim[1];
+    const long long nzo = (dim[2] - 1) / inc + 1;
+    const long long total = plane * nzo;
+    // phase 1 hands a slot's RNG counters across lanes as 32-bit offsets from lane 0's (poisson_phase1): a vector slot is 256
+    // consecutive outputs, and planes smaller than that put several plane boundaries -- each a jump of (index_inc - 1) planes of
+    // counter -- into one slot; all of them together must stay below 2^31 (double: the product may exceed 64 bits)
+    const double crossings = (double)((255 + plane - 1) / plane);
+    // ... and a work item carries its output position (and the resolver the plane) in 32 bits
+    const bool use_queue = qshare != 0 && crossings * (double)(index_inc - 1) * (double)plane < 2147483648.0 && total < (1ll << 32) &&
+                           plane < (1ll << 32);
+    const bool vec = (plane % 4 == 0) && (index_offset % 4 == 0) && aligned16;
+    path[1] = use_queue && qshare < 16 ? 1 : 0;
+    path[3] = 0;
+    if (use_queue) {
+        int qblocks;
+        unsigned int segcap;
+        if (vec) {
+            poisson_geometry(total, qshare, &qblocks, &segcap);
+        } else {
+            long long spp;
+            poisson_geometry_any(plane, nzo, qshare, &qblocks, &segcap, &spp);
+        }
+        path[0] = vec ? EXTRACT_K_NOISE2 : EXTRACT_K_NOISE2_ANY;
+        path[2] = qblocks;
+        path[3] = segcap;
+    } else if (vec) {
+        const long long want = (total / 4 + 255) / 256;
+        path[0] = EXTRACT_K_VEC;
+        path[2] = want < 1 ? 1 : (want > 256 * 64 ? 256 * 64 : want);
+    } else {
+        const long long want = (total + 255) / 256;
+        path[0] = EXTRACT_K_SCALAR;
+        path[2] = want < 1 ? 1 : (want > 256 * 32 ? 256 * 32 : want);
+    }
+}
+
 // nviews > 0: the same launch for `nviews` views whose inputs, outputs, [sum, factor] slots, RNG keys and queue workspaces come from
 // the device table `vt` (blockIdx.y = view; `vec_all`: every view's buffers allow the 16-byte form; in / out / scal / seed / stream /
 // queue_ws arguments unused)
 static int launch_extract_impl(hipStream_t s, const float* in, float* out, const int64_t dim[3], int inc, bool adjust,
                                const double* scal, float min_value, bool noise, double mul, uint64_t seed,
                                uint32_t stream, uint64_t index_offset, void* queue_ws, QueueMode queue_mode, int index_inc,
-                               int nviews, const ExtractView* vt, bool vec_all)
+                               int nviews, const ExtractView* vt, bool vec_all, int64_t* path_out)
 {
     // index_inc: plane stride of the RNG counter when it differs from the plane stride of the reads (a compact input
     // that holds only the planes k * index_inc of the source volume); 0 = the same as inc
     if (index_inc <= 0) index_inc = inc;
     const unsigned gy = nviews > 0 ? (unsigned)nviews : 1u;
     const long long plane = (long long)dim[0] * dim[1];
-    // phase 1 hands a slot's RNG counters across lanes as 32-bit offsets from lane 0's (poisson_phase1): a slot that straddles
-    // two acquired planes must not see them 2^32 voxels apart
-    // ... and a work item carries its output position in 32 bits
-    const bool use_queue = queue_mode.share != 0 && (long long)(index_inc - 1) * plane < (1ll << 31) && plane * ((dim[2] - 1) / inc + 1) < (1ll << 32) &&
-                           plane < (1ll << 32);
     const long long nzo = (dim[2] - 1) / inc + 1;
     const long long total = plane * nzo;
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    const int qshare = share_for(total, queue_mode.share);
-    const bool vec = (plane % 4 == 0) && (index_offset % 4 == 0) &&
-                     (nviews > 0 ? vec_all : ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) % 16 == 0));
-    if (vec) {
-        long long want = (total / 4 + 255) / 256;
-        int blocks = (int)(want < 1 ? 1 : (want > 256 * 64 ? 256 * 64 : want));
-#define MVSIM_LAUNCH_EX4(A, N)                                                                               \
-    hipLaunchKernelGGL((k_extract4<A, N>), dim3(blocks, gy), dim3(256), 0, s, in, out, plane / 4, nzo, inc, scal, \
-                       min_value, mul, k0, k1, stream, (unsigned long long)index_offset, vt)
-        if (noise && (queue_ws || nviews > 0) && use_queue) {
-            int qblocks;
-            unsigned int segcap;
-            unsigned int full_items;
-            poisson_geometry(total, 16, &qblocks, &full_items);
-            poisson_geometry(total, qshare, &qblocks, &segcap);
-            unsigned int* qcount = reinterpret_cast<unsigned int*>(queue_ws);
-            PItem* queue = queue_ws ? reinterpret_cast<PItem*>(reinterpret_cast<char*>(queue_ws) + QCOUNT_BYTES) : nullptr;
+    const int qshare = noise && (queue_ws || nviews > 0) && queue_mode.share != 0 ? share_for(total, queue_mode.share) : 0;
+    const bool aligned16 = nviews > 0 ? vec_all : ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) % 16 == 0);
+    int64_t path[4];
+    extract_path(dim, inc, index_inc, index_offset, aligned16, qshare, path);
+    if (path_out) {
+        for (int i = 0; i < 4; ++i) path_out[i] = path[i];
+        path_out[4] = gy;
+    }
+    const int qblocks = (int)path[2];
+    const unsigned int segcap = (unsigned int)path[3];
+    unsigned int* qcount = reinterpret_cast<unsigned int*>(queue_ws);
+    PItem* queue = queue_ws ? reinterpret_cast<PItem*>(reinterpret_cast<char*>(queue_ws) + QCOUNT_BYTES) : nullptr;
+    const bool checked = path[1] != 0;                    // segments that can fill up: the appends look before they write
+    if (path[0] == EXTRACT_K_NOISE2) {
+        int fb;
+        unsigned int full_items;
+        poisson_geometry(total, 16, &fb, &full_items);
 #define MVSIM_LAUNCH_N2(A, C)                                                                                                     \
     hipLaunchKernelGGL((k_extract4_noise2<A, C>), dim3(qblocks, gy), dim3(256), 0, s, in, out, plane / 4, nzo, inc, index_inc, scal, \
                        min_value, mul, k0, k1, stream, (unsigned long long)index_offset, queue, qcount, segcap, vt)
-            const bool checked = qshare < 16;                 // segments that can fill up: the appends look before they write
-            if (adjust && checked) MVSIM_LAUNCH_N2(true, true);
-            else if (adjust) MVSIM_LAUNCH_N2(true, false);
-            else if (checked) MVSIM_LAUNCH_N2(false, true);
-            else MVSIM_LAUNCH_N2(false, false);
+        if (adjust && checked) MVSIM_LAUNCH_N2(true, true);
+        else if (adjust) MVSIM_LAUNCH_N2(true, false);
+        else if (checked) MVSIM_LAUNCH_N2(false, true);
+        else MVSIM_LAUNCH_N2(false, false);
 #undef MVSIM_LAUNCH_N2
-            const ResolveJob rjob{out, queue, qcount, segcap, mul, k0, k1, stream, (unsigned int)plane, (unsigned int)index_inc,
-                                  (unsigned long long)index_offset, qshare >= 16 ? 0 : 1, total / 4, 0};
-            hipLaunchKernelGGL(k_poisson_resolve, dim3(qblocks, gy), dim3(256), 0, s, rjob, vt);
-            if (rjob.walk != 0)
-                hipLaunchKernelGGL(k_poisson_refused, dim3(qblocks < REFUSED_BLOCKS ? qblocks : REFUSED_BLOCKS, gy), dim3(256), 0, s, rjob, qblocks,
-                                   full_items, queue_mode.hint, vt);
-        }
-        else if (adjust && noise) MVSIM_LAUNCH_EX4(true, true);
-        else if (adjust) MVSIM_LAUNCH_EX4(true, false);
-        else if (noise) MVSIM_LAUNCH_EX4(false, true);
-        else MVSIM_LAUNCH_EX4(false, false);
-#undef MVSIM_LAUNCH_EX4
-        MVSIM_HIP(hipGetLastError());
-        return MVSIM_OK;
-    }
-    if (noise && (queue_ws || nviews > 0) && use_queue) {
+        const ResolveJob rjob{out, queue, qcount, segcap, mul, k0, k1, stream, (unsigned int)plane, (unsigned int)index_inc,
+                              (unsigned long long)index_offset, checked ? 1 : 0, total / 4, 0};
+        hipLaunchKernelGGL(k_poisson_resolve, dim3(qblocks, gy), dim3(256), 0, s, rjob, vt);
+        if (rjob.walk != 0)
+            hipLaunchKernelGGL(k_poisson_refused, dim3(qblocks < REFUSED_BLOCKS ? qblocks : REFUSED_BLOCKS, gy), dim3(256), 0, s, rjob, qblocks,
+                               full_items, queue_mode.hint, vt);
+    } else if (path[0] == EXTRACT_K_NOISE2_ANY) {
         // planes that are no multiple of four voxels / unaligned buffers: the same two launches, group by group (k_extract_noise2_any)
-        int qblocks;
-        unsigned int segcap;
-        long long spp;
+        int fb;
         unsigned int full_items;
-        poisson_geometry_any(plane, nzo, 16, &qblocks, &full_items, &spp);
-        poisson_geometry_any(plane, nzo, qshare, &qblocks, &segcap, &spp);
-        unsigned int* qcount = reinterpret_cast<unsigned int*>(queue_ws);
-        PItem* queue = queue_ws ? reinterpret_cast<PItem*>(reinterpret_cast<char*>(queue_ws) + QCOUNT_BYTES) : nullptr;
+        long long spp;
+        poisson_geometry_any(plane, nzo, 16, &fb, &full_items, &spp);
 #define MVSIM_LAUNCH_ANY(A, C)                                                                                                       \
     hipLaunchKernelGGL((k_extract_noise2_any<A, C>), dim3(qblocks, gy), dim3(256), 0, s, in, out, plane, nzo, inc, index_inc, scal, min_value, \
                        mul, k0, k1, stream, (unsigned long long)index_offset, queue, qcount, segcap, spp, vt)
-        const bool checked = qshare < 16;
         if (adjust && checked) MVSIM_LAUNCH_ANY(true, true);
         else if (adjust) MVSIM_LAUNCH_ANY(true, false);
         else if (checked) MVSIM_LAUNCH_ANY(false, true);
         else MVSIM_LAUNCH_ANY(false, false);
 #undef MVSIM_LAUNCH_ANY
         const ResolveJob rjob{out, queue, qcount, segcap, mul, k0, k1, stream, (unsigned int)plane, (unsigned int)index_inc,
-                              (unsigned long long)index_offset, qshare >= 16 ? 0 : 2, spp * nzo, spp};
+                              (unsigned long long)index_offset, checked ? 2 : 0, spp * nzo, spp};
         hipLaunchKernelGGL(k_poisson_resolve, dim3(qblocks, gy), dim3(256), 0, s, rjob, vt);
         if (rjob.walk != 0)
             hipLaunchKernelGGL(k_poisson_refused, dim3(qblocks < REFUSED_BLOCKS ? qblocks : REFUSED_BLOCKS, gy), dim3(256), 0, s, rjob, qblocks,
                                full_items, queue_mode.hint, vt);
-        MVSIM_HIP(hipGetLastError());
-        return MVSIM_OK;
-    }
-    long long want = (total + 255) / 256;
-    int blocks = (int)(want < 1 ? 1 : (want > 256 * 32 ? 256 * 32 : want));
+    } else if (path[0] == EXTRACT_K_VEC) {
+        const int blocks = (int)path[2];
+#define MVSIM_LAUNCH_EX4(A, N)                                                                                          \
+    hipLaunchKernelGGL((k_extract4<A, N>), dim3(blocks, gy), dim3(256), 0, s, in, out, plane / 4, nzo, inc, index_inc, scal, \
+                       min_value, mul, k0, k1, stream, (unsigned long long)index_offset, vt)
+        if (adjust && noise) MVSIM_LAUNCH_EX4(true, true);
+        else if (adjust) MVSIM_LAUNCH_EX4(true, false);
+        else if (noise) MVSIM_LAUNCH_EX4(false, true);
+        else MVSIM_LAUNCH_EX4(false, false);
+#undef MVSIM_LAUNCH_EX4
+    } else {
+        const int blocks = (int)path[2];
 #define MVSIM_LAUNCH_EX(A, N)                                                                             \
     hipLaunchKernelGGL((k_extract<A, N>), dim3(blocks, gy), dim3(256), 0, s, in, out, plane, nzo, inc, index_inc, scal, \
                        min_value, mul, k0, k1, stream, (unsigned long long)index_offset, vt)
-    if (adjust && noise) MVSIM_LAUNCH_EX(true, true);
-    else if (adjust) MVSIM_LAUNCH_EX(true, false);
-    else if (noise) MVSIM_LAUNCH_EX(false, true);
-    else MVSIM_LAUNCH_EX(false, false);
+        if (adjust && noise) MVSIM_LAUNCH_EX(true, true);
+        else if (adjust) MVSIM_LAUNCH_EX(true, false);
+        else if (noise) MVSIM_LAUNCH_EX(false, true);
+        else MVSIM_LAUNCH_EX(false, false);
 #undef MVSIM_LAUNCH_EX
+    }
     MVSIM_HIP(hipGetLastError());
     return MVSIM_OK;
 }
 
 int launch_extract(hipStream_t s, const float* in, float* out, const int64_t dim[3], int inc, bool adjust,
                    const double* scal, float min_value, bool noise, double mul, uint64_t seed,
-                   uint32_t stream, uint64_t index_offset, void* queue_ws, QueueMode queue_mode, int index_inc)
+                   uint32_t stream, uint64_t index_offset, void* queue_ws, QueueMode queue_mode, int index_inc, int64_t* path_out)
 {
     return launch_extract_impl(s, in, out, dim, inc, adjust, scal, min_value, noise, mul, seed, stream, index_offset, queue_ws, queue_mode,
-                               index_inc, 0, nullptr, false);
+                               index_inc, 0, nullptr, false, path_out);
 }
 
 // the queue region of one view inside a workspace of poisson_queue_bytes(n_out) bytes: [counts][segments]
@@ -1222,10 +1253,10 @@ void poisson_queue_split(void* queue_ws, void** queue_items, unsigned int** qcou
 }
 
 int launch_extract_views(hipStream_t s, const int64_t dim[3], int inc, bool adjust, float min_value, bool noise, double mul,
-                         QueueMode queue_mode, int index_inc, int nviews, const ExtractView* vt_dev, bool vec_all)
+                         QueueMode queue_mode, int index_inc, int nviews, const ExtractView* vt_dev, bool vec_all, int64_t* path_out)
 {
     return launch_extract_impl(s, nullptr, nullptr, dim, inc, adjust, nullptr, min_value, noise, mul, 0, 0, 0, nullptr, queue_mode, index_inc,
-                               nviews, vt_dev, vec_all);
+                               nviews, vt_dev, vec_all, path_out);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -216,8 +216,13 @@ __device__ __forceinline__ double ptrs_retry(const PtrsSetup& s, double lambda, 
 // so every term is O(1..50) and single precision is accurate to ~1e-5 absolute.  Returns +1 (surely accept),
 // -1 (surely reject) or 0 (too close to call: run the bit-defined fp64 test).  Pure optimisation: whenever it
 // answers, the answer equals the fp64 decision (margin >= 100x the error bound), so counts are unchanged.
+// The promise needs the fp64 test itself to be that accurate: its rhs sums terms of magnitude ~lambda log(lambda), so its own rounding
+// grows like ~4 * 2^-53 * lambda log(lambda) -- 7e-8 at lambda = 1e7 (the margin to eps stays ~300x), but 1e-5 at 1e9 and 1e-2 at 1e12,
+// where the screen's cancellation-free D and the fp64 decision part.  Above kScreenMaxLambda the fp64 test always decides.
+constexpr double kScreenMaxLambda = 1.0e7;
 __device__ __forceinline__ int ptrs_screen(const PtrsSetup& s, double lambda, double us, double V, double kd, const double* lf = kLogFact)
 {
+    if (!(lambda < kScreenMaxLambda)) return 0;
     const float lam = (float)lambda;
     if (kd <= 16.0) {
         // table branch of log(k!): -lambda + k log(lambda) - log(k!) has terms of magnitude <= ~100 here
@@ -606,11 +611,15 @@ __device__ __forceinline__ void poisson_phase1(const float vv[4], bool valid, un
     if (nb == 0u) return;                                   // wave-uniform
     *reinterpret_cast<float4*>(&ws->vin[4 * lane]) = make_float4(vv[0], vv[1], vv[2], vv[3]);
     // a pair's owner lane is found through the list; what it knows about its voxels (RNG counter, output position) comes over
-    // the lane crossbar instead of through LDS: the counters of a slot lie within 2^32 of lane 0's, the outputs are contiguous
-    const unsigned long long index_base = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned int)(index4 >> 32)) << 32) |
-                                          (unsigned long long)__builtin_amdgcn_readfirstlane((unsigned int)index4);
-    const unsigned long long out_base = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned int)(out4 >> 32)) << 32) |
-                                        (unsigned long long)__builtin_amdgcn_readfirstlane((unsigned int)out4);
+    // the lane crossbar instead of through LDS: the counters of a slot lie within 2^32 of lane 0's, the outputs are contiguous.
+    // (readfirstlane returns an int: each word goes through unsigned int before it is widened, or a low word >= 2^31 would
+    // sign-extend into the high word)
+    const unsigned int index_lo = (unsigned int)__builtin_amdgcn_readfirstlane((unsigned int)index4);
+    const unsigned int index_hi = (unsigned int)__builtin_amdgcn_readfirstlane((unsigned int)(index4 >> 32));
+    const unsigned int out_lo = (unsigned int)__builtin_amdgcn_readfirstlane((unsigned int)out4);
+    const unsigned int out_hi = (unsigned int)__builtin_amdgcn_readfirstlane((unsigned int)(out4 >> 32));
+    const unsigned long long index_base = ((unsigned long long)index_hi << 32) | (unsigned long long)index_lo;
+    const unsigned long long out_base = ((unsigned long long)out_hi << 32) | (unsigned long long)out_lo;
     const unsigned int index_delta = (unsigned int)(index4 - index_base);
     p1_wave_order();
     for (unsigned int i0 = 0u; i0 < nb; i0 += 64u) {        // wave-uniform trip count: the crossbar reads need every lane

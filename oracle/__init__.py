@@ -81,6 +81,7 @@ def lib():
         L.orc_det_lgamma_int.restype = C.c_double
         L.orc_poisson_counter.argtypes = [C.c_double, C.c_uint64, C.c_uint32, C.c_uint64]
         L.orc_poisson_counter.restype = C.c_int64
+        L.orc_poisson_counter_array.argtypes = [_f32p, C.c_int64, C.c_double, C.c_uint64, C.c_uint32, C.c_uint64, _f32p]
         L.orc_axis_rotation.argtypes = [_i64p, C.c_int, C.c_int, _f64p]
         L.orc_affine_invert.argtypes = [_f64p, _f64p]
         L.orc_rotate_around_axis.argtypes = [_f32p, _i64p, C.c_int, C.c_int, _f32p]
@@ -193,6 +194,16 @@ def det_lgamma_int(k: int) -> float:
 
 def poisson_counter(lam: float, seed: int, stream: int, index: int) -> int:
     return lib().orc_poisson_counter(lam, seed & 0xFFFFFFFFFFFFFFFF, stream, index)
+
+
+def poisson_counter_array(v, mul: float, seed: int, stream: int, index_offset: int) -> np.ndarray:
+    """Counts of lambda = (double)v[i] * mul, element i (C order) on counter index_offset + i (mod 2^64); same shape as v."""
+    a = np.ascontiguousarray(v, dtype=np.float32)
+    out = np.empty_like(a)
+    rc = lib().orc_poisson_counter_array(_p(a), a.size, float(mul), seed & 0xFFFFFFFFFFFFFFFF, stream & 0xFFFFFFFF,
+                                         index_offset & 0xFFFFFFFFFFFFFFFF, _p(out))
+    assert rc == 0
+    return out
 
 
 # --------------------------------------------------------------------------- stage ops

@@ -610,6 +610,16 @@ int orc_extract_slices_counter_window(const float* in, const int64_t dim[3], int
     return 0;
 }
 
+/* orc_poisson_counter over an array: out[i] = count of lambda = (double)v[i] * mul with counter index_offset + i (mod 2^64) */
+int orc_poisson_counter_array(const float* v, int64_t n, double mul, uint64_t seed, uint32_t stream, uint64_t index_offset, float* out)
+{
+    if (n < 0) return -1;
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; ++i)
+        out[i] = (float)orc_poisson_counter((double)v[i] * mul, seed, stream, index_offset + (uint64_t)i);
+    return 0;
+}
+
 int orc_extract_slices_counter(const float* in, const int64_t dim[3], int inc, float snr,
                                uint64_t seed, uint32_t stream, float* out)
 {

@@ -51,6 +51,8 @@ double   orc_det_exp(double x);
 double   orc_det_exp_neg(double lambda);        /* exp(-lambda), 0 < lambda < 10 */
 double   orc_det_lgamma_int(int64_t k);            /* log(k!) */
 int64_t  orc_poisson_counter(double lambda, uint64_t seed, uint32_t stream, uint64_t index);
+/* out[i] = orc_poisson_counter((double)v[i] * mul, seed, stream, index_offset + i), OpenMP */
+int      orc_poisson_counter_array(const float* v, int64_t n, double mul, uint64_t seed, uint32_t stream, uint64_t index_offset, float* out);
 
 /* ---- SMVD:80-102 axisRotation, mpicbg AffineModel3D semantics ---- */
 /* m = row-major 3x4 forward model T(+c) R T(-c); minv = createInverse() */
