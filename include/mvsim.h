@@ -74,7 +74,8 @@ int  mvsim_join(mvsim_ctx* ctx);
  * the FFT convolution as one kernel, so that the attenuated volume crosses HBM only when requested; auto = from 131072
  * columns up), "attenuate" = serial|scan (mvsim_attenuate3d
  * as a wavefront-level prefix scan along the illumination axis: parallel in y, not bit-identical to the serial walk), "beads_pair_cap" =
- * 1024..2^31 ((brick, bead) pairs the bead renderer bins at once; larger calls run in chunks with identical results).
+ * 1024..2^31 ((brick, bead) pairs the bead renderer bins at once; larger calls run in chunks with identical results; the refraction
+ * simulator's injection bins its (brick, step) pairs under the same cap).
  * MVSIM_OPTIONS="name=value;name=value" sets any of them process-wide.  Unknown names or values: MVSIM_EINVAL. */
 int  mvsim_set_option(mvsim_ctx* ctx, const char* name, const char* value);
 /* Release cached FFT plans / workspaces / PSF spectra held by the context. */
@@ -188,6 +189,98 @@ int mvsim_render_beads_dev(mvsim_ctx* ctx, const double* xyz, const int64_t* vie
  * float (a constant image gives NaN, as in the reference). */
 int mvsim_beads_normalize(mvsim_ctx* ctx, float* img, int64_t n);
 int mvsim_beads_normalize_dev(mvsim_ctx* ctx, float* img_dev, int64_t n);
+
+/* ---- the refraction simulator: net.preibisch.simulation.SimulateMultiViewAberrations --------------------------------------
+ *   SMVA = src/main/java/net/preibisch/simulation/SimulateMultiViewAberrations.java, HES = .../Hessian.java,
+ *   RAY = .../raytracing/Raytrace.java, LS = .../raytracing/Lightsheet.java, VI = .../VolumeInjection.java
+ * Volumes are floats, x fastest, dim = {Nx, Ny, Nz}, every dimension >= 2 (the mirror of Views.extendMirrorSingle needs two samples).
+ * Positions and directions are 3 doubles, x first.  The host forms take host buffers and are synchronous; the *_dev forms take DEVICE
+ * volumes (lists, scalars and the step list stay host memory).  NaN or infinite scalars and positions: MVSIM_EINVAL; a NaN VOXEL is not
+ * looked for and poisons what samples it, as in the reference.
+ * What is exact: ray starts, the sampler, the Hessian, the eigenpair, the injection of a given step list, normalize, project.  What is
+ * not: everything behind acos / asin / sin / cos (refraction) and exp (Gaussian weights), which the JDK, a host libm and the device
+ * library each round within about an ulp, differently.
+ * Third-party semantics are restated from the published algorithms and not pinned against the jars: ImgLib2's NLinearInterpolator (an
+ * fp64 position and an integer lower-corner tap; setPosition / move(distance) put the tap at floor(position), fwd / bck move both by
+ * one; weights = position - tap; Gray-code tap order, (float)(v * w) per tap, float accumulation), JAMA's EigenvalueDecomposition of a
+ * symmetric matrix (EISPACK tred2 + tql2, eigenvalues ascending; the QL loop is capped at 64 sweeps where JAMA has no cap). */
+/* LS:41-129: a x x + b x + c through (center, thickness_center) and (center -+ length / 2, thickness_edges) by the reference's
+ * normal equations and adjugate inverse.  MVSIM_EINVAL when the matrix is singular (the reference throws). */
+int mvsim_lightsheet_fit(double center, double thickness_center, double length, double thickness_edges, double abc[3]);
+/* HES:155-278 computeHessianMatrix3D on the INTERPOLATED image (RealRandomAccess over the mirrored volume, moved as the reference
+ * moves it) at n real positions (|coordinate| < 2^30), and HES:110-147 computeLargestEigenVectorAndValue3d: the eigenvalue of largest
+ * magnitude (first wins on ties) and its eigenvector with the decomposition's sign.  matrix9 (n * 9, row-major), eigvec3 (n * 3),
+ * eigval (n): host arrays, each may be NULL. */
+int mvsim_hessian_at(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const double* xyz, int64_t n, double* matrix9,
+                     double* eigvec3, double* eigval);
+int mvsim_hessian_at_dev(mvsim_ctx* ctx, const float* img_dev, const int64_t dim[3], const double* xyz, int64_t n, double* matrix9,
+                         double* eigvec3, double* eigval);
+/* HES:69-99, the loop of largestEigenVector (its Gauss3 blur is the caller's): integer positions through the mirror;
+ * eigval[Nz][Ny][Nx] = (float)eigenvalue, eigvec[3][Nz][Ny][Nx] = (float)eigenvector components. */
+int mvsim_hessian_images(mvsim_ctx* ctx, const float* img, const int64_t dim[3], float* eigval, float* eigvec);
+int mvsim_hessian_images_dev(mvsim_ctx* ctx, const float* img_dev, const int64_t dim[3], float* eigval_dev, float* eigvec_dev);
+/* SMVA:305-319: the starts of refract3d's rays, computed on the GPU: ray i consumes draws 3i .. 3i + 2 of nextDouble() of the caller's
+ * java.util.Random (48-bit state, see mvsim_draw_spheres), every ray jumping the generator ahead on its own.  x = u * (Nx - 1),
+ * y = illum ? Ny - 1 : 0, z = z + u * t - t / 2 with t = Lightsheet.predict(x) (abc from mvsim_lightsheet_fit), direction
+ * ((u - 0.5) / 5, illum ? -1 : 1, 0) normalised.  rnd_state is advanced by the 6 n generator steps.  Bit-exact. */
+int mvsim_refract3d_ray_starts(mvsim_ctx* ctx, uint64_t* rnd_state, const int64_t dim[3], int illum, int z, const double abc[3], int64_t n,
+                               double* pos3, double* dir3);
+/* SMVA:137-143: the starts of projectToCamera's rays, pixel-major (x fastest), rays_per_pixel per pixel: (px + (u - 0.5),
+ * py + (u - 0.5), 1), direction (0, 0, 1).  pos3 receives Nx * Ny * rays_per_pixel positions; rnd_state advances 4 steps per ray. */
+int mvsim_camera_ray_starts(mvsim_ctx* ctx, uint64_t* rnd_state, const int64_t dim[3], int rays_per_pixel, double* pos3);
+/* The step list of refract3d: one record per move of every ray, in ray order, then move order -- where the ray stood (before the
+ * move) and the image value it carried.  The caller provides host arrays for `capacity` steps (xyz: 3 doubles each) and num_rays
+ * move counts; any of the three may be NULL.  n returns the number of steps; more steps than capacity: MVSIM_EINVAL. */
+typedef struct mvsim_ray_steps {
+    int64_t  capacity;
+    int64_t  n;
+    double*  xyz;
+    float*   value;
+    int32_t* moves;
+} mvsim_ray_steps;
+/* SMVA:261-401 refract3d(imgIn, imgRi, illum, z, lsMiddle, lsEdge, ri) with num_rays rays (the reference: 200 000) drawn from
+ * rnd_state (the reference: new Random(2423); advanced by 6 steps per ray).  Each ray moves while it is inside the image
+ * (0 <= p <= N - 1) and has made fewer than Nz moves (maxMoves = dimension(2), kept), the light sheet is fitted over Nx
+ * (Lightsheet(Nx / 2.0, ls_middle, Nx, ls_edge), kept).  Per move: valueIm = imgIn at the position; Hessian of imgRi and its largest
+ * eigenpair; where |eigenvalue| > 0.01, n = (ri - 1) * imgRi + 1 sampled one ray vector behind and ahead, RAY:75-93 incidentAngle
+ * (quirk kept: the normal is flipped and pi / 2 SUBTRACTED when thetaI >= pi / 2), RAY:42-59 refract, NaN (total reflection) keeps
+ * the direction, then norm; addNormalizedGaussian(valueIm, position) with sigma 0.5 (a box of 5 voxels per axis); position +=
+ * direction.  image and weight (both may be NULL to trace only) are OVERWRITTEN with the injection's image and weight volumes,
+ * accumulated in float in list order: given the step list, bit for bit the reference's sums.  steps may be NULL. */
+int mvsim_refract3d(mvsim_ctx* ctx, const float* img, const float* ri_img, const int64_t dim[3], int illum, int z, double ls_middle,
+                    double ls_edge, double ri, int64_t num_rays, uint64_t* rnd_state, float* image, float* weight, mvsim_ray_steps* steps);
+/* Device volumes; image_dev and weight_dev are ADDED to (zero them for the reference's result).  Synchronises. */
+int mvsim_refract3d_dev(mvsim_ctx* ctx, const float* img_dev, const float* ri_img_dev, const int64_t dim[3], int illum, int z,
+                        double ls_middle, double ls_edge, double ri, int64_t num_rays, uint64_t* rnd_state, float* image_dev,
+                        float* weight_dev, mvsim_ray_steps* steps);
+/* VI:168-197 addGaussian (normalized = 0) / addNormalizedGaussian (1: intensity / sumWeights, VI:74-92 summed on the host in the
+ * constructor's cursor order) for n points IN LIST ORDER, in place: over the box Math.round(xyz_d) - size_d / 2 .. + size_d - 1
+ * (size = getSuggestedKernelDiameter(sigma)), value = ((1 * ex) * ey) * ez in fp64,
+ * image += (float)(value * intensity), weight += (float)value; writes outside the volume are dropped (extendZero).
+ * MVSIM_EINVAL: sigma <= 0 or not finite (the reference's sigma == 0, a box of one voxel, is not offered), non-finite positions or
+ * intensities. */
+int mvsim_volume_inject(mvsim_ctx* ctx, float* image, float* weight, const int64_t dim[3], const double sigma[3], const double* xyz,
+                        const double* intensity, int64_t n, int normalized);
+int mvsim_volume_inject_dev(mvsim_ctx* ctx, float* image_dev, float* weight_dev, const int64_t dim[3], const double sigma[3],
+                            const double* xyz, const double* intensity, int64_t n, int normalized);
+/* VI:45-94: the box sizes, sumWeights and numPixels of a VolumeInjection with this sigma (host only). */
+int mvsim_volume_inject_info(const double sigma[3], int32_t size[3], double* sum_weights, int32_t* num_pixels);
+/* VI:115-135 normalize: out = weight > 1.0f ? image / weight : image over n floats. */
+int mvsim_volume_normalize(mvsim_ctx* ctx, const float* image, const float* weight, int64_t n, float* out);
+int mvsim_volume_normalize_dev(mvsim_ctx* ctx, const float* image_dev, const float* weight_dev, int64_t n, float* out_dev);
+/* VI:199-232 project: per (x, y) the weighted mean along z over the voxels with image > 0 (fp64 sums of the float products);
+ * proj[Ny][Nx]; an empty column gives NaN (0 / 0), as the reference. */
+int mvsim_volume_project(mvsim_ctx* ctx, const float* image, const float* weight, const int64_t dim[3], float* proj);
+int mvsim_volume_project_dev(mvsim_ctx* ctx, const float* image_dev, const float* weight_dev, const int64_t dim[3], float* proj_dev);
+/* SMVA:89-254 projectToCamera(imgRi, refr, ri, currentzPlane): rays_per_pixel rays (the reference: 500; 1 .. 4096) per pixel of
+ * proj[Ny][Nx], drawn from rnd_state (the reference: the class's Random(464232194); advanced 4 steps per ray), refracted through
+ * imgRi as above and summing refr (interpolated) * exp(-dz^2 / (2 * 4^2)), dz = |z - current_z|, per move in fp64; the pixel is
+ * (float)(sum over its rays in ray order / 10.0).  Quirks kept: rays start at z = 1, the index contrast is 1.01 whatever ri is
+ * (SMVA:117, so the entry point takes no ri), maxMoves = Nz, `inside` is tested against refr (same dim here). */
+int mvsim_project_to_camera(mvsim_ctx* ctx, const float* ri_img, const float* refr, const int64_t dim[3], int current_z,
+                            int rays_per_pixel, uint64_t* rnd_state, float* proj);
+int mvsim_project_to_camera_dev(mvsim_ctx* ctx, const float* ri_img_dev, const float* refr_dev, const int64_t dim[3], int current_z,
+                                int rays_per_pixel, uint64_t* rnd_state, float* proj_dev);
 
 /* ---- stage operators, device-resident buffers (asynchronous on the context stream) ------ */
 /* (mvsim_draw_spheres_dev returns after the host walk; the compositing kernels are asynchronous.) */

@@ -277,6 +277,57 @@ JNIEXPORT void JNICALL JNI_FN(renderBeads)(JNIEnv* env, jclass, jlong h, jobject
                                       out_f32 ? f.data() : nullptr, out_u16 ? u.data() : nullptr));
 }
 
+// ---- the refraction simulator (mvsim_refract3d, mvsim_project_to_camera) ------------------------------------------------
+namespace {
+// the 48-bit java.util.Random state in rnd_state[0]; false (+ exception) when the array is missing
+bool state_in(JNIEnv* env, jlongArray rnd_state, const char* what, uint64_t* state)
+{
+    if (env->ExceptionCheck()) return false;
+    if (!rnd_state || env->GetArrayLength(rnd_state) < 1) { throw_new(env, "java/lang/IllegalArgumentException", what); return false; }
+    jlong st = 0;
+    env->GetLongArrayRegion(rnd_state, 0, 1, &st);
+    if (env->ExceptionCheck()) return false;
+    *state = static_cast<uint64_t>(st);
+    return true;
+}
+}  // namespace
+
+JNIEXPORT void JNICALL JNI_FN(refract3d)(JNIEnv* env, jclass, jlong h, jobject img, jobject ri_img, jlongArray dim, jboolean illum, jint z,
+                                         jdouble ls_middle, jdouble ls_edge, jdouble ri, jlong num_rays, jlongArray rnd_state, jobject image,
+                                         jobject weight)
+{
+    Dim d(env, dim);
+    if (!d.ok) return;
+    float* pi = fptr(env, img, d.n(), "refract3d: image buffer smaller than the dimensions");
+    float* pr = fptr(env, ri_img, d.n(), "refract3d: refractive-index buffer smaller than the dimensions");
+    float* po = fptr(env, image, d.n(), "refract3d: output image buffer smaller than the dimensions");
+    float* pw = fptr(env, weight, d.n(), "refract3d: output weight buffer smaller than the dimensions");
+    if (!pi || !pr || !po || !pw) return;
+    uint64_t state = 0;
+    if (!state_in(env, rnd_state, "refract3d: long[1] state expected", &state)) return;
+    const int rc = mvsim_refract3d(ctx_of(h), pi, pr, d.d, illum ? 1 : 0, z, ls_middle, ls_edge, ri, num_rays, &state, po, pw, nullptr);
+    if (rc != MVSIM_OK) { throw_for(env, rc); return; }
+    const jlong st = static_cast<jlong>(state);
+    env->SetLongArrayRegion(rnd_state, 0, 1, &st);
+}
+
+JNIEXPORT void JNICALL JNI_FN(projectToCamera)(JNIEnv* env, jclass, jlong h, jobject ri_img, jobject refr, jlongArray dim, jint current_z,
+                                               jint rays_per_pixel, jlongArray rnd_state, jobject proj)
+{
+    Dim d(env, dim);
+    if (!d.ok) return;
+    float* pr = fptr(env, ri_img, d.n(), "projectToCamera: refractive-index buffer smaller than the dimensions");
+    float* pf = fptr(env, refr, d.n(), "projectToCamera: refracted-volume buffer smaller than the dimensions");
+    float* pp = fptr(env, proj, d.d[0] * d.d[1], "projectToCamera: output buffer smaller than one plane");
+    if (!pr || !pf || !pp) return;
+    uint64_t state = 0;
+    if (!state_in(env, rnd_state, "projectToCamera: long[1] state expected", &state)) return;
+    const int rc = mvsim_project_to_camera(ctx_of(h), pr, pf, d.d, current_z, rays_per_pixel, &state, pp);
+    if (rc != MVSIM_OK) { throw_for(env, rc); return; }
+    const jlong st = static_cast<jlong>(state);
+    env->SetLongArrayRegion(rnd_state, 0, 1, &st);
+}
+
 // ---- per-stage operators with z-slab lists (mvsim_*_zslabs) ----------------------------------------------------------
 namespace {
 // the host pointers and plane counts of a FloatBuffer[] / long[] pair; every buffer is checked against plane * nz[i] floats

@@ -37,6 +37,14 @@ final class MvsimNative
 	static native void renderBeads( long ctx, java.nio.DoubleBuffer xyz, long n, long[] viewOffsets, java.nio.DoubleBuffer m12, int nviews,
 			long[] interval, double sigmaX, double sigmaY, double sigmaZ, FloatBuffer[] outF32, java.nio.ShortBuffer[] outU16 );
 
+	// SimulateMultiViewAberrations.refract3d (mvsim_refract3d): numRays rays drawn from rndState[0] (the 48-bit java.util.Random state,
+	// advanced on return) through imgRi; image and weight receive the injection's two volumes
+	static native void refract3d( long ctx, FloatBuffer imgIn, FloatBuffer imgRi, long[] dim, boolean illum, int z, double lsMiddle,
+			double lsEdge, double ri, long numRays, long[] rndState, FloatBuffer image, FloatBuffer weight );
+	// SimulateMultiViewAberrations.projectToCamera (mvsim_project_to_camera): proj receives dim[0] * dim[1] floats
+	static native void projectToCamera( long ctx, FloatBuffer imgRi, FloatBuffer refr, long[] dim, int currentZ, int raysPerPixel,
+			long[] rndState, FloatBuffer proj );
+
 	// the per-stage operators with volumes as z-slab lists (mvsim_*_zslabs): in[i] holds inNz[i] planes, out[j] receives outNz[j];
 	// this is how images beyond one 2 GiB direct buffer (2^29 voxels) cross the boundary -- a 512^3 image is a list of one
 	static native void rotateAroundAxisSlabs( long ctx, FloatBuffer[] in, long[] inNz, long[] dim, int axis, int degrees, FloatBuffer[] out, long[] outNz );

@@ -24,9 +24,11 @@ import numpy as np
 
 from . import _lib
 from ._lib import MvsimError, MvsimNoDeviceError, Sphere, Timings, ViewOutputs, ViewParams  # noqa: F401
+from .aberrations import ContextAberrations
 
-__all__ = ["AffineTransform3D", "Context", "Group", "JavaRandom", "SimulateBeads", "SimulateBeads2", "SimulateMultiViewDataset", "Tools", "broadcast_plan", "default_context", "MvsimError",
-           "MvsimNoDeviceError", "ViewParams", "shard_views", "version"]
+__all__ = ["AffineTransform3D", "Context", "Group", "Hessian", "JavaRandom", "Lightsheet", "Raytrace", "SimulateBeads", "SimulateBeads2", "SimulateMultiViewAberrations",
+           "SimulateMultiViewDataset", "Tools", "VolumeInjection", "broadcast_plan", "default_context", "MvsimError", "MvsimNoDeviceError", "ViewParams", "shard_views",
+           "version"]
 
 
 def broadcast_plan(nranks: int, rank: int, root: int, count: int, pieces: int = 8):
@@ -119,8 +121,9 @@ def _ptr(a: np.ndarray) -> C.c_void_p:
     return C.c_void_p(a.ctypes.data)
 
 
-class Context:
-    """One ``mvsim_ctx``: bound to one GPU, not thread-safe."""
+class Context(ContextAberrations):
+    """One ``mvsim_ctx``: bound to one GPU, not thread-safe.  (The refraction simulator's entry points -- refract3d,
+    project_to_camera, hessian_at, volume_inject, ... -- are in aberrations.ContextAberrations.)"""
 
     def __init__(self, device: int | None = None):
         self._h = C.c_void_p()
@@ -1045,3 +1048,4 @@ class SimulateTileStitching:
 
 
 from .beads import AffineTransform3D, SimulateBeads, SimulateBeads2  # noqa: E402
+from .aberrations import Hessian, Lightsheet, Raytrace, SimulateMultiViewAberrations, VolumeInjection  # noqa: E402

@@ -48,6 +48,12 @@ class Sphere(C.Structure):
     _fields_ = [("cx", C.c_int32), ("cy", C.c_int32), ("cz", C.c_int32), ("radius", C.c_int32), ("value", C.c_float)]
 
 
+class RaySteps(C.Structure):
+    """mvsim_ray_steps: host arrays the step list of refract3d is written to."""
+    _fields_ = [("capacity", C.c_int64), ("n", C.c_int64), ("xyz", C.POINTER(C.c_double)), ("value", C.POINTER(C.c_float)),
+                ("moves", C.POINTER(C.c_int32))]
+
+
 class Timings(C.Structure):
     _fields_ = [(n, C.c_float) for n in
                 ("rotate_ms", "attenuate_ms", "psf_ms", "convolve_ms", "adjust_ms", "extract_ms", "total_ms",
@@ -59,6 +65,7 @@ class Timings(C.Structure):
 
 _i64p = C.POINTER(C.c_int64)
 _vp = C.c_void_p
+_dp = C.POINTER(C.c_double)
 
 # name -> (restype, argtypes).  Must list every symbol declared in include/mvsim.h.
 SIGNATURES = {
@@ -172,6 +179,26 @@ SIGNATURES = {
                                          C.POINTER(C.c_double), C.POINTER(_vp), C.POINTER(_vp)]),
     "mvsim_beads_normalize": (C.c_int, [_vp, _vp, C.c_int64]),
     "mvsim_beads_normalize_dev": (C.c_int, [_vp, _vp, C.c_int64]),
+    "mvsim_lightsheet_fit": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, _dp]),
+    "mvsim_hessian_at": (C.c_int, [_vp, _vp, _i64p, _dp, C.c_int64, _dp, _dp, _dp]),
+    "mvsim_hessian_at_dev": (C.c_int, [_vp, _vp, _i64p, _dp, C.c_int64, _dp, _dp, _dp]),
+    "mvsim_hessian_images": (C.c_int, [_vp, _vp, _i64p, _vp, _vp]),
+    "mvsim_hessian_images_dev": (C.c_int, [_vp, _vp, _i64p, _vp, _vp]),
+    "mvsim_refract3d_ray_starts": (C.c_int, [_vp, C.POINTER(C.c_uint64), _i64p, C.c_int, C.c_int, _dp, C.c_int64, _dp, _dp]),
+    "mvsim_camera_ray_starts": (C.c_int, [_vp, C.POINTER(C.c_uint64), _i64p, C.c_int, _dp]),
+    "mvsim_refract3d": (C.c_int, [_vp, _vp, _vp, _i64p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64,
+                                  C.POINTER(C.c_uint64), _vp, _vp, C.POINTER(RaySteps)]),
+    "mvsim_refract3d_dev": (C.c_int, [_vp, _vp, _vp, _i64p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64,
+                                      C.POINTER(C.c_uint64), _vp, _vp, C.POINTER(RaySteps)]),
+    "mvsim_volume_inject": (C.c_int, [_vp, _vp, _vp, _i64p, _dp, _dp, _dp, C.c_int64, C.c_int]),
+    "mvsim_volume_inject_dev": (C.c_int, [_vp, _vp, _vp, _i64p, _dp, _dp, _dp, C.c_int64, C.c_int]),
+    "mvsim_volume_inject_info": (C.c_int, [_dp, C.POINTER(C.c_int32), _dp, C.POINTER(C.c_int32)]),
+    "mvsim_volume_normalize": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp]),
+    "mvsim_volume_normalize_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp]),
+    "mvsim_volume_project": (C.c_int, [_vp, _vp, _vp, _i64p, _vp]),
+    "mvsim_volume_project_dev": (C.c_int, [_vp, _vp, _vp, _i64p, _vp]),
+    "mvsim_project_to_camera": (C.c_int, [_vp, _vp, _vp, _i64p, C.c_int, C.c_int, C.POINTER(C.c_uint64), _vp]),
+    "mvsim_project_to_camera_dev": (C.c_int, [_vp, _vp, _vp, _i64p, C.c_int, C.c_int, C.POINTER(C.c_uint64), _vp]),
 }
 
 _lib = None

@@ -1,0 +1,353 @@
+"""Mirror of the reference's refraction simulator, ``net.preibisch.simulation.SimulateMultiViewAberrations``, and of the classes it
+is made of (``Hessian``, ``raytracing.Raytrace``, ``raytracing.Lightsheet``, ``VolumeInjection``): names and argument order of the
+Java methods.  The rays are traced and injected by the HIP kernels of aberrations.hip through the ``Context`` methods below; the
+single-vector helpers of ``Raytrace`` and the light-sheet fit are a handful of fp64 operations and run on the host.
+
+Volumes are ``(Nz, Ny, Nx)`` float32 arrays, positions ``(n, 3)`` float64 with x first.  Random numbers come from a ``JavaRandom``
+that is advanced exactly as the reference advances its ``java.util.Random``.
+
+Out of scope, as in the C ABI: ``multiSpheres`` and ``simulate(rnd, dir)`` (they need ``block4.tif``, a file the reference does not
+ship), ``RayTracingTest``, ``ClearingMap``, ``RefractiveIndexMap`` and ``cluster/``."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _lib
+
+_dp = C.POINTER(C.c_double)
+
+
+def _vol(a, name="image") -> np.ndarray:
+    v = np.ascontiguousarray(a, dtype=np.float32)
+    if v.ndim != 3:
+        raise ValueError(f"{name}: expected 3 dimensions, got {v.ndim}")
+    return v
+
+
+def _dim(v):
+    nz, ny, nx = v.shape
+    return (C.c_int64 * 3)(nx, ny, nz)
+
+
+def _p(a):
+    return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def _d(a):
+    return None if a is None else a.ctypes.data_as(_dp)
+
+
+def _vec3(v):
+    return (C.c_double * 3)(*[float(x) for x in v])
+
+
+def _points(xyz) -> np.ndarray:
+    return np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+
+
+class _State:
+    """The 48-bit state of a JavaRandom as the uint64 the C ABI advances; written back on exit."""
+
+    def __init__(self, rnd, default_seed):
+        from . import JavaRandom
+        self.rnd = JavaRandom(default_seed) if rnd is None else rnd
+        if not isinstance(self.rnd, JavaRandom):
+            raise TypeError("rnd must be a JavaRandom (the generator is jumped ahead natively)")
+        self.c = C.c_uint64(self.rnd._s)
+
+    def commit(self):
+        self.rnd._s = int(self.c.value)
+
+
+class ContextAberrations:
+    """The refraction simulator's entry points of a ``Context`` (aberrations.hip through include/mvsim.h)."""
+
+    def hessian_at(self, img, xyz):
+        """Hessian of the interpolated, mirrored image at real positions and its largest eigenpair:
+        (matrix (n, 3, 3), eigenvector (n, 3), eigenvalue (n))."""
+        v, pts = _vol(img), _points(xyz)
+        n = len(pts)
+        m, vec, val = np.empty((n, 3, 3)), np.empty((n, 3)), np.empty(n)
+        _lib.check(self._L.mvsim_hessian_at(self._h, _p(v), _dim(v), _d(pts), n, _d(m), _d(vec), _d(val)))
+        return m, vec, val
+
+    def hessian_images(self, img):
+        """Hessian.java:69-99 at every voxel: (eigenvalue image (Nz, Ny, Nx), eigenvector image (3, Nz, Ny, Nx))."""
+        v = _vol(img)
+        val = np.empty(v.shape, dtype=np.float32)
+        vec = np.empty((3,) + v.shape, dtype=np.float32)
+        _lib.check(self._L.mvsim_hessian_images(self._h, _p(v), _dim(v), _p(val), _p(vec)))
+        return val, vec
+
+    def refract3d_ray_starts(self, shape, illum, z, abc, n, rnd=None):
+        """The starts of refract3d's first n rays for a (Nz, Ny, Nx) volume: (positions (n, 3), directions (n, 3)); rnd advances."""
+        st = _State(rnd, 2423)
+        dim = (C.c_int64 * 3)(shape[2], shape[1], shape[0])
+        pos, vec = np.empty((n, 3)), np.empty((n, 3))
+        _lib.check(self._L.mvsim_refract3d_ray_starts(self._h, C.byref(st.c), dim, int(bool(illum)), int(z), _vec3(abc), n, _d(pos), _d(vec)))
+        st.commit()
+        return pos, vec
+
+    def camera_ray_starts(self, shape, rays_per_pixel=500, rnd=None):
+        """The starts of projectToCamera's rays, pixel-major: (Ny * Nx * rays_per_pixel, 3); rnd advances."""
+        st = _State(rnd, 464232194)
+        dim = (C.c_int64 * 3)(shape[2], shape[1], shape[0])
+        pos = np.empty((shape[1] * shape[2] * rays_per_pixel, 3))
+        _lib.check(self._L.mvsim_camera_ray_starts(self._h, C.byref(st.c), dim, rays_per_pixel, _d(pos)))
+        st.commit()
+        return pos
+
+    def refract3d(self, img, ri_img, illum, z, ls_middle, ls_edge, ri, num_rays=200000, rnd=None, steps=False, inject=True) -> dict:
+        """SimulateMultiViewAberrations.refract3d (:261-401).  Returns {"image", "weight"} (inject) and, with steps=True,
+        {"xyz" (steps, 3), "value" (steps), "moves" (rays)}: the step list in ray order, then move order."""
+        a, b = _vol(img, "imgIn"), _vol(ri_img, "imgRi")
+        if a.shape != b.shape:
+            raise ValueError("imgIn and imgRi must have the same dimensions")
+        st = _State(rnd, 2423)                                                                    # :305
+        out = {}
+        if inject:
+            out["image"], out["weight"] = np.empty(a.shape, np.float32), np.empty(a.shape, np.float32)
+        rs = None
+        if steps:
+            cap = max(1, int(num_rays)) * a.shape[0]
+            xyz, val, mv = np.empty((cap, 3)), np.empty(cap, np.float32), np.empty(max(1, int(num_rays)), np.int32)
+            rs = _lib.RaySteps(cap, 0, _d(xyz), val.ctypes.data_as(C.POINTER(C.c_float)), mv.ctypes.data_as(C.POINTER(C.c_int32)))
+        _lib.check(self._L.mvsim_refract3d(self._h, _p(a), _p(b), _dim(a), int(bool(illum)), int(z), float(ls_middle), float(ls_edge),
+                                           float(ri), int(num_rays), C.byref(st.c), _p(out.get("image")), _p(out.get("weight")),
+                                           None if rs is None else C.byref(rs)))
+        st.commit()
+        if steps:
+            out["xyz"], out["value"], out["moves"] = xyz[:rs.n].copy(), val[:rs.n].copy(), mv[:int(num_rays)]
+        return out
+
+    def volume_inject(self, image, weight, sigma, xyz, intensity, normalized=False) -> None:
+        """VolumeInjection.addGaussian / addNormalizedGaussian for every point in list order, in place on float32 volumes."""
+        for a, name in ((image, "image"), (weight, "weight")):
+            if not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or not a.flags.writeable or a.ndim != 3:
+                raise ValueError(f"{name}: in-place injection needs a writable C-contiguous 3-D float32 numpy array")
+        if image.shape != weight.shape:
+            raise ValueError("image and weight must have the same dimensions")
+        pts = _points(xyz)
+        inten = np.ascontiguousarray(intensity, dtype=np.float64).reshape(-1)
+        if len(inten) != len(pts):
+            raise ValueError("one intensity per point")
+        _lib.check(self._L.mvsim_volume_inject(self._h, _p(image), _p(weight), _dim(image), _vec3(sigma), _d(pts), _d(inten), len(pts),
+                                               int(bool(normalized))))
+
+    def volume_normalize(self, image, weight) -> np.ndarray:
+        a, w = _vol(image), _vol(weight, "weight")
+        if a.shape != w.shape:
+            raise ValueError("image and weight must have the same dimensions")
+        out = np.empty_like(a)
+        _lib.check(self._L.mvsim_volume_normalize(self._h, _p(a), _p(w), a.size, _p(out)))
+        return out
+
+    def volume_project(self, image, weight) -> np.ndarray:
+        a, w = _vol(image), _vol(weight, "weight")
+        if a.shape != w.shape:
+            raise ValueError("image and weight must have the same dimensions")
+        out = np.empty(a.shape[1:], dtype=np.float32)
+        _lib.check(self._L.mvsim_volume_project(self._h, _p(a), _p(w), _dim(a), _p(out)))
+        return out
+
+    def project_to_camera(self, ri_img, refr, current_z, rays_per_pixel=500, rnd=None) -> np.ndarray:
+        """SimulateMultiViewAberrations.projectToCamera (:89-254): the (Ny, Nx) camera image of plane current_z."""
+        a, b = _vol(ri_img, "imgRi"), _vol(refr, "refr")
+        if a.shape != b.shape:
+            raise ValueError("imgRi and refr must have the same dimensions")
+        st = _State(rnd, 464232194)
+        out = np.empty(a.shape[1:], dtype=np.float32)
+        _lib.check(self._L.mvsim_project_to_camera(self._h, _p(a), _p(b), _dim(a), int(current_z), int(rays_per_pixel), C.byref(st.c),
+                                                   _p(out)))
+        st.commit()
+        return out
+
+
+def _ctx():
+    from . import default_context
+    return default_context()
+
+
+class Lightsheet:
+    """raytracing/Lightsheet.java: the thickness a x x + b x + c fitted through centre and both edges."""
+
+    def __init__(self, center, thicknessCenter=None, length=None, thickNessEdges=None):
+        if thicknessCenter is not None and thickNessEdges is None:      # Lightsheet(a, b, c), :66-71
+            self.a, self.b, self.c = float(center), float(thicknessCenter), float(length)
+            return
+        abc = (C.c_double * 3)()
+        _lib.check(_lib.load().mvsim_lightsheet_fit(float(center), float(thicknessCenter), float(length), float(thickNessEdges), abc))
+        self.a, self.b, self.c = abc[0], abc[1], abc[2]
+
+    def getA(self):
+        return self.a
+
+    def getB(self):
+        return self.b
+
+    def getC(self):
+        return self.c
+
+    def predict(self, x: float) -> float:
+        return self.a * x * x + self.b * x + self.c
+
+
+class Raytrace:
+    """raytracing/Raytrace.java :32-93 on single vectors (host fp64; the kernels hold the same operations)."""
+
+    @staticmethod
+    def reflect(i, n, r) -> None:
+        dotP = i[0] * n[0] + i[1] * n[1] + i[2] * n[2]
+        for d in range(3):
+            r[d] = i[d] - 2 * dotP * n[d]
+
+    @staticmethod
+    def refract(i, n, n0, n1, thetaI, t) -> float:
+        deltaN = n0 / n1
+        s = deltaN * math.sin(thetaI)
+        thetaT = math.asin(s) if -1.0 <= s <= 1.0 else float("nan")
+        if math.isnan(thetaT):
+            return thetaT
+        cosThetaI = math.cos(thetaI)
+        sinThetaT = math.sin(thetaT)
+        for d in range(3):
+            t[d] = deltaN * i[d] - n[d] * (deltaN * cosThetaI - math.sqrt(1 - sinThetaT * sinThetaT))
+        return thetaT
+
+    @staticmethod
+    def length(v) -> float:
+        return math.sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2])
+
+    @staticmethod
+    def norm(v) -> None:
+        l = Raytrace.length(v)
+        for d in range(3):
+            v[d] /= l
+
+    @staticmethod
+    def incidentAngle(i, n) -> float:
+        """:75-93 -- flips n in place and SUBTRACTS pi / 2 when the angle is >= pi / 2 (the reference's quirk, kept)."""
+        c = (n[0] * i[0] + n[1] * i[1] + n[2] * i[2]) / (math.sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]) *
+                                                           math.sqrt(i[0] * i[0] + i[1] * i[1] + i[2] * i[2]))
+        thetaI = math.acos(c) if -1.0 <= c <= 1.0 else float("nan")
+        if thetaI >= math.pi / 2:
+            for d in range(3):
+                n[d] *= -1
+            thetaI -= math.pi / 2
+        return thetaI
+
+
+class Hessian:
+    """Hessian.java on the GPU."""
+
+    @staticmethod
+    def largestEigenVector(img):
+        """:46-102 without the Gauss3 blur (blur the image first to follow the reference to the letter): (eigenvalue image,
+        eigenvector image (3, Nz, Ny, Nx))."""
+        return _ctx().hessian_images(img)
+
+    @staticmethod
+    def computeHessianMatrix3D(img, position) -> np.ndarray:
+        """:155-278 at one real position of the interpolated, mirrored image."""
+        return _ctx().hessian_at(img, [position])[0][0]
+
+    @staticmethod
+    def computeLargestEigenVectorAndValue3d(img, position):
+        """:110-147 of the Hessian at one real position: (eigenvalue, eigenvector)."""
+        _, vec, val = _ctx().hessian_at(img, [position])
+        return float(val[0]), vec[0]
+
+
+class VolumeInjection:
+    """VolumeInjection.java: Gaussians added to an image and a weight volume in call order."""
+
+    def __init__(self, image, weight, sigma, ctx=None):
+        self.image, self.weight, self.sigma = image, weight, [float(s) for s in sigma]
+        self._ctx = ctx
+        size = (C.c_int32 * 3)()
+        sw, npx = C.c_double(), C.c_int32()
+        _lib.check(_lib.load().mvsim_volume_inject_info(_vec3(self.sigma), size, C.byref(sw), C.byref(npx)))
+        self.size, self.sumWeights, self.numPixels = list(size), sw.value, npx.value
+
+    def _c(self):
+        return self._ctx or _ctx()
+
+    def getSize(self):
+        return self.size
+
+    def getImage(self):
+        return self.image
+
+    def getWeight(self):
+        return self.weight
+
+    def getSumWeights(self):
+        return self.sumWeights
+
+    def getNumPixels(self):
+        return self.numPixels
+
+    def addGaussian(self, intensity, location) -> None:
+        self._c().volume_inject(self.image, self.weight, self.sigma, [location], [intensity], False)
+
+    def addNormalizedGaussian(self, intensity, location) -> None:
+        self._c().volume_inject(self.image, self.weight, self.sigma, [location], [intensity], True)
+
+    def addGaussians(self, intensities, locations, normalized=False) -> None:
+        """Many calls of addGaussian / addNormalizedGaussian in list order as one launch sequence."""
+        self._c().volume_inject(self.image, self.weight, self.sigma, locations, intensities, normalized)
+
+    def normalize(self) -> np.ndarray:
+        return self._c().volume_normalize(self.image, self.weight)
+
+    def project(self) -> np.ndarray:
+        return self._c().volume_project(self.image, self.weight)
+
+
+class SimulateMultiViewAberrations:
+    """net.preibisch.simulation.SimulateMultiViewAberrations."""
+
+    @staticmethod
+    def _rnd():
+        from . import JavaRandom
+        if SimulateMultiViewAberrations.rnd is None:
+            SimulateMultiViewAberrations.rnd = JavaRandom(464232194)                            # :78
+        return SimulateMultiViewAberrations.rnd
+
+    rnd = None
+
+    @staticmethod
+    def inside(rayPosition, interval) -> bool:
+        """:80-87 -- interval: a (Nz, Ny, Nx) array or shape."""
+        shape = getattr(interval, "shape", interval)
+        return all(0 <= rayPosition[d] <= shape[2 - d] - 1 for d in range(len(rayPosition)))
+
+    @staticmethod
+    def refract3d(imgIn, imgRi, illum, z, lsMiddle, lsEdge, ri, numRays=200000, ctx=None) -> VolumeInjection:
+        """:261-401 -- the reference's 200 000 rays from new Random(2423)."""
+        c = ctx or _ctx()
+        out = c.refract3d(imgIn, imgRi, illum, z, lsMiddle, lsEdge, ri, num_rays=numRays)
+        return VolumeInjection(out["image"], out["weight"], [0.5, 0.5, 0.5], ctx=ctx)
+
+    @staticmethod
+    def projectToCamera(imgRi, refr, ri, currentzPlane, raysPerPixel=500, ctx=None) -> np.ndarray:
+        """:89-254 -- draws from the class's generator; ``ri`` is accepted and unused, as in the reference (:117)."""
+        c = ctx or _ctx()
+        return c.project_to_camera(imgRi, refr, currentzPlane, raysPerPixel, SimulateMultiViewAberrations._rnd())
+
+    @staticmethod
+    def downSample2x(img) -> np.ndarray:
+        """:442-472 -- the kernel of SimulateMultiViewDataset.downSample2x."""
+        return _ctx().downsample2x(img)
+
+    @staticmethod
+    def simulate(imgIn, imgRi, illum, lsMiddle, lsEdge, ri, z, numRays=200000, raysPerPixel=500, ctx=None) -> dict:
+        """What simulate(illum, lsMiddle, lsEdge, ri, dir, service, z) computes for one z plane on a given image / index pair:
+        {"refr_img", "refr_weight", "proj"}; the caller saves them."""
+        c = ctx or _ctx()
+        out = c.refract3d(imgIn, imgRi, illum, z, lsMiddle, lsEdge, ri, num_rays=numRays)
+        proj = c.project_to_camera(imgRi, out["image"], z, raysPerPixel, SimulateMultiViewAberrations._rnd())
+        return {"refr_img": out["image"], "refr_weight": out["weight"], "proj": proj}

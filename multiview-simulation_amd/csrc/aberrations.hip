@@ -1,0 +1,990 @@
+// The refraction simulator (SimulateMultiViewAberrations.java): light-sheet rays refracted through a refractive-index volume and
+// injected as Gaussians (refract3d, :261-401), camera rays summing the refracted volume (projectToCamera, :89-254), and the pieces
+// they are made of (Hessian.java, raytracing/Raytrace.java, VolumeInjection.java).
+//
+//   ray step   one __device__ function for both tracers, with the reference's rounding points (the build compiles with
+//              -ffp-contract=off): the n-linear sampler over a mirrored volume as an ACCESSOR that is moved -- an fp64 position plus
+//              the integer position of its lower-corner tap; setPosition / move(distance) put the tap at floor(position), fwd / bck
+//              move both by one, the weights are position - tap, so (p + 1) - 1 enters the weights as the reference computes it --,
+//              the Hessian by the reference's literal sequence of moves (Hessian.java:155-278), the largest eigenpair by Householder
+//              tridiagonalisation and implicit QL (EISPACK tred2 / tql2 as JAMA runs them for a symmetric matrix; + - * / sqrt only),
+//              Snell refraction (Raytrace.java:42-93; acos, asin, sin, cos of the device library).
+//   starts     ray i takes its draws of the caller's java.util.Random by jumping the 48-bit generator ahead (a^k and
+//              c (a^k - 1) / (a - 1) mod 2^48 by squaring): ray starts are bit-exact whatever the launch shape.
+//   refract3d  one ray per lane writes a step record (x, y, z, valueIm) per move at slot ray * maxMoves + move and its move count;
+//              an exclusive scan over the counts compacts the records into the step LIST in ray order, then move order.
+//   injection  VolumeInjection.addGaussian in list order into image and weight.  Float addition does not associate, so -- as for
+//              the bead images (beads.hip) -- nothing is scattered with atomics: cull (box per step, bricks it overlaps) -> scan ->
+//              emit (brick, step) pairs -> stable radix sort by brick -> one block per brick adds its steps in list order, every voxel
+//              owned by one lane.  Lists whose pairs exceed the option "beads_pair_cap" run in ranges, each continuing from the
+//              image and weight the previous one left: the same sequential sum.
+//   camera     one block per camera pixel, lanes over the pixel's rays; the per-ray fp64 signals go to LDS and ONE lane adds them in
+//              ray order (avgValue, :242).
+#include "common.h"
+
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+namespace mvsim {
+
+namespace {
+
+// ---- java.util.Random, jumped ahead -----------------------------------------------------------------------------------------
+constexpr unsigned long long JR_MASK = (1ULL << 48) - 1, JR_A = 0x5DEECE66DULL, JR_C = 0xBULL;
+
+// the state after k steps from s: s * a^k + c (a^(k-1) + ... + 1)  (mod 2^48), composing the affine map with itself by squaring
+__host__ __device__ inline unsigned long long jr_jump(unsigned long long s, unsigned long long k)
+{
+    unsigned long long A = 1, C = 0, a = JR_A, c = JR_C;
+    while (k) {
+        if (k & 1) { A = (A * a) & JR_MASK; C = (C * a + c) & JR_MASK; }
+        c = ((a + 1) * c) & JR_MASK;
+        a = (a * a) & JR_MASK;
+        k >>= 1;
+    }
+    return (s * A + C) & JR_MASK;
+}
+
+__device__ __forceinline__ int jr_next(unsigned long long& s, int bits)
+{
+    s = (s * JR_A + JR_C) & JR_MASK;
+    return (int)((long long)s >> (48 - bits));
+}
+
+__device__ __forceinline__ double jr_double(unsigned long long& s)
+{
+    const long long hi = (long long)jr_next(s, 26) << 27;
+    return (double)(hi + jr_next(s, 27)) * 0x1.0p-53;
+}
+
+// ---- the interpolating accessor (ImgLib2 NLinearInterpolator over Views.extendMirrorSingle) ---------------------------------
+__device__ __forceinline__ int mirror_single(int i, int n)
+{
+    if ((unsigned)i < (unsigned)n) return i;
+    const int period = 2 * n - 2;
+    i %= period;
+    if (i < 0) i += period;
+    return i < n ? i : period - i;
+}
+
+struct Accessor {
+    const float* img;
+    int nx, ny, nz;
+    double px, py, pz;      // the real position
+    int tx, ty, tz;         // the lower-corner tap
+    __device__ __forceinline__ void set(double x, double y, double z)
+    {
+        px = x; py = y; pz = z;
+        tx = (int)floor(x); ty = (int)floor(y); tz = (int)floor(z);
+    }
+    template <int D> __device__ __forceinline__ void fwd()
+    {
+        if (D == 0) { px += 1.0; tx += 1; } else if (D == 1) { py += 1.0; ty += 1; } else { pz += 1.0; tz += 1; }
+    }
+    template <int D> __device__ __forceinline__ void bck()
+    {
+        if (D == 0) { px -= 1.0; tx -= 1; } else if (D == 1) { py -= 1.0; ty -= 1; } else { pz -= 1.0; tz -= 1; }
+    }
+    __device__ __forceinline__ void move(double dx, double dy, double dz)
+    {
+        px += dx; tx = (int)floor(px);
+        py += dy; ty = (int)floor(py);
+        pz += dz; tz = (int)floor(pz);
+    }
+    __device__ __forceinline__ float tap(int x, int y, int z) const
+    {
+        return img[(long long)mirror_single(x, nx) + (long long)nx * ((long long)mirror_single(y, ny) + (long long)ny * mirror_single(z, nz))];
+    }
+    // taps in Gray-code order, each (float)(v * w) with the weight product in fp64, float accumulation
+    __device__ __forceinline__ float get() const
+    {
+        const double w0 = px - (double)tx, w1 = py - (double)ty, w2 = pz - (double)tz;
+        const double w0n = 1.0 - w0, w1n = 1.0 - w1, w2n = 1.0 - w2;
+        const int x0 = mirror_single(tx, nx), x1 = mirror_single(tx + 1, nx);
+        const long long y0 = (long long)nx * mirror_single(ty, ny), y1 = (long long)nx * mirror_single(ty + 1, ny);
+        const long long z0 = (long long)nx * ny * mirror_single(tz, nz), z1 = (long long)nx * ny * mirror_single(tz + 1, nz);
+        float s = (float)((double)img[x0 + y0 + z0] * (w0n * w1n * w2n));
+        s += (float)((double)img[x1 + y0 + z0] * (w0 * w1n * w2n));
+        s += (float)((double)img[x1 + y1 + z0] * (w0 * w1 * w2n));
+        s += (float)((double)img[x0 + y1 + z0] * (w0n * w1 * w2n));
+        s += (float)((double)img[x0 + y1 + z1] * (w0n * w1 * w2));
+        s += (float)((double)img[x1 + y1 + z1] * (w0 * w1 * w2));
+        s += (float)((double)img[x1 + y0 + z1] * (w0 * w1n * w2));
+        s += (float)((double)img[x0 + y0 + z1] * (w0n * w1n * w2));
+        return s;
+    }
+};
+
+// ---- Hessian.computeHessianMatrix3D (:155-278) by the reference's moves -----------------------------------------------------
+template <int D> __device__ __forceinline__ double hess_second(Accessor& a, double temp)
+{
+    a.fwd<D>();
+    double h = (double)a.get();
+    h -= temp;
+    a.bck<D>();
+    a.bck<D>();
+    h += (double)a.get();
+    a.fwd<D>();
+    return h;
+}
+
+template <int U, int V> __device__ __forceinline__ double hess_mixed(Accessor& a)
+{
+    a.fwd<U>(); a.fwd<V>();
+    const double p = (double)a.get();
+    a.bck<U>(); a.bck<U>();
+    const double q = (double)a.get();
+    a.fwd<U>(); a.fwd<U>(); a.bck<V>(); a.bck<V>();
+    const double r = (double)a.get();
+    a.bck<U>(); a.bck<U>();
+    const double s = (double)a.get();
+    a.fwd<U>(); a.fwd<V>();
+    return ((p - q) / 2 - (r - s) / 2) / 2;
+}
+
+// m = {xx, yy, zz, xy, xz, yz}
+__device__ __forceinline__ void hessian_by_moves(Accessor& a, double m[6])
+{
+    const double temp = (double)(2 * a.get());
+    m[0] = hess_second<0>(a, temp);
+    m[1] = hess_second<1>(a, temp);
+    m[2] = hess_second<2>(a, temp);
+    m[3] = hess_mixed<0, 1>(a);
+    m[4] = hess_mixed<0, 2>(a);
+    m[5] = hess_mixed<1, 2>(a);
+}
+
+// ---- Hessian.computeLargestEigenVectorAndValue3d (:110-147): JAMA's symmetric path for n = 3 ---------------------------------
+__device__ __forceinline__ double jama_hypot(double a, double b)
+{
+    double r;
+    if (fabs(a) > fabs(b)) { r = b / a; r = fabs(a) * sqrt(1 + r * r); }
+    else if (b != 0) { r = a / b; r = fabs(b) * sqrt(1 + r * r); }
+    else r = 0.0;
+    return r;
+}
+
+constexpr int QL_MAX_SWEEPS = 64;     // JAMA has no limit; a matrix of finite entries converges in a handful of sweeps
+
+// m = {xx, yy, zz, xy, xz, yz}; returns the eigenvalue of largest magnitude (first wins on ties, eigenvalues ascending) and its
+// eigenvector with the sign the decomposition gives it
+__device__ double largest_eigenpair(const double m[6], double vec[3])
+{
+    constexpr int N = 3;
+    double V[N][N] = {{m[0], m[3], m[4]}, {m[3], m[1], m[5]}, {m[4], m[5], m[2]}};
+    double d[N], e[N];
+    // tred2
+#pragma unroll
+    for (int j = 0; j < N; ++j) d[j] = V[N - 1][j];
+#pragma unroll
+    for (int i = N - 1; i > 0; --i) {
+        double scale = 0.0, h = 0.0;
+#pragma unroll
+        for (int k = 0; k < i; ++k) scale = scale + fabs(d[k]);
+        if (scale == 0.0) {
+            e[i] = d[i - 1];
+#pragma unroll
+            for (int j = 0; j < i; ++j) { d[j] = V[i - 1][j]; V[i][j] = 0.0; V[j][i] = 0.0; }
+        } else {
+#pragma unroll
+            for (int k = 0; k < i; ++k) { d[k] /= scale; h += d[k] * d[k]; }
+            double f = d[i - 1];
+            double g = sqrt(h);
+            if (f > 0) g = -g;
+            e[i] = scale * g;
+            h = h - f * g;
+            d[i - 1] = f - g;
+#pragma unroll
+            for (int j = 0; j < i; ++j) e[j] = 0.0;
+#pragma unroll
+            for (int j = 0; j < i; ++j) {
+                f = d[j];
+                V[j][i] = f;
+                g = e[j] + V[j][j] * f;
+#pragma unroll
+                for (int k = j + 1; k <= i - 1; ++k) { g += V[k][j] * d[k]; e[k] += V[k][j] * f; }
+                e[j] = g;
+            }
+            f = 0.0;
+#pragma unroll
+            for (int j = 0; j < i; ++j) { e[j] /= h; f += e[j] * d[j]; }
+            const double hh = f / (h + h);
+#pragma unroll
+            for (int j = 0; j < i; ++j) e[j] -= hh * d[j];
+#pragma unroll
+            for (int j = 0; j < i; ++j) {
+                f = d[j];
+                g = e[j];
+#pragma unroll
+                for (int k = j; k <= i - 1; ++k) V[k][j] -= (f * e[k] + g * d[k]);
+                d[j] = V[i - 1][j];
+                V[i][j] = 0.0;
+            }
+        }
+        d[i] = h;
+    }
+#pragma unroll
+    for (int i = 0; i < N - 1; ++i) {
+        V[N - 1][i] = V[i][i];
+        V[i][i] = 1.0;
+        const double h = d[i + 1];
+        if (h != 0.0) {
+#pragma unroll
+            for (int k = 0; k <= i; ++k) d[k] = V[k][i + 1] / h;
+#pragma unroll
+            for (int j = 0; j <= i; ++j) {
+                double g = 0.0;
+#pragma unroll
+                for (int k = 0; k <= i; ++k) g += V[k][i + 1] * V[k][j];
+#pragma unroll
+                for (int k = 0; k <= i; ++k) V[k][j] -= g * d[k];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k <= i; ++k) V[k][i + 1] = 0.0;
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) { d[j] = V[N - 1][j]; V[N - 1][j] = 0.0; }
+    V[N - 1][N - 1] = 1.0;
+    e[0] = 0.0;
+
+    // tql2
+#pragma unroll
+    for (int i = 1; i < N; ++i) e[i - 1] = e[i];
+    e[N - 1] = 0.0;
+    double f = 0.0, tst1 = 0.0;
+    const double eps = 0x1.0p-52;
+#pragma unroll
+    for (int l = 0; l < N; ++l) {
+        const double t = fabs(d[l]) + fabs(e[l]);
+        tst1 = tst1 > t ? tst1 : t;
+        int mm = l;
+#pragma unroll
+        for (int q = l; q < N; ++q)               // while (m < n) { if (|e[m]| <= eps tst1) break; m++; }; e[n-1] == 0 ends it
+            if (mm == q && !(fabs(e[q]) <= eps * tst1)) mm = q + 1;
+        if (mm > N - 1) mm = N - 1;               // only a NaN reaches this: e[n-1] == 0 passes the test otherwise
+        if (mm > l) {
+            int iter = 0;
+            do {
+                iter = iter + 1;
+                double g = d[l];
+                double p = (d[l + 1 < N ? l + 1 : l] - g) / (2.0 * e[l]);
+                double r = jama_hypot(p, 1.0);
+                if (p < 0) r = -r;
+                d[l] = e[l] / (p + r);
+                d[l + 1 < N ? l + 1 : l] = e[l] * (p + r);
+                const double dl1 = d[l + 1 < N ? l + 1 : l];
+                double h = g - d[l];
+#pragma unroll
+                for (int i = l + 2; i < N; ++i) d[i] -= h;
+                f = f + h;
+                p = mm == 2 ? d[2] : d[1];
+                double c = 1.0, c2 = c, c3 = c;
+                const double el1 = e[l + 1 < N ? l + 1 : l];
+                double s = 0.0, s2 = 0.0;
+#pragma unroll
+                for (int i = N - 2; i >= l; --i) {
+                    if (i > mm - 1) continue;
+                    c3 = c2;
+                    c2 = c;
+                    s2 = s;
+                    g = c * e[i];
+                    h = c * p;
+                    r = jama_hypot(p, e[i]);
+                    e[i + 1] = s * r;
+                    s = e[i] / r;
+                    c = p / r;
+                    p = c * d[i] - s * g;
+                    d[i + 1] = h + s * (c * g + s * d[i]);
+#pragma unroll
+                    for (int k = 0; k < N; ++k) {
+                        h = V[k][i + 1];
+                        V[k][i + 1] = s * V[k][i] + c * h;
+                        V[k][i] = c * V[k][i] - s * h;
+                    }
+                }
+                p = -s * s2 * c3 * el1 * e[l] / dl1;
+                e[l] = s * p;
+                d[l] = c * p;
+            } while (fabs(e[l]) > eps * tst1 && iter < QL_MAX_SWEEPS);
+        }
+        d[l] = d[l] + f;
+        e[l] = 0.0;
+    }
+    // ascending order, columns swapped with their values
+#pragma unroll
+    for (int i = 0; i < N - 1; ++i) {
+        int k = i;
+        double p = d[i];
+#pragma unroll
+        for (int j = i + 1; j < N; ++j)
+            if (d[j] < p) { k = j; p = d[j]; }
+        if (k != i) {
+#pragma unroll
+            for (int j = i + 1; j < N; ++j)
+                if (j == k) {
+                    d[j] = d[i];
+#pragma unroll
+                    for (int r = 0; r < N; ++r) { const double t = V[r][i]; V[r][i] = V[r][j]; V[r][j] = t; }
+                }
+            d[i] = p;
+        }
+    }
+    int idx = 0;
+    double best = d[0];
+#pragma unroll
+    for (int i = 1; i < N; ++i)
+        if (fabs(d[i]) > fabs(best)) { best = d[i]; idx = i; }
+#pragma unroll
+    for (int r = 0; r < N; ++r) vec[r] = idx == 0 ? V[r][0] : (idx == 1 ? V[r][1] : V[r][2]);
+    return best;
+}
+
+// ---- Raytrace ---------------------------------------------------------------------------------------------------------------
+constexpr double HALF_PI = 1.5707963267948966;      // Math.PI / 2
+
+__device__ __forceinline__ void norm3(double v[3])
+{
+    const double l = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    v[0] /= l; v[1] /= l; v[2] /= l;
+}
+
+// One move's refraction (SimulateMultiViewAberrations.java:155-214 and :331-378): the Hessian of the index volume at pos, and where
+// its largest eigenvalue exceeds 0.01 in magnitude, Snell's law across the plane its eigenvector is normal to.
+__device__ __forceinline__ void refract_step(Accessor& ri, const double pos[3], double vec[3], double nA, double nB)
+{
+    double m[6], en[3];
+    ri.set(pos[0], pos[1], pos[2]);
+    hessian_by_moves(ri, m);
+    const double ev = largest_eigenpair(m, en);
+    if (fabs(ev) > 0.01) {
+        ri.set(pos[0], pos[1], pos[2]);
+        ri.move(-vec[0], -vec[1], -vec[2]);
+        const double i0 = (double)ri.get();
+        ri.move(2 * vec[0], 2 * vec[1], 2 * vec[2]);
+        const double i1 = (double)ri.get();
+        const double n0 = (nB - nA) * i0 + nA;
+        const double n1 = (nB - nA) * i1 + nA;
+        // Raytrace.incidentAngle (:75-93), quirk kept: the normal is flipped and the angle reduced by pi / 2 (not mirrored)
+        double thetaI = acos((en[0] * vec[0] + en[1] * vec[1] + en[2] * vec[2]) /
+                             (sqrt(en[0] * en[0] + en[1] * en[1] + en[2] * en[2]) * sqrt(vec[0] * vec[0] + vec[1] * vec[1] + vec[2] * vec[2])));
+        if (thetaI >= HALF_PI) {
+            en[0] *= -1; en[1] *= -1; en[2] *= -1;
+            thetaI -= HALF_PI;
+        }
+        // Raytrace.refract (:42-59); total reflection (NaN): the ray keeps its direction
+        const double deltaN = n0 / n1;
+        const double thetaT = asin(deltaN * sin(thetaI));
+        double t[3] = {vec[0], vec[1], vec[2]};
+        if (thetaT == thetaT) {
+            const double cosThetaI = cos(thetaI);
+            const double sinThetaT = sin(thetaT);
+            const double k = deltaN * cosThetaI - sqrt(1 - sinThetaT * sinThetaT);
+            t[0] = deltaN * vec[0] - en[0] * k;
+            t[1] = deltaN * vec[1] - en[1] * k;
+            t[2] = deltaN * vec[2] - en[2] * k;
+        }
+        norm3(t);
+        vec[0] = t[0]; vec[1] = t[1]; vec[2] = t[2];
+    }
+}
+
+__device__ __forceinline__ bool inside3(const double p[3], int nx, int ny, int nz)
+{
+    return !(p[0] < 0.0 || p[0] > (double)(nx - 1) || p[1] < 0.0 || p[1] > (double)(ny - 1) || p[2] < 0.0 || p[2] > (double)(nz - 1));
+}
+
+// ---- ray starts -------------------------------------------------------------------------------------------------------------
+struct SheetParams {
+    unsigned long long state;     // java.util.Random state in front of ray 0
+    double a, b, c;               // Lightsheet: a x x + b x + c
+    int    illum, z;
+};
+
+// refract3d :309-319: ray i consumes draws 3i .. 3i + 2 of nextDouble(), two generator steps each
+__device__ __forceinline__ void sheet_ray_start(const SheetParams& sp, long long ray, int nx, int ny, double pos[3], double vec[3])
+{
+    unsigned long long s = jr_jump(sp.state, 6ULL * (unsigned long long)ray);
+    pos[0] = jr_double(s) * (double)(nx - 1);
+    pos[1] = sp.illum ? (double)(ny - 1) : 0.0;
+    const double th = sp.a * pos[0] * pos[0] + sp.b * pos[0] + sp.c;
+    pos[2] = (double)sp.z + (jr_double(s) * th) - th / 2.0;
+    vec[0] = (jr_double(s) - 0.5) / 5;
+    vec[1] = sp.illum ? -1.0 : 1.0;
+    vec[2] = 0.0;
+    norm3(vec);
+}
+
+// projectToCamera :137-143: ray (pixel p, i) consumes draws 2 (rays p + i) ..; start z = 1, direction +z
+__device__ __forceinline__ void camera_ray_start(unsigned long long state, long long ray, int px, int py, double pos[3], double vec[3])
+{
+    unsigned long long s = jr_jump(state, 4ULL * (unsigned long long)ray);
+    pos[0] = (double)px + (jr_double(s) - 0.5);
+    pos[1] = (double)py + (jr_double(s) - 0.5);
+    pos[2] = 1.0;
+    vec[0] = 0.0; vec[1] = 0.0; vec[2] = 1.0;
+}
+
+__global__ __launch_bounds__(256) void k_ray_starts(SheetParams sp, int camera, int rays_per_pixel, int nx, int ny, long long n,
+                                                    double* __restrict__ pos3, double* __restrict__ dir3)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double p[3], v[3];
+    if (camera) {
+        const long long pix = i / rays_per_pixel;
+        camera_ray_start(sp.state, i, (int)(pix % nx), (int)(pix / nx), p, v);
+    } else {
+        sheet_ray_start(sp, i, nx, ny, p, v);
+    }
+    for (int d = 0; d < 3; ++d) {
+        pos3[3 * i + d] = p[d];
+        if (dir3) dir3[3 * i + d] = v[d];
+    }
+}
+
+// ---- refract3d: trace -------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_refract3d_trace(const float* __restrict__ img, const float* __restrict__ ri_img, int nx, int ny,
+                                                        int nz, SheetParams sp, double nB, long long ray0, int nrays, int max_moves,
+                                                        double* __restrict__ slot_xyz, float* __restrict__ slot_val,
+                                                        int* __restrict__ moves_out)
+{
+    const int r = blockIdx.x * 64 + threadIdx.x;
+    if (r >= nrays) return;
+    double pos[3], vec[3];
+    sheet_ray_start(sp, ray0 + r, nx, ny, pos, vec);
+    Accessor aim{img, nx, ny, nz, 0, 0, 0, 0, 0, 0}, ari{ri_img, nx, ny, nz, 0, 0, 0, 0, 0, 0};
+    int moves = 0;
+    const long long base = (long long)r * max_moves;
+    while (inside3(pos, nx, ny, nz) && moves < max_moves) {
+        aim.set(pos[0], pos[1], pos[2]);
+        const float value = aim.get();
+        const double at[3] = {pos[0], pos[1], pos[2]};
+        refract_step(ari, pos, vec, 1.00, nB);
+        double* q = slot_xyz + 3 * (base + moves);
+        q[0] = at[0]; q[1] = at[1]; q[2] = at[2];
+        slot_val[base + moves] = value;
+        ++moves;
+        pos[0] += vec[0]; pos[1] += vec[1]; pos[2] += vec[2];
+    }
+    moves_out[r] = moves;
+}
+
+__global__ __launch_bounds__(256) void k_compact_steps(const double* __restrict__ slot_xyz, const float* __restrict__ slot_val,
+                                                       const int* __restrict__ moves, const int* __restrict__ offs, int nrays, int max_moves,
+                                                       double* __restrict__ xyz, float* __restrict__ val)
+{
+    const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (s >= (long long)nrays * max_moves) return;
+    const int r = (int)(s / max_moves), mv = (int)(s - (long long)r * max_moves);
+    if (mv >= moves[r]) return;
+    const long long o = (long long)offs[r] + mv;
+    xyz[3 * o] = slot_xyz[3 * s]; xyz[3 * o + 1] = slot_xyz[3 * s + 1]; xyz[3 * o + 2] = slot_xyz[3 * s + 2];
+    val[o] = slot_val[s];
+}
+
+// ---- projectToCamera --------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_project_to_camera(const float* __restrict__ ri_img, const float* __restrict__ refr, int nx, int ny,
+                                                           int nz, int current_z, int rays_per_pixel, unsigned long long state,
+                                                           float* __restrict__ proj)
+{
+    extern __shared__ double s_signal[];
+    const int pix = blockIdx.x;
+    const int px = pix % nx, py = pix / nx;
+    const int max_moves = nz;
+    const double two_sq_sigma = 2 * 4.0 * 4.0;
+    Accessor ari{ri_img, nx, ny, nz, 0, 0, 0, 0, 0, 0}, aref{refr, nx, ny, nz, 0, 0, 0, 0, 0, 0};
+    for (int i = threadIdx.x; i < rays_per_pixel; i += 256) {
+        double pos[3], vec[3], signal = 0.0;
+        camera_ray_start(state, (long long)pix * rays_per_pixel + i, px, py, pos, vec);
+        int moves = 0;
+        while (inside3(pos, nx, ny, nz) && moves < max_moves) {
+            ++moves;
+            const double at[3] = {pos[0], pos[1], pos[2]};
+            refract_step(ari, pos, vec, 1.00, 1.01);                      // nB = 1.01 whatever ri is (:117)
+            aref.set(at[0], at[1], at[2]);
+            const double zo = fabs(at[2] - (double)current_z);
+            signal += (double)aref.get() * exp(-(zo * zo) / two_sq_sigma);
+            pos[0] += vec[0]; pos[1] += vec[1]; pos[2] += vec[2];
+        }
+        s_signal[i] = signal;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double avg = 0.0;
+        for (int i = 0; i < rays_per_pixel; ++i) avg += s_signal[i];
+        proj[pix] = (float)(avg / 10.0);
+    }
+}
+
+// ---- Hessian at positions / over the image ----------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_hessian_at(const float* __restrict__ img, int nx, int ny, int nz, const double* __restrict__ xyz,
+                                                   long long n, double* __restrict__ matrix9, double* __restrict__ vec3,
+                                                   double* __restrict__ val)
+{
+    const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    Accessor a{img, nx, ny, nz, 0, 0, 0, 0, 0, 0};
+    a.set(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+    double m[6], v[3];
+    hessian_by_moves(a, m);
+    const double ev = largest_eigenpair(m, v);
+    double* q = matrix9 + 9 * i;
+    q[0] = m[0]; q[1] = m[3]; q[2] = m[4];
+    q[3] = m[3]; q[4] = m[1]; q[5] = m[5];
+    q[6] = m[4]; q[7] = m[5]; q[8] = m[2];
+    vec3[3 * i] = v[0]; vec3[3 * i + 1] = v[1]; vec3[3 * i + 2] = v[2];
+    val[i] = ev;
+}
+
+// Hessian.largestEigenVector (:69-99) without its blur: integer positions through the mirror
+__global__ __launch_bounds__(64) void k_hessian_images(const float* __restrict__ img, int nx, int ny, int nz, float* __restrict__ eigval,
+                                                       float* __restrict__ eigvec)
+{
+    const long long nvox = (long long)nx * ny * nz;
+    const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (i >= nvox) return;
+    const int x = (int)(i % nx), y = (int)((i / nx) % ny), z = (int)(i / ((long long)nx * ny));
+    Accessor a{img, nx, ny, nz, 0, 0, 0, 0, 0, 0};
+    const double temp = (double)(2 * a.tap(x, y, z));
+    double m[6], v[3];
+    m[0] = (double)a.tap(x + 1, y, z); m[0] -= temp; m[0] += (double)a.tap(x - 1, y, z);
+    m[1] = (double)a.tap(x, y + 1, z); m[1] -= temp; m[1] += (double)a.tap(x, y - 1, z);
+    m[2] = (double)a.tap(x, y, z + 1); m[2] -= temp; m[2] += (double)a.tap(x, y, z - 1);
+    m[3] = (((double)a.tap(x + 1, y + 1, z) - (double)a.tap(x - 1, y + 1, z)) / 2 -
+            ((double)a.tap(x + 1, y - 1, z) - (double)a.tap(x - 1, y - 1, z)) / 2) / 2;
+    m[4] = (((double)a.tap(x + 1, y, z + 1) - (double)a.tap(x - 1, y, z + 1)) / 2 -
+            ((double)a.tap(x + 1, y, z - 1) - (double)a.tap(x - 1, y, z - 1)) / 2) / 2;
+    m[5] = (((double)a.tap(x, y + 1, z + 1) - (double)a.tap(x, y - 1, z + 1)) / 2 -
+            ((double)a.tap(x, y + 1, z - 1) - (double)a.tap(x, y - 1, z - 1)) / 2) / 2;
+    const double ev = largest_eigenpair(m, v);
+    eigval[i] = (float)ev;
+    eigvec[i] = (float)v[0];
+    eigvec[i + nvox] = (float)v[1];
+    eigvec[i + 2 * nvox] = (float)v[2];
+}
+
+// ---- VolumeInjection: normalize (:115-135), project (:199-232) ---------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_volume_normalize(const float* __restrict__ image, const float* __restrict__ weight, long long n,
+                                                          float* __restrict__ out)
+{
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const float w = weight[i], v = image[i];
+        out[i] = w > 1.0f ? v / w : v;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_volume_project(const float* __restrict__ image, const float* __restrict__ weight, int nx, int ny,
+                                                        int nz, float* __restrict__ proj)
+{
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x, plane = (long long)nx * ny;
+    if (p >= plane) return;
+    double sum = 0.0, count = 0.0;
+    for (int z = 0; z < nz; ++z) {
+        const float v = image[p + plane * z], w = weight[p + plane * z];
+        if (v > 0) {
+            sum += (double)(v * w);       // float * float, widened afterwards (:223)
+            count += (double)w;
+        }
+    }
+    proj[p] = (float)(sum / count);       // an empty column: 0 / 0 = NaN, as the reference
+}
+
+// ---- VolumeInjection.addGaussian (:175-197) in list order -------------------------------------------------------------------
+constexpr int BX = 32, BY = 8, BZ = 16;     // brick, as beads.hip: two 32-voxel rows per wave, four waves, 16 planes per lane
+constexpr int CH = 32;                      // steps per LDS chunk
+constexpr int NTAB = BX + BY + BZ;
+
+struct InjRec {
+    double loc[3];
+    double inten;
+    int    lo[3], hi[3];    // box clipped to the image, inclusive
+};
+
+// Java Math.round(double) for finite values: floor, plus one when the fraction is >= 0.5
+__device__ __forceinline__ long long java_round_d(double x)
+{
+    const double f = floor(x);
+    return (long long)f + ((x - f) >= 0.5 ? 1 : 0);
+}
+
+__global__ __launch_bounds__(256) void k_inject_cull(const double* __restrict__ xyz, const double* __restrict__ inten, const float* __restrict__ val,
+                                                     double sumw, long long n, InjRec* __restrict__ recs, uint32_t* __restrict__ counts, int nx,
+                                                     int ny, int nz, int s0, int s1, int s2)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int dim[3] = {nx, ny, nz}, size[3] = {s0, s1, s2}, bs[3] = {BX, BY, BZ};
+    InjRec r;
+    double v = val ? (double)val[i] : inten[i];
+    if (sumw != 0.0) v = v / sumw;                               // addNormalizedGaussian (:168-173)
+    r.inten = v;
+    uint32_t cnt = 1;
+    for (int d = 0; d < 3; ++d) {
+        const double p = xyz[3 * i + d];
+        r.loc[d] = p;
+        r.lo[d] = 1; r.hi[d] = 0;
+        if (!(fabs(p) < 1.0e9)) { cnt = 0; continue; }          // nowhere near the image (or NaN): every write is dropped
+        const long long lo = java_round_d(p) - size[d] / 2;      // getCursor (:147-160)
+        const long long hi = lo + size[d] - 1;
+        const long long a = lo < 0 ? 0 : lo, b = hi > dim[d] - 1 ? dim[d] - 1 : hi;
+        r.lo[d] = (int)a;
+        r.hi[d] = (int)b;
+        cnt = a > b ? 0u : cnt * (uint32_t)(b / bs[d] - a / bs[d] + 1);
+    }
+    if (cnt == 0) { r.lo[0] = 1; r.hi[0] = 0; }
+    recs[i] = r;
+    counts[i] = cnt;
+}
+
+__global__ __launch_bounds__(256) void k_inject_emit(const InjRec* __restrict__ recs, const uint32_t* __restrict__ counts,
+                                                     const uint32_t* __restrict__ offs, long long n, uint32_t* __restrict__ keys,
+                                                     uint32_t* __restrict__ vals, int nbx, int nby)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || counts[i] == 0) return;
+    const InjRec r = recs[i];
+    uint32_t o = offs[i];
+    for (int bz = r.lo[2] / BZ; bz <= r.hi[2] / BZ; ++bz)
+        for (int by = r.lo[1] / BY; by <= r.hi[1] / BY; ++by)
+            for (int bx = r.lo[0] / BX; bx <= r.hi[0] / BX; ++bx) {
+                keys[o] = (uint32_t)(bx + nbx * (by + nby * bz));
+                vals[o] = (uint32_t)i;
+                ++o;
+            }
+}
+
+// slots past the last pair: a key beyond every brick, so that they sort to the end
+__global__ __launch_bounds__(256) void k_inject_pad(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ offs, long long n,
+                                                    uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, long long slots, uint32_t pad_key)
+{
+    const long long total = n > 0 ? (long long)offs[n - 1] + counts[n - 1] : 0;
+    for (long long i = total + (long long)blockIdx.x * 256 + threadIdx.x; i < slots; i += (long long)gridDim.x * 256) {
+        keys[i] = pad_key;
+        vals[i] = 0u;
+    }
+}
+
+// starts[k] = first sorted pair of brick k (k = 0 .. bricks)
+__global__ __launch_bounds__(256) void k_inject_starts(const uint32_t* __restrict__ keys, long long slots, uint32_t* __restrict__ starts,
+                                                       uint32_t nkeys)
+{
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (k > (long long)nkeys) return;
+    long long lo = 0, hi = slots;
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if ((long long)keys[mid] < k) lo = mid + 1; else hi = mid;
+    }
+    starts[k] = (uint32_t)lo;
+}
+
+// one block per brick: image and weight of its voxels continue from what they hold, step after step in list order
+__global__ __launch_bounds__(256) void k_inject_render(const InjRec* __restrict__ recs, const uint32_t* __restrict__ vals,
+                                                       const uint32_t* __restrict__ starts, float* __restrict__ image, float* __restrict__ weight,
+                                                       int nx, int ny, int nz, int nbx, int nby, double t0, double t1, double t2)
+{
+    __shared__ double s_tab[CH][NTAB];
+    __shared__ double s_loc[CH][3], s_int[CH];
+    __shared__ int s_lo[CH][3], s_hi[CH][3];
+
+    const uint32_t brick = blockIdx.x;
+    const uint32_t s = starts[brick], e = starts[brick + 1];
+    if (s == e) return;                                 // nothing lands here: the voxels stay as they are
+    const int bx0 = (int)(brick % (uint32_t)nbx) * BX;
+    const int by0 = (int)((brick / (uint32_t)nbx) % (uint32_t)nby) * BY;
+    const int bz0 = (int)(brick / ((uint32_t)nbx * (uint32_t)nby)) * BZ;
+    const int tid = threadIdx.x;
+    const int xl = tid & 31, yl = tid >> 5;
+    const int x = bx0 + xl, y = by0 + yl;
+    const bool inxy = x < nx && y < ny;
+    const long long row = (long long)nx * ny;
+    const long long base = inxy ? (long long)x + (long long)nx * y : 0;
+
+    float acc_i[BZ], acc_w[BZ];
+#pragma unroll
+    for (int k = 0; k < BZ; ++k) {
+        const int z = bz0 + k;
+        const bool in = inxy && z < nz;
+        acc_i[k] = in ? image[base + row * z] : 0.0f;
+        acc_w[k] = in ? weight[base + row * z] : 0.0f;
+    }
+    const double tss[3] = {t0, t1, t2};
+    for (uint32_t c0 = s; c0 < e; c0 += CH) {
+        const int m = (int)min((uint32_t)CH, e - c0);
+        __syncthreads();                                // the previous chunk's tables have been read
+        if (tid < m) {
+            const InjRec r = recs[vals[c0 + tid]];
+            for (int d = 0; d < 3; ++d) { s_loc[tid][d] = r.loc[d]; s_lo[tid][d] = r.lo[d]; s_hi[tid][d] = r.hi[d]; }
+            s_int[tid] = r.inten;
+        }
+        __syncthreads();
+        for (int t = tid; t < m * NTAB; t += 256) {
+            const int c = t / NTAB, i = t - c * NTAB;
+            const int d = i < BX ? 0 : (i < BX + BY ? 1 : 2);
+            const int pos = d == 0 ? bx0 + i : (d == 1 ? by0 + i - BX : bz0 + i - BX - BY);
+            double v = 0.0;
+            if (pos >= s_lo[c][d] && pos <= s_hi[c][d]) {
+                const double xd = s_loc[c][d] - (double)pos;
+                v = exp(-(xd * xd) / tss[d]);           // getGaussValue (:162-166)
+            }
+            s_tab[c][i] = v;
+        }
+        __syncthreads();
+        for (int c = 0; c < m; ++c) {
+            if (x < s_lo[c][0] || x > s_hi[c][0] || y < s_lo[c][1] || y > s_hi[c][1]) continue;
+            const int zl = s_lo[c][2] - bz0, zh = s_hi[c][2] - bz0;
+            const double exy = (1 * s_tab[c][xl]) * s_tab[c][BX + yl];
+            const double inten = s_int[c];
+#pragma unroll
+            for (int k = 0; k < BZ; ++k)
+                if (k >= zl && k <= zh) {
+                    const double value = exy * s_tab[c][BX + BY + k];
+                    acc_i[k] = acc_i[k] + (float)(value * inten);        // :194
+                    acc_w[k] = acc_w[k] + (float)value;                  // :195
+                }
+        }
+    }
+    if (!inxy) return;
+#pragma unroll
+    for (int k = 0; k < BZ; ++k) {
+        const int z = bz0 + k;
+        if (z >= nz) break;
+        image[base + row * z] = acc_i[k];
+        weight[base + row * z] = acc_w[k];
+    }
+}
+
+// device buffers that live for one call
+struct Scratch {
+    DevBuf b[12];
+    ~Scratch() { for (DevBuf& x : b) x.release(); }
+};
+
+int64_t bricks_spanned(int64_t len, int b, int64_t nbricks)
+{
+    const int64_t k = (len + b - 2) / b + 1;
+    return k < nbricks ? k : nbricks;
+}
+
+}  // namespace
+
+// VolumeInjection's constructor (:56-72) for sigma > 0, with Util.getSuggestedKernelDiameter (ImgLib2, recalled)
+void aberr_inject_geometry(const double sigma[3], int size[3], double tss[3])
+{
+    for (int d = 0; d < 3; ++d) {
+        const int s = 2 * (int)(3 * sigma[d] + 0.5) + 1;
+        size[d] = s > 3 ? s : 3;
+        tss[d] = 2 * sigma[d] * sigma[d];
+    }
+}
+
+uint64_t aberr_random_jump(uint64_t state, uint64_t steps) { return jr_jump(state & JR_MASK, steps); }
+
+// xyz (3 doubles per step) with either inten (doubles) or val (floats), all on the device; sumw != 0 divides every intensity by it
+int aberr_inject_dev(mvsim_ctx* ctx, float* image, float* weight, const int64_t dim[3], const double sigma[3], const double* xyz,
+                     const double* inten, const float* val, int64_t n, double sumw)
+{
+    if (n == 0) return MVSIM_OK;
+    int size[3];
+    double tss[3];
+    aberr_inject_geometry(sigma, size, tss);
+    const int nbx = (int)((dim[0] + BX - 1) / BX), nby = (int)((dim[1] + BY - 1) / BY), nbz = (int)((dim[2] + BZ - 1) / BZ);
+    const uint64_t nb = (uint64_t)nbx * nby * nbz;
+    if (nb >= ((uint64_t)1 << 31)) {
+        set_error("invalid argument: volume injection: image of %llu bricks", (unsigned long long)nb);
+        return MVSIM_EINVAL;
+    }
+    const int bs[3] = {BX, BY, BZ};
+    const int64_t nbd[3] = {nbx, nby, nbz};
+    int64_t per_item = 1;
+    for (int d = 0; d < 3; ++d) per_item *= bricks_spanned(std::min<int64_t>(size[d], dim[d]), bs[d], nbd[d]);
+    const int64_t cap = ctx->opt.beads_pair_cap;
+    const int64_t per_range = std::max<int64_t>(1, std::min<int64_t>(cap / per_item, ((int64_t)1 << 31) / per_item - 1));
+    const int64_t max_items = std::min(n, per_range), max_slots = max_items * per_item + 1;
+
+    Scratch ws;
+    size_t scan_tmp = 0, sort_tmp = 0;
+    MVSIM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)max_items, ctx->stream));
+    MVSIM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr,
+                                                 (uint32_t*)nullptr, (int)max_slots, 0, 32, ctx->stream));
+    MVSIM_TRY(ws.b[0].reserve((size_t)max_items * sizeof(InjRec)));
+    MVSIM_TRY(ws.b[1].reserve((size_t)(2 * max_items + (int64_t)nb + 1) * sizeof(uint32_t)));
+    MVSIM_TRY(ws.b[2].reserve((size_t)(2 * max_slots) * sizeof(uint32_t)));
+    MVSIM_TRY(ws.b[3].reserve((size_t)(2 * max_slots) * sizeof(uint32_t)));
+    MVSIM_TRY(ws.b[4].reserve(std::max<size_t>(16, std::max(scan_tmp, sort_tmp))));
+    InjRec* recs = ws.b[0].as<InjRec>();
+    uint32_t* counts = ws.b[1].as<uint32_t>();
+    uint32_t* offs = counts + max_items;
+    uint32_t* starts = offs + max_items;
+    uint32_t* keys = ws.b[2].as<uint32_t>();
+    uint32_t* vals = ws.b[3].as<uint32_t>();
+    int end_bit = 1;
+    while (end_bit < 32 && (nb >> end_bit) != 0) ++end_bit;
+
+    for (int64_t first = 0; first < n; first += per_range) {
+        const int64_t cnt = std::min(per_range, n - first), slots = cnt * per_item + 1;
+        const unsigned blocks = (unsigned)((cnt + 255) / 256);
+        hipLaunchKernelGGL(k_inject_cull, dim3(blocks), dim3(256), 0, ctx->stream, xyz + 3 * first, inten ? inten + first : nullptr,
+                           val ? val + first : nullptr, sumw, (long long)cnt, recs, counts, (int)dim[0], (int)dim[1], (int)dim[2], size[0],
+                           size[1], size[2]);
+        MVSIM_HIP(hipGetLastError());
+        size_t t = ws.b[4].bytes;
+        MVSIM_HIP(hipcub::DeviceScan::ExclusiveSum(ws.b[4].p, t, counts, offs, (int)cnt, ctx->stream));
+        hipLaunchKernelGGL(k_inject_emit, dim3(blocks), dim3(256), 0, ctx->stream, recs, counts, offs, (long long)cnt, keys, vals, nbx, nby);
+        MVSIM_HIP(hipGetLastError());
+        const long long pad_blocks = std::min<long long>(4096, (slots + 255) / 256);
+        hipLaunchKernelGGL(k_inject_pad, dim3((unsigned)pad_blocks), dim3(256), 0, ctx->stream, counts, offs, (long long)cnt, keys, vals,
+                           (long long)slots, (uint32_t)nb);
+        MVSIM_HIP(hipGetLastError());
+        t = ws.b[4].bytes;
+        MVSIM_HIP(hipcub::DeviceRadixSort::SortPairs(ws.b[4].p, t, keys, keys + max_slots, vals, vals + max_slots, (int)slots, 0, end_bit,
+                                                     ctx->stream));
+        hipLaunchKernelGGL(k_inject_starts, dim3((unsigned)((nb + 1 + 255) / 256)), dim3(256), 0, ctx->stream, keys + max_slots,
+                           (long long)slots, starts, (uint32_t)nb);
+        MVSIM_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_inject_render, dim3((unsigned)nb), dim3(256), 0, ctx->stream, recs, vals + max_slots, starts, image, weight,
+                           (int)dim[0], (int)dim[1], (int)dim[2], nbx, nby, tss[0], tss[1], tss[2]);
+        MVSIM_HIP(hipGetLastError());
+    }
+    MVSIM_HIP(hipStreamSynchronize(ctx->stream));          // the workspaces go away with this call
+    return MVSIM_OK;
+}
+
+// refract3d on device volumes; image and weight are ADDED to (the caller zeroes them for the reference's result).  steps: host buffers
+// or null.  Rays run in ranges whose step records and pairs fit the option "beads_pair_cap".
+int aberr_refract3d_dev(mvsim_ctx* ctx, const float* img, const float* ri_img, const int64_t dim[3], int illum, int z, const double abc[3],
+                        double ri, int64_t num_rays, uint64_t state, float* image, float* weight, double sumw, mvsim_ray_steps* steps)
+{
+    const double sigma[3] = {0.5, 0.5, 0.5};                                                       // :280
+    const int max_moves = (int)dim[2];                                                            // :304
+    const int64_t cap_steps = std::max<int64_t>(max_moves, std::min<int64_t>(ctx->opt.beads_pair_cap / 8, (int64_t)1 << 25));
+    const int64_t rays_per_range = std::max<int64_t>(1, cap_steps / max_moves);
+    const int64_t max_rays = std::min(std::max<int64_t>(num_rays, 1), rays_per_range), max_slots = max_rays * max_moves;
+    if (steps) steps->n = 0;
+
+    Scratch ws;
+    size_t scan_tmp = 0;
+    MVSIM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, (int*)nullptr, (int*)nullptr, (int)max_rays, ctx->stream));
+    MVSIM_TRY(ws.b[0].reserve((size_t)max_slots * 3 * sizeof(double)));
+    MVSIM_TRY(ws.b[1].reserve((size_t)max_slots * sizeof(float)));
+    MVSIM_TRY(ws.b[2].reserve((size_t)max_rays * 2 * sizeof(int)));
+    MVSIM_TRY(ws.b[3].reserve((size_t)max_slots * 3 * sizeof(double)));
+    MVSIM_TRY(ws.b[4].reserve((size_t)max_slots * sizeof(float)));
+    MVSIM_TRY(ws.b[5].reserve(std::max<size_t>(16, scan_tmp)));
+    double* slot_xyz = ws.b[0].as<double>();
+    float* slot_val = ws.b[1].as<float>();
+    int* moves = ws.b[2].as<int>();
+    int* offs = moves + max_rays;
+    double* xyz = ws.b[3].as<double>();
+    float* val = ws.b[4].as<float>();
+    SheetParams sp{state & JR_MASK, abc[0], abc[1], abc[2], illum ? 1 : 0, z};
+
+    for (int64_t r0 = 0; r0 < num_rays; r0 += rays_per_range) {
+        const int nr = (int)std::min(rays_per_range, num_rays - r0);
+        hipLaunchKernelGGL(k_refract3d_trace, dim3((unsigned)((nr + 63) / 64)), dim3(64), 0, ctx->stream, img, ri_img, (int)dim[0], (int)dim[1],
+                           (int)dim[2], sp, ri, (long long)r0, nr, max_moves, slot_xyz, slot_val, moves);
+        MVSIM_HIP(hipGetLastError());
+        size_t t = ws.b[5].bytes;
+        MVSIM_HIP(hipcub::DeviceScan::ExclusiveSum(ws.b[5].p, t, moves, offs, nr, ctx->stream));
+        hipLaunchKernelGGL(k_compact_steps, dim3((unsigned)(((long long)nr * max_moves + 255) / 256)), dim3(256), 0, ctx->stream, slot_xyz,
+                           slot_val, moves, offs, nr, max_moves, xyz, val);
+        MVSIM_HIP(hipGetLastError());
+        int last[2];
+        MVSIM_HIP(hipMemcpyAsync(&last[0], moves + nr - 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        MVSIM_HIP(hipMemcpyAsync(&last[1], offs + nr - 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        MVSIM_HIP(hipStreamSynchronize(ctx->stream));
+        const int64_t nsteps = (int64_t)last[0] + last[1];
+        if (steps) {
+            if (steps->n + nsteps > steps->capacity) {
+                set_error("invalid argument: refract3d: the step list needs more than its capacity of %lld steps", (long long)steps->capacity);
+                return MVSIM_EINVAL;
+            }
+            if (steps->xyz) MVSIM_HIP(hipMemcpyAsync(steps->xyz + 3 * steps->n, xyz, (size_t)nsteps * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            if (steps->value) MVSIM_HIP(hipMemcpyAsync(steps->value + steps->n, val, (size_t)nsteps * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+            if (steps->moves) MVSIM_HIP(hipMemcpyAsync(steps->moves + r0, moves, (size_t)nr * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            steps->n += nsteps;
+        }
+        if (image && weight) MVSIM_TRY(aberr_inject_dev(ctx, image, weight, dim, sigma, xyz, nullptr, val, nsteps, sumw));
+        MVSIM_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return MVSIM_OK;
+}
+
+int aberr_project_to_camera_dev(mvsim_ctx* ctx, const float* ri_img, const float* refr, const int64_t dim[3], int current_z,
+                                int rays_per_pixel, uint64_t state, float* proj)
+{
+    const size_t lds = (size_t)rays_per_pixel * sizeof(double);
+    hipLaunchKernelGGL(k_project_to_camera, dim3((unsigned)(dim[0] * dim[1])), dim3(256), lds, ctx->stream, ri_img, refr, (int)dim[0],
+                       (int)dim[1], (int)dim[2], current_z, rays_per_pixel, (unsigned long long)(state & JR_MASK), proj);
+    MVSIM_HIP(hipGetLastError());
+    return MVSIM_OK;
+}
+
+// camera = 0: refract3d's starts (pos3 and dir3); 1: projectToCamera's (pos3; dir3 may be null).  Host outputs.
+int aberr_ray_starts(mvsim_ctx* ctx, uint64_t state, const int64_t dim[3], int camera, int illum, int z, const double abc[3],
+                     int rays_per_pixel, int64_t n, double* pos3, double* dir3)
+{
+    if (n == 0) return MVSIM_OK;
+    Scratch ws;
+    MVSIM_TRY(ws.b[0].reserve((size_t)n * 3 * sizeof(double)));
+    if (dir3) MVSIM_TRY(ws.b[1].reserve((size_t)n * 3 * sizeof(double)));
+    SheetParams sp{state & JR_MASK, abc ? abc[0] : 0.0, abc ? abc[1] : 0.0, abc ? abc[2] : 0.0, illum ? 1 : 0, z};
+    hipLaunchKernelGGL(k_ray_starts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, sp, camera, rays_per_pixel, (int)dim[0],
+                       (int)dim[1], (long long)n, ws.b[0].as<double>(), dir3 ? ws.b[1].as<double>() : nullptr);
+    MVSIM_HIP(hipGetLastError());
+    MVSIM_HIP(hipMemcpyAsync(pos3, ws.b[0].p, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (dir3) MVSIM_HIP(hipMemcpyAsync(dir3, ws.b[1].p, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    MVSIM_HIP(hipStreamSynchronize(ctx->stream));
+    return MVSIM_OK;
+}
+
+// img on the device; positions and results on the host
+int aberr_hessian_at_dev(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const double* xyz, int64_t n, double* matrix9, double* eigvec3,
+                         double* eigval)
+{
+    if (n == 0) return MVSIM_OK;
+    Scratch ws;
+    MVSIM_TRY(ws.b[0].reserve((size_t)n * 3 * sizeof(double)));
+    MVSIM_TRY(ws.b[1].reserve((size_t)n * 13 * sizeof(double)));
+    double* out = ws.b[1].as<double>();
+    MVSIM_HIP(hipMemcpyAsync(ws.b[0].p, xyz, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_hessian_at, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, img, (int)dim[0], (int)dim[1], (int)dim[2],
+                       ws.b[0].as<double>(), (long long)n, out, out + 9 * n, out + 12 * n);
+    MVSIM_HIP(hipGetLastError());
+    if (matrix9) MVSIM_HIP(hipMemcpyAsync(matrix9, out, (size_t)n * 9 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (eigvec3) MVSIM_HIP(hipMemcpyAsync(eigvec3, out + 9 * n, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (eigval) MVSIM_HIP(hipMemcpyAsync(eigval, out + 12 * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    MVSIM_HIP(hipStreamSynchronize(ctx->stream));
+    return MVSIM_OK;
+}
+
+int aberr_hessian_images_dev(mvsim_ctx* ctx, const float* img, const int64_t dim[3], float* eigval, float* eigvec)
+{
+    const int64_t n = dim[0] * dim[1] * dim[2];
+    hipLaunchKernelGGL(k_hessian_images, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, img, (int)dim[0], (int)dim[1], (int)dim[2],
+                       eigval, eigvec);
+    MVSIM_HIP(hipGetLastError());
+    return MVSIM_OK;
+}
+
+int aberr_normalize_dev(mvsim_ctx* ctx, const float* image, const float* weight, int64_t n, float* out)
+{
+    hipLaunchKernelGGL(k_volume_normalize, dim3((unsigned)std::min<int64_t>(8192, (n + 255) / 256)), dim3(256), 0, ctx->stream, image, weight,
+                       (long long)n, out);
+    MVSIM_HIP(hipGetLastError());
+    return MVSIM_OK;
+}
+
+int aberr_project_dev(mvsim_ctx* ctx, const float* image, const float* weight, const int64_t dim[3], float* proj)
+{
+    hipLaunchKernelGGL(k_volume_project, dim3((unsigned)((dim[0] * dim[1] + 255) / 256)), dim3(256), 0, ctx->stream, image, weight,
+                       (int)dim[0], (int)dim[1], (int)dim[2], proj);
+    MVSIM_HIP(hipGetLastError());
+    return MVSIM_OK;
+}
+
+}  // namespace mvsim

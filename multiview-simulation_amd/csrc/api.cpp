@@ -1971,6 +1971,325 @@ int mvsim_beads_normalize(mvsim_ctx* ctx, float* img, int64_t n)
     return down(ctx, img, ctx->vol_a.p, bytes);
 }
 
+// ---- the refraction simulator: SimulateMultiViewAberrations (aberrations.hip) ---------------------------------------------
+int mvsim_lightsheet_fit(double center, double thickness_center, double length, double thickness_edges, double abc[3])
+{
+    MVSIM_CHECK_ARG(abc != nullptr, "null pointer");
+    MVSIM_CHECK_ARG(std::isfinite(center) && std::isfinite(thickness_center) && std::isfinite(length) && std::isfinite(thickness_edges),
+                    "light sheet: non-finite argument");
+    const double px[3] = {center, center - length / 2, center + length / 2};                    // Lightsheet.java:47-50
+    const double py[3] = {thickness_center, thickness_edges, thickness_edges};
+    double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, t[3] = {0, 0, 0};
+    for (int k = 0; k < 3; ++k) {                                                                 // :90-113
+        const double x = px[k], y = py[k], xx = x * x, xxx = xx * x;
+        m[0] += xx * xx; m[1] += xxx; m[2] += xx;
+        m[3] += xxx; m[4] += xx; m[5] += x;
+        m[6] += xx; m[7] += x; m[8] += 1;
+        t[0] += xx * y; t[1] += x * y; t[2] += y;
+    }
+    const double det = m[0] * m[4] * m[8] + m[3] * m[7] * m[2] + m[6] * m[1] * m[5] - m[2] * m[4] * m[6] - m[5] * m[7] * m[0] -
+                       m[8] * m[1] * m[3];                                                        // :131-142
+    abc[0] = abc[1] = abc[2] = 0;
+    MVSIM_CHECK_ARG(det != 0 && std::isfinite(det), "light sheet: cannot invert the matrix of the fit");
+    const double inv[9] = {(m[4] * m[8] - m[5] * m[7]) / det, (m[2] * m[7] - m[1] * m[8]) / det, (m[1] * m[5] - m[2] * m[4]) / det,
+                           (m[5] * m[6] - m[3] * m[8]) / det, (m[0] * m[8] - m[2] * m[6]) / det, (m[2] * m[3] - m[0] * m[5]) / det,
+                           (m[3] * m[7] - m[4] * m[6]) / det, (m[1] * m[6] - m[0] * m[7]) / det, (m[0] * m[4] - m[1] * m[3]) / det};
+    for (int r = 0; r < 3; ++r) abc[r] = inv[3 * r] * t[0] + inv[3 * r + 1] * t[1] + inv[3 * r + 2] * t[2];   // :126-128
+    return MVSIM_OK;
+}
+
+static int aberr_dim_check(const int64_t dim[3])
+{
+    MVSIM_CHECK_ARG(dim != nullptr, "null dim");
+    for (int d = 0; d < 3; ++d) MVSIM_CHECK_ARG(dim[d] >= 2 && dim[d] <= (1 << 24), "the refraction simulator needs 2 .. 2^24 samples per dimension");
+    MVSIM_CHECK_ARG(dim[0] * dim[1] * dim[2] < ((int64_t)1 << 40), "volume too large");
+    return MVSIM_OK;
+}
+
+static size_t aberr_bytes(const int64_t dim[3]) { return (size_t)(dim[0] * dim[1] * dim[2]) * sizeof(float); }
+
+static int aberr_points_check(const double* xyz, int64_t n, double limit)
+{
+    MVSIM_CHECK_ARG(n >= 0 && (xyz || n == 0), "null point list or negative count");
+    for (int64_t i = 0; i < 3 * n; ++i) MVSIM_CHECK_ARG(std::fabs(xyz[i]) < limit, "position not finite or too far away");   // false for NaN
+    return MVSIM_OK;
+}
+
+int mvsim_hessian_at_dev(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const double* xyz, int64_t n, double* matrix9,
+                         double* eigvec3, double* eigval)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(img != nullptr, "null image");
+    MVSIM_TRY(aberr_points_check(xyz, n, 0x1.0p30));
+    MVSIM_TRY(set_device(ctx));
+    return aberr_hessian_at_dev(ctx, img, dim, xyz, n, matrix9, eigvec3, eigval);
+}
+
+int mvsim_hessian_at(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const double* xyz, int64_t n, double* matrix9, double* eigvec3,
+                     double* eigval)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(img != nullptr, "null image");
+    MVSIM_TRY(aberr_points_check(xyz, n, 0x1.0p30));
+    MVSIM_TRY(set_device(ctx));
+    MVSIM_TRY(up(ctx, ctx->vol_a, img, aberr_bytes(dim)));
+    return aberr_hessian_at_dev(ctx, ctx->vol_a.as<float>(), dim, xyz, n, matrix9, eigvec3, eigval);
+}
+
+int mvsim_hessian_images_dev(mvsim_ctx* ctx, const float* img, const int64_t dim[3], float* eigval, float* eigvec)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(img && eigval && eigvec, "null pointer");
+    MVSIM_TRY(set_device(ctx));
+    return aberr_hessian_images_dev(ctx, img, dim, eigval, eigvec);
+}
+
+int mvsim_hessian_images(mvsim_ctx* ctx, const float* img, const int64_t dim[3], float* eigval, float* eigvec)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(img && eigval && eigvec, "null pointer");
+    MVSIM_TRY(set_device(ctx));
+    const size_t bytes = aberr_bytes(dim);
+    MVSIM_TRY(up(ctx, ctx->vol_a, img, bytes));
+    MVSIM_TRY(ctx->vol_b.reserve(4 * bytes));
+    float* out = ctx->vol_b.as<float>();
+    MVSIM_TRY(aberr_hessian_images_dev(ctx, ctx->vol_a.as<float>(), dim, out, out + bytes / sizeof(float)));
+    MVSIM_HIP(hipMemcpyAsync(eigval, out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return down(ctx, eigvec, out + bytes / sizeof(float), 3 * bytes);
+}
+
+int mvsim_refract3d_ray_starts(mvsim_ctx* ctx, uint64_t* rnd_state, const int64_t dim[3], int illum, int z, const double abc[3], int64_t n,
+                               double* pos3, double* dir3)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(rnd_state && abc && n >= 0 && ((pos3 && dir3) || n == 0), "null pointer or negative count");
+    MVSIM_CHECK_ARG(std::isfinite(abc[0]) && std::isfinite(abc[1]) && std::isfinite(abc[2]), "light sheet: non-finite coefficient");
+    MVSIM_TRY(set_device(ctx));
+    MVSIM_TRY(aberr_ray_starts(ctx, *rnd_state, dim, 0, illum, z, abc, 1, n, pos3, dir3));
+    *rnd_state = aberr_random_jump(*rnd_state, 6 * (uint64_t)n);
+    return MVSIM_OK;
+}
+
+int mvsim_camera_ray_starts(mvsim_ctx* ctx, uint64_t* rnd_state, const int64_t dim[3], int rays_per_pixel, double* pos3)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(rnd_state && pos3, "null pointer");
+    MVSIM_CHECK_ARG(rays_per_pixel >= 1 && rays_per_pixel <= 4096, "rays_per_pixel must be 1 .. 4096");
+    MVSIM_TRY(set_device(ctx));
+    const int64_t n = dim[0] * dim[1] * rays_per_pixel;
+    MVSIM_TRY(aberr_ray_starts(ctx, *rnd_state, dim, 1, 0, 0, nullptr, rays_per_pixel, n, pos3, nullptr));
+    *rnd_state = aberr_random_jump(*rnd_state, 4 * (uint64_t)n);
+    return MVSIM_OK;
+}
+
+// VolumeInjection's constructor (:74-92): the Gaussian of a point at the origin over its box, summed in cursor order (x fastest)
+static double aberr_sum_weights(const double sigma[3], int size[3], int* num_pixels)
+{
+    double tss[3], sum = 0;
+    aberr_inject_geometry(sigma, size, tss);
+    int count = 0;
+    for (int z = -(size[2] / 2); z < -(size[2] / 2) + size[2]; ++z)
+        for (int y = -(size[1] / 2); y < -(size[1] / 2) + size[1]; ++y)
+            for (int x = -(size[0] / 2); x < -(size[0] / 2) + size[0]; ++x) {
+                const double c[3] = {(double)x, (double)y, (double)z};
+                double value = 1;
+                for (int d = 0; d < 3; ++d) {
+                    const double q = 0.0 - c[d];
+                    value *= std::exp(-(q * q) / tss[d]);
+                }
+                sum += value;
+                ++count;
+            }
+    if (num_pixels) *num_pixels = count;
+    return sum;
+}
+
+static int aberr_sigma_check(const double sigma[3])
+{
+    MVSIM_CHECK_ARG(sigma != nullptr, "null sigma");
+    for (int d = 0; d < 3; ++d) MVSIM_CHECK_ARG(std::isfinite(sigma[d]) && sigma[d] > 0.0 && sigma[d] <= 1.0e4, "sigma must be finite, > 0 and <= 1e4");
+    return MVSIM_OK;
+}
+
+int mvsim_volume_inject_info(const double sigma[3], int32_t size[3], double* sum_weights, int32_t* num_pixels)
+{
+    MVSIM_TRY(aberr_sigma_check(sigma));
+    MVSIM_CHECK_ARG(size && sum_weights && num_pixels, "null pointer");
+    int s[3], np = 0;
+    *sum_weights = aberr_sum_weights(sigma, s, &np);
+    for (int d = 0; d < 3; ++d) size[d] = s[d];
+    *num_pixels = np;
+    return MVSIM_OK;
+}
+
+static int aberr_refract3d_check(const int64_t dim[3], double ls_middle, double ls_edge, double ri, int64_t num_rays, const uint64_t* rnd_state,
+                                 const mvsim_ray_steps* steps, double abc[3])
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(rnd_state != nullptr, "null rnd_state");
+    MVSIM_CHECK_ARG(num_rays >= 0, "negative number of rays");
+    MVSIM_CHECK_ARG(std::isfinite(ls_middle) && std::isfinite(ls_edge) && std::isfinite(ri), "refract3d: non-finite argument");
+    MVSIM_CHECK_ARG(!steps || steps->capacity >= 0, "negative step capacity");
+    return mvsim_lightsheet_fit(dim[0] / 2.0, ls_middle, (double)dim[0], ls_edge, abc);        // SMVA:297
+}
+
+int mvsim_refract3d_dev(mvsim_ctx* ctx, const float* img, const float* ri_img, const int64_t dim[3], int illum, int z, double ls_middle,
+                        double ls_edge, double ri, int64_t num_rays, uint64_t* rnd_state, float* image, float* weight, mvsim_ray_steps* steps)
+{
+    double abc[3];
+    MVSIM_TRY(aberr_refract3d_check(dim, ls_middle, ls_edge, ri, num_rays, rnd_state, steps, abc));
+    MVSIM_CHECK_ARG(img && ri_img && ((image != nullptr) == (weight != nullptr)), "null volume (image and weight go together)");
+    MVSIM_TRY(set_device(ctx));
+    const double sigma[3] = {0.5, 0.5, 0.5};
+    int size[3];
+    const double sumw = aberr_sum_weights(sigma, size, nullptr);
+    MVSIM_TRY(aberr_refract3d_dev(ctx, img, ri_img, dim, illum, z, abc, ri, num_rays, *rnd_state, image, weight, sumw, steps));
+    *rnd_state = aberr_random_jump(*rnd_state, 6 * (uint64_t)num_rays);
+    return MVSIM_OK;
+}
+
+int mvsim_refract3d(mvsim_ctx* ctx, const float* img, const float* ri_img, const int64_t dim[3], int illum, int z, double ls_middle,
+                    double ls_edge, double ri, int64_t num_rays, uint64_t* rnd_state, float* image, float* weight, mvsim_ray_steps* steps)
+{
+    double abc[3];
+    MVSIM_TRY(aberr_refract3d_check(dim, ls_middle, ls_edge, ri, num_rays, rnd_state, steps, abc));
+    MVSIM_CHECK_ARG(img && ri_img && ((image != nullptr) == (weight != nullptr)), "null volume (image and weight go together)");
+    MVSIM_TRY(set_device(ctx));
+    const size_t bytes = aberr_bytes(dim);
+    MVSIM_TRY(up(ctx, ctx->vol_a, img, bytes));
+    MVSIM_TRY(up(ctx, ctx->vol_b, ri_img, bytes));
+    float* out = nullptr;
+    if (image) {
+        MVSIM_TRY(ctx->vol_c.reserve(2 * bytes));
+        out = ctx->vol_c.as<float>();
+        MVSIM_HIP(hipMemsetAsync(out, 0, 2 * bytes, ctx->stream));
+    }
+    const double sigma[3] = {0.5, 0.5, 0.5};
+    int size[3];
+    const double sumw = aberr_sum_weights(sigma, size, nullptr);
+    MVSIM_TRY(aberr_refract3d_dev(ctx, ctx->vol_a.as<float>(), ctx->vol_b.as<float>(), dim, illum, z, abc, ri, num_rays, *rnd_state, out,
+                                  out ? out + bytes / sizeof(float) : nullptr, sumw, steps));
+    *rnd_state = aberr_random_jump(*rnd_state, 6 * (uint64_t)num_rays);
+    if (!image) return MVSIM_OK;
+    MVSIM_HIP(hipMemcpyAsync(image, out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return down(ctx, weight, out + bytes / sizeof(float), bytes);
+}
+
+static int aberr_inject_check(const int64_t dim[3], const double sigma[3], const double* xyz, const double* intensity, int64_t n)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_TRY(aberr_sigma_check(sigma));
+    MVSIM_TRY(aberr_points_check(xyz, n, INFINITY));
+    MVSIM_CHECK_ARG(intensity || n == 0, "null intensity list");
+    for (int64_t i = 0; i < n; ++i) MVSIM_CHECK_ARG(std::isfinite(intensity[i]), "intensity not finite");
+    return MVSIM_OK;
+}
+
+int mvsim_volume_inject_dev(mvsim_ctx* ctx, float* image, float* weight, const int64_t dim[3], const double sigma[3], const double* xyz,
+                            const double* intensity, int64_t n, int normalized)
+{
+    MVSIM_TRY(aberr_inject_check(dim, sigma, xyz, intensity, n));
+    MVSIM_CHECK_ARG(image && weight, "null volume");
+    MVSIM_TRY(set_device(ctx));
+    if (n == 0) return MVSIM_OK;
+    int size[3];
+    const double sumw = normalized ? aberr_sum_weights(sigma, size, nullptr) : 0.0;
+    DevBuf pts;
+    int rc = pts.reserve((size_t)n * 4 * sizeof(double));
+    if (rc == MVSIM_OK) {
+        double* d = pts.as<double>();
+        hipError_t e = hipMemcpyAsync(d, xyz, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + 3 * n, intensity, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) { set_error("hipMemcpyAsync failed: %s", hipGetErrorString(e)); rc = MVSIM_EHIP; }
+        else rc = aberr_inject_dev(ctx, image, weight, dim, sigma, d, d + 3 * n, nullptr, n, sumw);
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    pts.release();
+    return rc;
+}
+
+int mvsim_volume_inject(mvsim_ctx* ctx, float* image, float* weight, const int64_t dim[3], const double sigma[3], const double* xyz,
+                        const double* intensity, int64_t n, int normalized)
+{
+    MVSIM_TRY(aberr_inject_check(dim, sigma, xyz, intensity, n));
+    MVSIM_CHECK_ARG(image && weight, "null volume");
+    MVSIM_TRY(set_device(ctx));
+    const size_t bytes = aberr_bytes(dim);
+    MVSIM_TRY(up(ctx, ctx->vol_a, image, bytes));
+    MVSIM_TRY(up(ctx, ctx->vol_b, weight, bytes));
+    MVSIM_TRY(mvsim_volume_inject_dev(ctx, ctx->vol_a.as<float>(), ctx->vol_b.as<float>(), dim, sigma, xyz, intensity, n, normalized));
+    MVSIM_HIP(hipMemcpyAsync(image, ctx->vol_a.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return down(ctx, weight, ctx->vol_b.p, bytes);
+}
+
+int mvsim_volume_normalize_dev(mvsim_ctx* ctx, const float* image, const float* weight, int64_t n, float* out)
+{
+    MVSIM_CHECK_ARG(image && weight && out && n >= 1, "null volume or empty count");
+    MVSIM_TRY(set_device(ctx));
+    return aberr_normalize_dev(ctx, image, weight, n, out);
+}
+
+int mvsim_volume_normalize(mvsim_ctx* ctx, const float* image, const float* weight, int64_t n, float* out)
+{
+    MVSIM_CHECK_ARG(image && weight && out && n >= 1, "null volume or empty count");
+    MVSIM_TRY(set_device(ctx));
+    const size_t bytes = (size_t)n * sizeof(float);
+    MVSIM_TRY(up(ctx, ctx->vol_a, image, bytes));
+    MVSIM_TRY(up(ctx, ctx->vol_b, weight, bytes));
+    MVSIM_TRY(ctx->vol_c.reserve(bytes));
+    MVSIM_TRY(aberr_normalize_dev(ctx, ctx->vol_a.as<float>(), ctx->vol_b.as<float>(), n, ctx->vol_c.as<float>()));
+    return down(ctx, out, ctx->vol_c.p, bytes);
+}
+
+int mvsim_volume_project_dev(mvsim_ctx* ctx, const float* image, const float* weight, const int64_t dim[3], float* proj)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(image && weight && proj, "null pointer");
+    MVSIM_TRY(set_device(ctx));
+    return aberr_project_dev(ctx, image, weight, dim, proj);
+}
+
+int mvsim_volume_project(mvsim_ctx* ctx, const float* image, const float* weight, const int64_t dim[3], float* proj)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(image && weight && proj, "null pointer");
+    MVSIM_TRY(set_device(ctx));
+    const size_t bytes = aberr_bytes(dim), pbytes = (size_t)(dim[0] * dim[1]) * sizeof(float);
+    MVSIM_TRY(up(ctx, ctx->vol_a, image, bytes));
+    MVSIM_TRY(up(ctx, ctx->vol_b, weight, bytes));
+    MVSIM_TRY(ctx->vol_c.reserve(pbytes));
+    MVSIM_TRY(aberr_project_dev(ctx, ctx->vol_a.as<float>(), ctx->vol_b.as<float>(), dim, ctx->vol_c.as<float>()));
+    return down(ctx, proj, ctx->vol_c.p, pbytes);
+}
+
+int mvsim_project_to_camera_dev(mvsim_ctx* ctx, const float* ri_img, const float* refr, const int64_t dim[3], int current_z,
+                                int rays_per_pixel, uint64_t* rnd_state, float* proj)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(ri_img && refr && proj && rnd_state, "null pointer");
+    MVSIM_CHECK_ARG(rays_per_pixel >= 1 && rays_per_pixel <= 4096, "rays_per_pixel must be 1 .. 4096");
+    MVSIM_TRY(set_device(ctx));
+    MVSIM_TRY(aberr_project_to_camera_dev(ctx, ri_img, refr, dim, current_z, rays_per_pixel, *rnd_state, proj));
+    *rnd_state = aberr_random_jump(*rnd_state, 4 * (uint64_t)(dim[0] * dim[1]) * (uint64_t)rays_per_pixel);
+    return MVSIM_OK;
+}
+
+int mvsim_project_to_camera(mvsim_ctx* ctx, const float* ri_img, const float* refr, const int64_t dim[3], int current_z, int rays_per_pixel,
+                            uint64_t* rnd_state, float* proj)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(ri_img && refr && proj && rnd_state, "null pointer");
+    MVSIM_CHECK_ARG(rays_per_pixel >= 1 && rays_per_pixel <= 4096, "rays_per_pixel must be 1 .. 4096");
+    MVSIM_TRY(set_device(ctx));
+    const size_t bytes = aberr_bytes(dim), pbytes = (size_t)(dim[0] * dim[1]) * sizeof(float);
+    MVSIM_TRY(up(ctx, ctx->vol_a, ri_img, bytes));
+    MVSIM_TRY(up(ctx, ctx->vol_b, refr, bytes));
+    MVSIM_TRY(ctx->vol_c.reserve(pbytes));
+    MVSIM_TRY(mvsim_project_to_camera_dev(ctx, ctx->vol_a.as<float>(), ctx->vol_b.as<float>(), dim, current_z, rays_per_pixel, rnd_state,
+                                          ctx->vol_c.as<float>()));
+    return down(ctx, proj, ctx->vol_c.p, pbytes);
+}
+
 // the slot's view has landed (ev_d2h synchronised): 16-bit counts become the caller's float32 acquisition -- or, when the device
 // flagged a value that does not fit (or is no integer), the float32 buffer is fetched after all
 static int async_land(mvsim_ctx* ctx, int s)

@@ -170,7 +170,7 @@ struct Options {
                                        // the pieces that have arrived among themselves (mvsim_comm_broadcast_plan; comm.cpp: bcast_pipelined)
     int64_t fft_pad[3] = {0, 0, 0};    // explicit padded sizes on the rocFFT path (0: choose)
     bool    skip_empty = true;         // convolution passes skip planes the fused rotate kernel found empty (exact; option for A/B runs)
-    int64_t beads_pair_cap = (int64_t)1 << 28;   // bead renderer: (brick, bead) pairs one chunk may bin; larger calls run in chunks (beads.hip)
+    int64_t beads_pair_cap = (int64_t)1 << 28;   // bead renderer and volume injection: (brick, item) pairs one chunk may bin; larger calls run in chunks (beads.hip, aberrations.hip)
 };
 // How launch_extract samples.  share 0: one launch, no work queue.  1..16: work queue whose per-block segments hold that many sixteenths
 // of the block's voxels.  QUEUE_SHARE_AUTO + L (L = 0..16): the library's choice -- every voxel for queues of up to 64 MiB, else
@@ -376,6 +376,22 @@ int render_beads_dev(mvsim_ctx* ctx, const double* xyz, const int64_t* view_offs
                      const int64_t dim[3], const int64_t imin[3], const double sigma[3], float* const* out_f32, uint16_t* const* out_u16);
 int beads_normalize_dev(mvsim_ctx* ctx, float* img, int64_t n);
 void beads_release(mvsim_ctx* ctx);
+// the refraction simulator (aberrations.hip); arguments validated by the caller (api.cpp), volumes on the device
+void aberr_inject_geometry(const double sigma[3], int size[3], double tss[3]);
+uint64_t aberr_random_jump(uint64_t state, uint64_t steps);
+int aberr_inject_dev(mvsim_ctx* ctx, float* image, float* weight, const int64_t dim[3], const double sigma[3], const double* xyz,
+                     const double* inten, const float* val, int64_t n, double sumw);
+int aberr_refract3d_dev(mvsim_ctx* ctx, const float* img, const float* ri_img, const int64_t dim[3], int illum, int z, const double abc[3],
+                        double ri, int64_t num_rays, uint64_t state, float* image, float* weight, double sumw, mvsim_ray_steps* steps);
+int aberr_project_to_camera_dev(mvsim_ctx* ctx, const float* ri_img, const float* refr, const int64_t dim[3], int current_z,
+                                int rays_per_pixel, uint64_t state, float* proj);
+int aberr_ray_starts(mvsim_ctx* ctx, uint64_t state, const int64_t dim[3], int camera, int illum, int z, const double abc[3],
+                     int rays_per_pixel, int64_t n, double* pos3, double* dir3);
+int aberr_hessian_at_dev(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const double* xyz, int64_t n, double* matrix9,
+                         double* eigvec3, double* eigval);
+int aberr_hessian_images_dev(mvsim_ctx* ctx, const float* img, const int64_t dim[3], float* eigval, float* eigvec);
+int aberr_normalize_dev(mvsim_ctx* ctx, const float* image, const float* weight, int64_t n, float* out);
+int aberr_project_dev(mvsim_ctx* ctx, const float* image, const float* weight, const int64_t dim[3], float* proj);
 int launch_weight_image(hipStream_t s, float* out, const int64_t dim[3]);
 int launch_weights(hipStream_t s, float* const* views, int nv, int64_t n, const float* sum_in, float* sum_out,
                    float osem, bool sum_only);

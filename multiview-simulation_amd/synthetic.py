@@ -88,6 +88,25 @@ def measured_like_psf(k: int = 51) -> np.ndarray:
     return np.ascontiguousarray(g, dtype=np.float32)
 
 
+def smooth_blobs(nx: int, ny: int | None = None, nz: int | None = None, seed: int = 1, count: int = 14, sigma=(0.08, 0.14),
+                 lo: float = 0.0, hi: float = 1.0) -> np.ndarray:
+    """A smooth field in [lo, hi], shape (Nz, Ny, Nx): `count` Gaussian blobs of random weight, centres uniform in the volume, widths
+    uniform in `sigma` (fractions of the smallest dimension), range-normalised.  The image / refractive-index pairs of the refraction
+    simulator's example and benchmark (the reference's `block4.tif` is not shipped): with the default widths the index field's
+    curvature is well above the tracer's |eigenvalue| > 0.01 threshold, so rays do refract."""
+    ny = ny or nx
+    nz = nz or nx
+    rng = np.random.default_rng(seed)
+    f = np.zeros((nz, ny, nx), dtype=np.float64)
+    for _ in range(count):
+        c = rng.random(3) * np.array([nz, ny, nx])
+        s = (sigma[0] + rng.random() * (sigma[1] - sigma[0])) * min(nx, ny, nz)
+        g = [np.exp(-((np.arange(n) - c[d]) ** 2) / (2 * s * s)) for d, n in enumerate((nz, ny, nx))]
+        f += rng.random() * g[0][:, None, None] * g[1][None, :, None] * g[2][None, None, :]
+    f = (f - f.min()) / (f.max() - f.min())
+    return np.ascontiguousarray(lo + (hi - lo) * f, dtype=np.float32)
+
+
 def view_angles(n_views: int, offset: int = 15) -> list[int]:
     """angleOffset + k * (360 / n_views) (SimulateMultiViewDataset.java:540-548,567-570)."""
     step = 360 // n_views
