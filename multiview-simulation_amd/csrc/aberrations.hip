@@ -21,6 +21,7 @@
 //   camera     one block per camera pixel, lanes over the pixel's rays; the per-ray fp64 signals go to LDS and ONE lane adds them in
 //              ray order (avgValue, :242).
 #include "common.h"
+#include "jrandom.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -31,34 +32,6 @@
 namespace mvsim {
 
 namespace {
-
-// ---- java.util.Random, jumped ahead -----------------------------------------------------------------------------------------
-constexpr unsigned long long JR_MASK = (1ULL << 48) - 1, JR_A = 0x5DEECE66DULL, JR_C = 0xBULL;
-
-// the state after k steps from s: s * a^k + c (a^(k-1) + ... + 1)  (mod 2^48), composing the affine map with itself by squaring
-__host__ __device__ inline unsigned long long jr_jump(unsigned long long s, unsigned long long k)
-{
-    unsigned long long A = 1, C = 0, a = JR_A, c = JR_C;
-    while (k) {
-        if (k & 1) { A = (A * a) & JR_MASK; C = (C * a + c) & JR_MASK; }
-        c = ((a + 1) * c) & JR_MASK;
-        a = (a * a) & JR_MASK;
-        k >>= 1;
-    }
-    return (s * A + C) & JR_MASK;
-}
-
-__device__ __forceinline__ int jr_next(unsigned long long& s, int bits)
-{
-    s = (s * JR_A + JR_C) & JR_MASK;
-    return (int)((long long)s >> (48 - bits));
-}
-
-__device__ __forceinline__ double jr_double(unsigned long long& s)
-{
-    const long long hi = (long long)jr_next(s, 26) << 27;
-    return (double)(hi + jr_next(s, 27)) * 0x1.0p-53;
-}
 
 // ---- the interpolating accessor (ImgLib2 NLinearInterpolator over Views.extendMirrorSingle) ---------------------------------
 __device__ __forceinline__ int mirror_single(int i, int n)
@@ -407,12 +380,12 @@ struct SheetParams {
 // refract3d :309-319: ray i consumes draws 3i .. 3i + 2 of nextDouble(), two generator steps each
 __device__ __forceinline__ void sheet_ray_start(const SheetParams& sp, long long ray, int nx, int ny, double pos[3], double vec[3])
 {
-    unsigned long long s = jr_jump(sp.state, 6ULL * (unsigned long long)ray);
-    pos[0] = jr_double(s) * (double)(nx - 1);
+    JRandom rnd{jr_jump(sp.state, 6ULL * (unsigned long long)ray)};
+    pos[0] = rnd.next_double() * (double)(nx - 1);
     pos[1] = sp.illum ? (double)(ny - 1) : 0.0;
     const double th = sp.a * pos[0] * pos[0] + sp.b * pos[0] + sp.c;
-    pos[2] = (double)sp.z + (jr_double(s) * th) - th / 2.0;
-    vec[0] = (jr_double(s) - 0.5) / 5;
+    pos[2] = (double)sp.z + (rnd.next_double() * th) - th / 2.0;
+    vec[0] = (rnd.next_double() - 0.5) / 5;
     vec[1] = sp.illum ? -1.0 : 1.0;
     vec[2] = 0.0;
     norm3(vec);
@@ -421,9 +394,9 @@ __device__ __forceinline__ void sheet_ray_start(const SheetParams& sp, long long
 // projectToCamera :137-143: ray (pixel p, i) consumes draws 2 (rays p + i) ..; start z = 1, direction +z
 __device__ __forceinline__ void camera_ray_start(unsigned long long state, long long ray, int px, int py, double pos[3], double vec[3])
 {
-    unsigned long long s = jr_jump(state, 4ULL * (unsigned long long)ray);
-    pos[0] = (double)px + (jr_double(s) - 0.5);
-    pos[1] = (double)py + (jr_double(s) - 0.5);
+    JRandom rnd{jr_jump(state, 4ULL * (unsigned long long)ray)};
+    pos[0] = (double)px + (rnd.next_double() - 0.5);
+    pos[1] = (double)py + (rnd.next_double() - 0.5);
     pos[2] = 1.0;
     vec[0] = 0.0; vec[1] = 0.0; vec[2] = 1.0;
 }
@@ -782,7 +755,6 @@ void aberr_inject_geometry(const double sigma[3], int size[3], double tss[3])
     }
 }
 
-uint64_t aberr_random_jump(uint64_t state, uint64_t steps) { return jr_jump(state & JR_MASK, steps); }
 
 // xyz (3 doubles per step) with either inten (doubles) or val (floats), all on the device; sumw != 0 divides every intensity by it
 int aberr_inject_dev(mvsim_ctx* ctx, float* image, float* weight, const int64_t dim[3], const double sigma[3], const double* xyz,

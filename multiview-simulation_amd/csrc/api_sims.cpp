@@ -1,0 +1,519 @@
+// C ABI of libmvsim, part 4: the simulators around the per-view pipeline -- the sphere phantom (phantom.hip), bead images
+// (SimulateBeads / SimulateBeads2, beads.hip) and the refraction simulator (SimulateMultiViewAberrations, aberrations.hip).
+// Arguments are checked here, before a device is touched; every check is stated once for a host entry point and its _dev twin.
+#include "api_internal.h"
+#include "jrandom.h"
+
+using namespace mvsim;
+
+extern "C" {
+
+static int draw_spheres_args(mvsim_ctx* ctx, const float* img, const int64_t dim[3], int scale, const uint64_t* rnd_state)
+{
+    MVSIM_TRY(set_device(ctx));
+    MVSIM_TRY(check_dim(dim));
+    MVSIM_CHECK_ARG(img && rnd_state, "null pointer");
+    MVSIM_CHECK_ARG(scale >= 1 && scale <= 64, "scale must be in 1..64");
+    return MVSIM_OK;
+}
+
+int mvsim_draw_spheres_dev(mvsim_ctx* ctx, float* img, const int64_t dim[3], double min_value, double max_value,
+                           int scale, int half_pixel_offset, uint64_t* rnd_state, int64_t* n_spheres)
+{
+    MVSIM_TRY(draw_spheres_args(ctx, img, dim, scale, rnd_state));
+    return draw_spheres_dev(ctx, img, dim, min_value, max_value, scale, half_pixel_offset, rnd_state, n_spheres);
+}
+
+int mvsim_downsample2x_dev(mvsim_ctx* ctx, const float* in, const int64_t dim[3], float* out)
+{
+    MVSIM_TRY(set_device(ctx));
+    MVSIM_TRY(check_dim(dim));
+    MVSIM_CHECK_ARG(in && out && in != out, "null or aliased buffer");
+    MVSIM_CHECK_ARG(dim[0] >= 4 && dim[1] >= 4 && dim[2] >= 4, "downSample2x needs at least 4 samples per dimension");
+    return launch_downsample2x(ctx->stream, in, dim, out);
+}
+
+int mvsim_draw_spheres(mvsim_ctx* ctx, float* img, const int64_t dim[3], double min_value, double max_value,
+                       int scale, int half_pixel_offset, uint64_t* rnd_state, int64_t* n_spheres)
+{
+    MVSIM_TRY(draw_spheres_args(ctx, img, dim, scale, rnd_state));
+    const size_t bytes = (size_t)nvox(dim) * sizeof(float);
+    MVSIM_TRY(up(ctx, ctx->vol_a, img, bytes));
+    MVSIM_TRY(draw_spheres_dev(ctx, ctx->vol_a.as<float>(), dim, min_value, max_value, scale, half_pixel_offset, rnd_state, n_spheres));
+    return down(ctx, img, ctx->vol_a.p, bytes);
+}
+
+int mvsim_downsample2x(mvsim_ctx* ctx, const float* in, const int64_t dim[3], float* out)
+{
+    MVSIM_TRY(set_device(ctx));
+    MVSIM_TRY(check_dim(dim));
+    MVSIM_CHECK_ARG(in && out, "null buffer");
+    MVSIM_CHECK_ARG(dim[0] >= 4 && dim[1] >= 4 && dim[2] >= 4, "downSample2x needs at least 4 samples per dimension");
+    const size_t bytes = (size_t)nvox(dim) * sizeof(float);
+    const size_t obytes = (size_t)(dim[0] / 2 - 1) * (size_t)(dim[1] / 2 - 1) * (size_t)(dim[2] / 2 - 1) * sizeof(float);
+    MVSIM_TRY(up(ctx, ctx->vol_a, in, bytes));
+    MVSIM_TRY(ctx->out_buf.reserve(obytes));
+    MVSIM_TRY(mvsim_downsample2x_dev(ctx, ctx->vol_a.as<float>(), dim, ctx->out_buf.as<float>()));
+    return down(ctx, out, ctx->out_buf.p, obytes);
+}
+
+static int splat_spheres_args(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const mvsim_sphere* spheres, int64_t n)
+{
+    MVSIM_TRY(set_device(ctx));
+    MVSIM_TRY(check_dim(dim));
+    MVSIM_CHECK_ARG(img && (spheres || n == 0) && n >= 0, "null pointer or negative count");
+    return MVSIM_OK;
+}
+
+int mvsim_splat_spheres_dev(mvsim_ctx* ctx, float* img, const int64_t dim[3], const mvsim_sphere* spheres, int64_t n)
+{
+    MVSIM_TRY(splat_spheres_args(ctx, img, dim, spheres, n));
+    return splat_spheres_dev(ctx, img, dim, spheres, n);
+}
+
+int mvsim_splat_spheres(mvsim_ctx* ctx, float* img, const int64_t dim[3], const mvsim_sphere* spheres, int64_t n)
+{
+    MVSIM_TRY(splat_spheres_args(ctx, img, dim, spheres, n));
+    const size_t bytes = (size_t)nvox(dim) * sizeof(float);
+    MVSIM_TRY(up(ctx, ctx->vol_a, img, bytes));
+    MVSIM_TRY(splat_spheres_dev(ctx, ctx->vol_a.as<float>(), dim, spheres, n));
+    return down(ctx, img, ctx->vol_a.p, bytes);
+}
+
+// ---- bead images: SimulateBeads / SimulateBeads2 (beads.hip) ----------------------------------------------------------
+int mvsim_beads_random_points(uint64_t* rnd_state, int64_t n, const int64_t min[3], const int64_t max[3], double* xyz)
+{
+    MVSIM_CHECK_ARG(rnd_state && min && max && (xyz || n == 0), "null pointer");
+    MVSIM_CHECK_ARG(n >= 0, "negative number of points");
+    JRandom rnd{*rnd_state & JR_MASK};
+    for (int64_t i = 0; i < n; ++i)
+        for (int d = 0; d < 3; ++d)                                    // SimulateBeads.java:159-160
+            xyz[3 * i + d] = rnd.next_double() * (double)(max[d] - min[d]) + (double)min[d];
+    *rnd_state = rnd.s;
+    return MVSIM_OK;
+}
+
+// the arguments first: their errors need no device
+static int beads_check(mvsim_ctx* ctx, const double* xyz, const int64_t* view_offsets, int64_t n, const double* m12, int nviews, const int64_t min[3],
+                       const int64_t max[3], const double sigma[3], float* const* out_f32, uint16_t* const* out_u16, int64_t dim[3])
+{
+    MVSIM_CHECK_ARG(min && max && sigma, "null interval or sigma");
+    MVSIM_CHECK_ARG(n >= 0 && (xyz || n == 0), "null point list or negative count");
+    MVSIM_CHECK_ARG(nviews >= 1, "renderBeads needs at least one view");
+    MVSIM_CHECK_ARG(out_f32 || out_u16, "renderBeads: no output list");
+    for (int d = 0; d < 3; ++d) {
+        dim[d] = max[d] - min[d];                                      // SimulateBeads.java:105-106: one voxel less than the interval
+        MVSIM_CHECK_ARG(dim[d] >= 1, "image dimension (interval max - min) must be >= 1");
+        MVSIM_CHECK_ARG(std::isfinite(sigma[d]) && sigma[d] > 0.0, "sigma must be finite and > 0");
+        MVSIM_CHECK_ARG(sigma[d] <= 1.0e4, "sigma must be <= 1e4");
+    }
+    MVSIM_CHECK_ARG(dim[0] <= (1 << 24) && dim[1] <= (1 << 24) && dim[2] <= (1 << 24), "image dimension too large");
+    if (view_offsets) {
+        MVSIM_CHECK_ARG(view_offsets[0] >= 0 && view_offsets[nviews] <= n, "view_offsets outside the point list");
+        for (int v = 0; v < nviews; ++v) MVSIM_CHECK_ARG(view_offsets[v] <= view_offsets[v + 1], "view_offsets must not decrease");
+    }
+    if (m12)
+        for (int64_t k = 0; k < 12 * (int64_t)nviews; ++k) MVSIM_CHECK_ARG(std::isfinite(m12[k]), "transform with a non-finite entry");
+    for (int v = 0; v < nviews; ++v)
+        MVSIM_CHECK_ARG((!out_f32 || out_f32[v]) && (!out_u16 || out_u16[v]), "renderBeads: null image in an output list");
+    return set_device(ctx);
+}
+
+int mvsim_render_beads_dev(mvsim_ctx* ctx, const double* xyz, const int64_t* view_offsets, int64_t n, const double* m12, int nviews,
+                           const int64_t min[3], const int64_t max[3], const double sigma[3], float* const* out_f32,
+                           uint16_t* const* out_u16)
+{
+    int64_t dim[3];
+    MVSIM_TRY(beads_check(ctx, xyz, view_offsets, n, m12, nviews, min, max, sigma, out_f32, out_u16, dim));
+    return render_beads_dev(ctx, xyz, view_offsets, n, m12, nviews, dim, min, sigma, out_f32, out_u16);
+}
+
+int mvsim_render_beads(mvsim_ctx* ctx, const double* xyz, const int64_t* view_offsets, int64_t n, const double* m12, int nviews,
+                       const int64_t min[3], const int64_t max[3], const double sigma[3], float* const* out_f32, uint16_t* const* out_u16)
+{
+    int64_t dim[3];
+    MVSIM_TRY(beads_check(ctx, xyz, view_offsets, n, m12, nviews, min, max, sigma, out_f32, out_u16, dim));
+    // device twins of the outputs: every view's float image in vol_a, its uint16 image in vol_b
+    const size_t nv = (size_t)(dim[0] * dim[1] * dim[2]);
+    std::vector<float*> df(nviews, nullptr);
+    std::vector<uint16_t*> du(nviews, nullptr);
+    if (out_f32) {
+        MVSIM_TRY(ctx->vol_a.reserve(nv * sizeof(float) * nviews));
+        for (int v = 0; v < nviews; ++v) df[v] = ctx->vol_a.as<float>() + nv * v;
+    }
+    if (out_u16) {
+        MVSIM_TRY(ctx->vol_b.reserve(nv * sizeof(uint16_t) * nviews));
+        for (int v = 0; v < nviews; ++v) du[v] = reinterpret_cast<uint16_t*>(ctx->vol_b.p) + nv * v;
+    }
+    MVSIM_TRY(render_beads_dev(ctx, xyz, view_offsets, n, m12, nviews, dim, min, sigma, out_f32 ? df.data() : nullptr,
+                               out_u16 ? du.data() : nullptr));
+    for (int v = 0; v < nviews; ++v) {
+        if (out_f32) MVSIM_HIP(hipMemcpyAsync(out_f32[v], df[v], nv * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        if (out_u16) MVSIM_HIP(hipMemcpyAsync(out_u16[v], du[v], nv * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    MVSIM_HIP(hipStreamSynchronize(ctx->stream));
+    return MVSIM_OK;
+}
+
+int mvsim_beads_normalize_dev(mvsim_ctx* ctx, float* img, int64_t n)
+{
+    MVSIM_TRY(set_device(ctx));
+    MVSIM_CHECK_ARG(img && n >= 1, "null image or empty count");
+    return beads_normalize_dev(ctx, img, n);
+}
+
+int mvsim_beads_normalize(mvsim_ctx* ctx, float* img, int64_t n)
+{
+    MVSIM_TRY(set_device(ctx));
+    MVSIM_CHECK_ARG(img && n >= 1, "null image or empty count");
+    const size_t bytes = (size_t)n * sizeof(float);
+    MVSIM_TRY(up(ctx, ctx->vol_a, img, bytes));
+    MVSIM_TRY(beads_normalize_dev(ctx, ctx->vol_a.as<float>(), n));
+    return down(ctx, img, ctx->vol_a.p, bytes);
+}
+
+// ---- the refraction simulator: SimulateMultiViewAberrations (aberrations.hip) ---------------------------------------------
+int mvsim_lightsheet_fit(double center, double thickness_center, double length, double thickness_edges, double abc[3])
+{
+    MVSIM_CHECK_ARG(abc != nullptr, "null pointer");
+    MVSIM_CHECK_ARG(std::isfinite(center) && std::isfinite(thickness_center) && std::isfinite(length) && std::isfinite(thickness_edges),
+                    "light sheet: non-finite argument");
+    const double px[3] = {center, center - length / 2, center + length / 2};                    // Lightsheet.java:47-50
+    const double py[3] = {thickness_center, thickness_edges, thickness_edges};
+    double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, t[3] = {0, 0, 0};
+    for (int k = 0; k < 3; ++k) {                                                                 // :90-113
+        const double x = px[k], y = py[k], xx = x * x, xxx = xx * x;
+        m[0] += xx * xx; m[1] += xxx; m[2] += xx;
+        m[3] += xxx; m[4] += xx; m[5] += x;
+        m[6] += xx; m[7] += x; m[8] += 1;
+        t[0] += xx * y; t[1] += x * y; t[2] += y;
+    }
+    const double det = m[0] * m[4] * m[8] + m[3] * m[7] * m[2] + m[6] * m[1] * m[5] - m[2] * m[4] * m[6] - m[5] * m[7] * m[0] -
+                       m[8] * m[1] * m[3];                                                        // :131-142
+    abc[0] = abc[1] = abc[2] = 0;
+    MVSIM_CHECK_ARG(det != 0 && std::isfinite(det), "light sheet: cannot invert the matrix of the fit");
+    const double inv[9] = {(m[4] * m[8] - m[5] * m[7]) / det, (m[2] * m[7] - m[1] * m[8]) / det, (m[1] * m[5] - m[2] * m[4]) / det,
+                           (m[5] * m[6] - m[3] * m[8]) / det, (m[0] * m[8] - m[2] * m[6]) / det, (m[2] * m[3] - m[0] * m[5]) / det,
+                           (m[3] * m[7] - m[4] * m[6]) / det, (m[1] * m[6] - m[0] * m[7]) / det, (m[0] * m[4] - m[1] * m[3]) / det};
+    for (int r = 0; r < 3; ++r) abc[r] = inv[3 * r] * t[0] + inv[3 * r + 1] * t[1] + inv[3 * r + 2] * t[2];   // :126-128
+    return MVSIM_OK;
+}
+
+static int aberr_dim_check(const int64_t dim[3])
+{
+    MVSIM_CHECK_ARG(dim != nullptr, "null dim");
+    for (int d = 0; d < 3; ++d) MVSIM_CHECK_ARG(dim[d] >= 2 && dim[d] <= (1 << 24), "the refraction simulator needs 2 .. 2^24 samples per dimension");
+    MVSIM_CHECK_ARG(dim[0] * dim[1] * dim[2] < ((int64_t)1 << 40), "volume too large");
+    return MVSIM_OK;
+}
+
+static size_t aberr_bytes(const int64_t dim[3]) { return (size_t)(dim[0] * dim[1] * dim[2]) * sizeof(float); }
+
+static int aberr_points_check(const double* xyz, int64_t n, double limit)
+{
+    MVSIM_CHECK_ARG(n >= 0 && (xyz || n == 0), "null point list or negative count");
+    for (int64_t i = 0; i < 3 * n; ++i) MVSIM_CHECK_ARG(std::fabs(xyz[i]) < limit, "position not finite or too far away");   // false for NaN
+    return MVSIM_OK;
+}
+
+static int hessian_at_args(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const double* xyz, int64_t n)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(img != nullptr, "null image");
+    MVSIM_TRY(aberr_points_check(xyz, n, 0x1.0p30));
+    return set_device(ctx);
+}
+
+int mvsim_hessian_at_dev(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const double* xyz, int64_t n, double* matrix9,
+                         double* eigvec3, double* eigval)
+{
+    MVSIM_TRY(hessian_at_args(ctx, img, dim, xyz, n));
+    return aberr_hessian_at_dev(ctx, img, dim, xyz, n, matrix9, eigvec3, eigval);
+}
+
+int mvsim_hessian_at(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const double* xyz, int64_t n, double* matrix9, double* eigvec3,
+                     double* eigval)
+{
+    MVSIM_TRY(hessian_at_args(ctx, img, dim, xyz, n));
+    MVSIM_TRY(up(ctx, ctx->vol_a, img, aberr_bytes(dim)));
+    return aberr_hessian_at_dev(ctx, ctx->vol_a.as<float>(), dim, xyz, n, matrix9, eigvec3, eigval);
+}
+
+static int hessian_images_args(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const float* eigval, const float* eigvec)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(img && eigval && eigvec, "null pointer");
+    return set_device(ctx);
+}
+
+int mvsim_hessian_images_dev(mvsim_ctx* ctx, const float* img, const int64_t dim[3], float* eigval, float* eigvec)
+{
+    MVSIM_TRY(hessian_images_args(ctx, img, dim, eigval, eigvec));
+    return aberr_hessian_images_dev(ctx, img, dim, eigval, eigvec);
+}
+
+int mvsim_hessian_images(mvsim_ctx* ctx, const float* img, const int64_t dim[3], float* eigval, float* eigvec)
+{
+    MVSIM_TRY(hessian_images_args(ctx, img, dim, eigval, eigvec));
+    const size_t bytes = aberr_bytes(dim);
+    MVSIM_TRY(up(ctx, ctx->vol_a, img, bytes));
+    MVSIM_TRY(ctx->vol_b.reserve(4 * bytes));
+    float* out = ctx->vol_b.as<float>();
+    MVSIM_TRY(aberr_hessian_images_dev(ctx, ctx->vol_a.as<float>(), dim, out, out + bytes / sizeof(float)));
+    MVSIM_HIP(hipMemcpyAsync(eigval, out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return down(ctx, eigvec, out + bytes / sizeof(float), 3 * bytes);
+}
+
+// What a call leaves the caller's java.util.Random at: a light-sheet ray takes three nextDouble() (six steps of the generator), a
+// camera ray two (four steps), whatever the launch shape traced (aberrations.hip: starts)
+static void advance_sheet_rays(uint64_t* rnd_state, int64_t rays) { *rnd_state = jr_jump(*rnd_state & JR_MASK, 6 * (uint64_t)rays); }
+static void advance_camera_rays(uint64_t* rnd_state, const int64_t dim[3], int rays_per_pixel)
+{
+    *rnd_state = jr_jump(*rnd_state & JR_MASK, 4 * (uint64_t)(dim[0] * dim[1]) * (uint64_t)rays_per_pixel);
+}
+
+static int rays_per_pixel_check(int rays_per_pixel)
+{
+    MVSIM_CHECK_ARG(rays_per_pixel >= 1 && rays_per_pixel <= 4096, "rays_per_pixel must be 1 .. 4096");
+    return MVSIM_OK;
+}
+
+int mvsim_refract3d_ray_starts(mvsim_ctx* ctx, uint64_t* rnd_state, const int64_t dim[3], int illum, int z, const double abc[3], int64_t n,
+                               double* pos3, double* dir3)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(rnd_state && abc && n >= 0 && ((pos3 && dir3) || n == 0), "null pointer or negative count");
+    MVSIM_CHECK_ARG(std::isfinite(abc[0]) && std::isfinite(abc[1]) && std::isfinite(abc[2]), "light sheet: non-finite coefficient");
+    MVSIM_TRY(set_device(ctx));
+    MVSIM_TRY(aberr_ray_starts(ctx, *rnd_state, dim, 0, illum, z, abc, 1, n, pos3, dir3));
+    advance_sheet_rays(rnd_state, n);
+    return MVSIM_OK;
+}
+
+int mvsim_camera_ray_starts(mvsim_ctx* ctx, uint64_t* rnd_state, const int64_t dim[3], int rays_per_pixel, double* pos3)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(rnd_state && pos3, "null pointer");
+    MVSIM_TRY(rays_per_pixel_check(rays_per_pixel));
+    MVSIM_TRY(set_device(ctx));
+    MVSIM_TRY(aberr_ray_starts(ctx, *rnd_state, dim, 1, 0, 0, nullptr, rays_per_pixel, dim[0] * dim[1] * rays_per_pixel, pos3, nullptr));
+    advance_camera_rays(rnd_state, dim, rays_per_pixel);
+    return MVSIM_OK;
+}
+
+// VolumeInjection's constructor (:74-92): the Gaussian of a point at the origin over its box, summed in cursor order (x fastest)
+static double aberr_sum_weights(const double sigma[3], int size[3], int* num_pixels)
+{
+    double tss[3], sum = 0;
+    aberr_inject_geometry(sigma, size, tss);
+    int count = 0;
+    for (int z = -(size[2] / 2); z < -(size[2] / 2) + size[2]; ++z)
+        for (int y = -(size[1] / 2); y < -(size[1] / 2) + size[1]; ++y)
+            for (int x = -(size[0] / 2); x < -(size[0] / 2) + size[0]; ++x) {
+                const double c[3] = {(double)x, (double)y, (double)z};
+                double value = 1;
+                for (int d = 0; d < 3; ++d) {
+                    const double q = 0.0 - c[d];
+                    value *= std::exp(-(q * q) / tss[d]);
+                }
+                sum += value;
+                ++count;
+            }
+    if (num_pixels) *num_pixels = count;
+    return sum;
+}
+
+static int aberr_sigma_check(const double sigma[3])
+{
+    MVSIM_CHECK_ARG(sigma != nullptr, "null sigma");
+    for (int d = 0; d < 3; ++d) MVSIM_CHECK_ARG(std::isfinite(sigma[d]) && sigma[d] > 0.0 && sigma[d] <= 1.0e4, "sigma must be finite, > 0 and <= 1e4");
+    return MVSIM_OK;
+}
+
+int mvsim_volume_inject_info(const double sigma[3], int32_t size[3], double* sum_weights, int32_t* num_pixels)
+{
+    MVSIM_TRY(aberr_sigma_check(sigma));
+    MVSIM_CHECK_ARG(size && sum_weights && num_pixels, "null pointer");
+    int s[3], np = 0;
+    *sum_weights = aberr_sum_weights(sigma, s, &np);
+    for (int d = 0; d < 3; ++d) size[d] = s[d];
+    *num_pixels = np;
+    return MVSIM_OK;
+}
+
+// everything refract3d checks, the light sheet's fit (SMVA:297) and the weight sum of the injected Gaussians (sigma 0.5)
+static int refract3d_args(mvsim_ctx* ctx, const float* img, const float* ri_img, const int64_t dim[3], double ls_middle, double ls_edge, double ri,
+                          int64_t num_rays, const uint64_t* rnd_state, const float* image, const float* weight, const mvsim_ray_steps* steps,
+                          double abc[3], double* sumw)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(rnd_state != nullptr, "null rnd_state");
+    MVSIM_CHECK_ARG(num_rays >= 0, "negative number of rays");
+    MVSIM_CHECK_ARG(std::isfinite(ls_middle) && std::isfinite(ls_edge) && std::isfinite(ri), "refract3d: non-finite argument");
+    MVSIM_CHECK_ARG(!steps || steps->capacity >= 0, "negative step capacity");
+    MVSIM_TRY(mvsim_lightsheet_fit(dim[0] / 2.0, ls_middle, (double)dim[0], ls_edge, abc));        // SMVA:297
+    MVSIM_CHECK_ARG(img && ri_img && ((image != nullptr) == (weight != nullptr)), "null volume (image and weight go together)");
+    MVSIM_TRY(set_device(ctx));
+    const double sigma[3] = {0.5, 0.5, 0.5};
+    int size[3];
+    *sumw = aberr_sum_weights(sigma, size, nullptr);
+    return MVSIM_OK;
+}
+
+int mvsim_refract3d_dev(mvsim_ctx* ctx, const float* img, const float* ri_img, const int64_t dim[3], int illum, int z, double ls_middle,
+                        double ls_edge, double ri, int64_t num_rays, uint64_t* rnd_state, float* image, float* weight, mvsim_ray_steps* steps)
+{
+    double abc[3], sumw;
+    MVSIM_TRY(refract3d_args(ctx, img, ri_img, dim, ls_middle, ls_edge, ri, num_rays, rnd_state, image, weight, steps, abc, &sumw));
+    MVSIM_TRY(aberr_refract3d_dev(ctx, img, ri_img, dim, illum, z, abc, ri, num_rays, *rnd_state, image, weight, sumw, steps));
+    advance_sheet_rays(rnd_state, num_rays);
+    return MVSIM_OK;
+}
+
+int mvsim_refract3d(mvsim_ctx* ctx, const float* img, const float* ri_img, const int64_t dim[3], int illum, int z, double ls_middle,
+                    double ls_edge, double ri, int64_t num_rays, uint64_t* rnd_state, float* image, float* weight, mvsim_ray_steps* steps)
+{
+    double abc[3], sumw;
+    MVSIM_TRY(refract3d_args(ctx, img, ri_img, dim, ls_middle, ls_edge, ri, num_rays, rnd_state, image, weight, steps, abc, &sumw));
+    const size_t bytes = aberr_bytes(dim);
+    MVSIM_TRY(up(ctx, ctx->vol_a, img, bytes));
+    MVSIM_TRY(up(ctx, ctx->vol_b, ri_img, bytes));
+    float* out = nullptr;
+    if (image) {
+        MVSIM_TRY(ctx->vol_c.reserve(2 * bytes));
+        out = ctx->vol_c.as<float>();
+        MVSIM_HIP(hipMemsetAsync(out, 0, 2 * bytes, ctx->stream));
+    }
+    MVSIM_TRY(aberr_refract3d_dev(ctx, ctx->vol_a.as<float>(), ctx->vol_b.as<float>(), dim, illum, z, abc, ri, num_rays, *rnd_state, out,
+                                  out ? out + bytes / sizeof(float) : nullptr, sumw, steps));
+    advance_sheet_rays(rnd_state, num_rays);
+    if (!image) return MVSIM_OK;
+    MVSIM_HIP(hipMemcpyAsync(image, out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return down(ctx, weight, out + bytes / sizeof(float), bytes);
+}
+
+static int volume_inject_args(mvsim_ctx* ctx, const float* image, const float* weight, const int64_t dim[3], const double sigma[3],
+                              const double* xyz, const double* intensity, int64_t n)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_TRY(aberr_sigma_check(sigma));
+    MVSIM_TRY(aberr_points_check(xyz, n, INFINITY));
+    MVSIM_CHECK_ARG(intensity || n == 0, "null intensity list");
+    for (int64_t i = 0; i < n; ++i) MVSIM_CHECK_ARG(std::isfinite(intensity[i]), "intensity not finite");
+    MVSIM_CHECK_ARG(image && weight, "null volume");
+    return set_device(ctx);
+}
+
+int mvsim_volume_inject_dev(mvsim_ctx* ctx, float* image, float* weight, const int64_t dim[3], const double sigma[3], const double* xyz,
+                            const double* intensity, int64_t n, int normalized)
+{
+    MVSIM_TRY(volume_inject_args(ctx, image, weight, dim, sigma, xyz, intensity, n));
+    if (n == 0) return MVSIM_OK;
+    int size[3];
+    const double sumw = normalized ? aberr_sum_weights(sigma, size, nullptr) : 0.0;
+    DevBuf pts;
+    int rc = pts.reserve((size_t)n * 4 * sizeof(double));
+    if (rc == MVSIM_OK) {
+        double* d = pts.as<double>();
+        hipError_t e = hipMemcpyAsync(d, xyz, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + 3 * n, intensity, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) { set_error("hipMemcpyAsync failed: %s", hipGetErrorString(e)); rc = MVSIM_EHIP; }
+        else rc = aberr_inject_dev(ctx, image, weight, dim, sigma, d, d + 3 * n, nullptr, n, sumw);
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    pts.release();
+    return rc;
+}
+
+int mvsim_volume_inject(mvsim_ctx* ctx, float* image, float* weight, const int64_t dim[3], const double sigma[3], const double* xyz,
+                        const double* intensity, int64_t n, int normalized)
+{
+    MVSIM_TRY(volume_inject_args(ctx, image, weight, dim, sigma, xyz, intensity, n));
+    const size_t bytes = aberr_bytes(dim);
+    MVSIM_TRY(up(ctx, ctx->vol_a, image, bytes));
+    MVSIM_TRY(up(ctx, ctx->vol_b, weight, bytes));
+    MVSIM_TRY(mvsim_volume_inject_dev(ctx, ctx->vol_a.as<float>(), ctx->vol_b.as<float>(), dim, sigma, xyz, intensity, n, normalized));
+    MVSIM_HIP(hipMemcpyAsync(image, ctx->vol_a.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return down(ctx, weight, ctx->vol_b.p, bytes);
+}
+
+static int volume_normalize_args(mvsim_ctx* ctx, const float* image, const float* weight, int64_t n, const float* out)
+{
+    MVSIM_CHECK_ARG(image && weight && out && n >= 1, "null volume or empty count");
+    return set_device(ctx);
+}
+
+int mvsim_volume_normalize_dev(mvsim_ctx* ctx, const float* image, const float* weight, int64_t n, float* out)
+{
+    MVSIM_TRY(volume_normalize_args(ctx, image, weight, n, out));
+    return aberr_normalize_dev(ctx, image, weight, n, out);
+}
+
+int mvsim_volume_normalize(mvsim_ctx* ctx, const float* image, const float* weight, int64_t n, float* out)
+{
+    MVSIM_TRY(volume_normalize_args(ctx, image, weight, n, out));
+    const size_t bytes = (size_t)n * sizeof(float);
+    MVSIM_TRY(up(ctx, ctx->vol_a, image, bytes));
+    MVSIM_TRY(up(ctx, ctx->vol_b, weight, bytes));
+    MVSIM_TRY(ctx->vol_c.reserve(bytes));
+    MVSIM_TRY(aberr_normalize_dev(ctx, ctx->vol_a.as<float>(), ctx->vol_b.as<float>(), n, ctx->vol_c.as<float>()));
+    return down(ctx, out, ctx->vol_c.p, bytes);
+}
+
+static int volume_project_args(mvsim_ctx* ctx, const float* image, const float* weight, const int64_t dim[3], const float* proj)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(image && weight && proj, "null pointer");
+    return set_device(ctx);
+}
+
+int mvsim_volume_project_dev(mvsim_ctx* ctx, const float* image, const float* weight, const int64_t dim[3], float* proj)
+{
+    MVSIM_TRY(volume_project_args(ctx, image, weight, dim, proj));
+    return aberr_project_dev(ctx, image, weight, dim, proj);
+}
+
+int mvsim_volume_project(mvsim_ctx* ctx, const float* image, const float* weight, const int64_t dim[3], float* proj)
+{
+    MVSIM_TRY(volume_project_args(ctx, image, weight, dim, proj));
+    const size_t bytes = aberr_bytes(dim), pbytes = (size_t)(dim[0] * dim[1]) * sizeof(float);
+    MVSIM_TRY(up(ctx, ctx->vol_a, image, bytes));
+    MVSIM_TRY(up(ctx, ctx->vol_b, weight, bytes));
+    MVSIM_TRY(ctx->vol_c.reserve(pbytes));
+    MVSIM_TRY(aberr_project_dev(ctx, ctx->vol_a.as<float>(), ctx->vol_b.as<float>(), dim, ctx->vol_c.as<float>()));
+    return down(ctx, proj, ctx->vol_c.p, pbytes);
+}
+
+static int project_to_camera_args(mvsim_ctx* ctx, const float* ri_img, const float* refr, const int64_t dim[3], int rays_per_pixel,
+                                  const uint64_t* rnd_state, const float* proj)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(ri_img && refr && proj && rnd_state, "null pointer");
+    MVSIM_TRY(rays_per_pixel_check(rays_per_pixel));
+    return set_device(ctx);
+}
+
+int mvsim_project_to_camera_dev(mvsim_ctx* ctx, const float* ri_img, const float* refr, const int64_t dim[3], int current_z,
+                                int rays_per_pixel, uint64_t* rnd_state, float* proj)
+{
+    MVSIM_TRY(project_to_camera_args(ctx, ri_img, refr, dim, rays_per_pixel, rnd_state, proj));
+    MVSIM_TRY(aberr_project_to_camera_dev(ctx, ri_img, refr, dim, current_z, rays_per_pixel, *rnd_state, proj));
+    advance_camera_rays(rnd_state, dim, rays_per_pixel);
+    return MVSIM_OK;
+}
+
+int mvsim_project_to_camera(mvsim_ctx* ctx, const float* ri_img, const float* refr, const int64_t dim[3], int current_z, int rays_per_pixel,
+                            uint64_t* rnd_state, float* proj)
+{
+    MVSIM_TRY(project_to_camera_args(ctx, ri_img, refr, dim, rays_per_pixel, rnd_state, proj));
+    const size_t bytes = aberr_bytes(dim), pbytes = (size_t)(dim[0] * dim[1]) * sizeof(float);
+    MVSIM_TRY(up(ctx, ctx->vol_a, ri_img, bytes));
+    MVSIM_TRY(up(ctx, ctx->vol_b, refr, bytes));
+    MVSIM_TRY(ctx->vol_c.reserve(pbytes));
+    MVSIM_TRY(aberr_project_to_camera_dev(ctx, ctx->vol_a.as<float>(), ctx->vol_b.as<float>(), dim, current_z, rays_per_pixel, *rnd_state,
+                                          ctx->vol_c.as<float>()));
+    advance_camera_rays(rnd_state, dim, rays_per_pixel);
+    return down(ctx, proj, ctx->vol_c.p, pbytes);
+}
+
+}  // extern "C"

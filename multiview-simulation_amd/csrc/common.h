@@ -109,6 +109,26 @@ struct PinnedRing {
     void release_all();
 };
 
+// The 16-bit transfer of acquisitions (option acq_transfer): Poisson counts (Tools.java:84 stores them as floats) are packed to uint16 on
+// the device, cross PCIe as half the bytes and are widened into the caller's buffers by the host threads -- or fetched as float32 after
+// all where the device flags a value that does not survive the round trip.  One device buffer [body of view 0][body of view 1] ...
+// [one flag word per view] (bodies padded to 256 bytes) and its page-locked twin; reserve -> pack per view -> fetch -> land
+// (api_host.cpp).  Every step is enqueued on the stream the caller names; land() expects that stream's work to have completed.
+struct CountsStaging {
+    DevBuf dev;
+    void*  host       = nullptr;       // page-locked twin
+    size_t host_bytes = 0;
+    std::vector<long long> count;      // values per view of the current call
+    std::vector<size_t>    body;       // byte offset of each view's body; body[views]: the flag words
+    std::vector<char>      packed;     // views pack() was called for since reserve()
+    int  reserve(const long long* counts, int views);
+    int  pack(hipStream_t s, int view, const float* src);          // the first pack() of a call clears the flags
+    int  fetch(hipStream_t s);                                     // ONE transfer: every body and the flags
+    // every packed view: flag test, statistics, float32 fallback from src_dev[view], or widening into dst_host[view] (one pool job)
+    int  land(mvsim_ctx* ctx, const float* const* src_dev, float* const* dst_host);
+    void release();
+};
+
 // Run-time switches of a context.  Defaults come from the environment, read ONCE per process (env_options); the tests
 // reach every code path through mvsim_set_option.  Nothing on a launch path calls getenv.
 struct Options {
@@ -162,7 +182,7 @@ struct Options {
                                        // view is sampled (snr >= 0), widened on the host; automatic float32 fallback per view.  0: always float32
     int     host_threads = 0;          // threads of the host-side widening (0 = auto: min(16, hardware threads))
     int     view_lanes = 0;            // mvsim_simulate_views_dev: views in flight side by side (0 = auto: from the size of a view)
-    int     view_batch = 2;            // mvsim_simulate_views_dev: the views STACKED -- one launch per stage for all of them (api.cpp:
+    int     view_batch = 2;            // mvsim_simulate_views_dev: the views STACKED -- one launch per stage for all of them (api_view.cpp:
                                        // views_enqueue_batched): 0 never, 1 whenever the views allow it, 2 auto (views of <= 2^26 voxels)
     bool    bcast_ring = false;        // ground-truth broadcast as one ncclBroadcast instead of scatter + all-gather
     bool    bcast_peer_copy = false;   // ... or as copy-engine transfers between IPC-mapped buffers (comm.cpp: bcast_peer_copy)
@@ -194,6 +214,7 @@ struct mvsim_ctx {
     mvsim_ctx();
     mvsim_ctx(const mvsim_ctx&) = delete;
     mvsim_ctx& operator=(const mvsim_ctx&) = delete;
+    template <class F> void each_workspace(F&& f);   // f(DevBuf&, traits) for every device workspace of the context (below)
     unsigned long long alloc_epoch = 1;     // see DevBuf::epoch
     int         roctx_depth = 0;            // stage ranges open on this context (rebalanced by every entry point after an error return)
     int         device     = 0;
@@ -262,17 +283,11 @@ struct mvsim_ctx {
     bool        tail_pending = false;
     const char *tail_lo[2] = {nullptr, nullptr}, *tail_hi[2] = {nullptr, nullptr};   // byte ranges the pending tail writes / reads
     mvsim::DevBuf async_gt[ASYNC_SLOTS], async_acq[ASYNC_SLOTS];
-    // acquisitions cross PCIe as 16-bit counts (option acq_transfer): packed on the device, widened on the host by mvsim_wait
-    mvsim::DevBuf async_u16[ASYNC_SLOTS];         // [n_out uint16, padded to 256 bytes][flag word]
-    void*      async_u16_host[ASYNC_SLOTS] = {};  // page-locked twin
-    size_t     async_u16_host_bytes[ASYNC_SLOTS] = {};
-    bool       async_as_u16[ASYNC_SLOTS] = {};
+    // acquisitions cross PCIe as 16-bit counts: one staging per pipelined slot (landed by mvsim_wait), one for the synchronous
+    // host-buffer entry points (down_counts, mvsim_simulate_views)
+    mvsim::CountsStaging async_counts[ASYNC_SLOTS], sync_counts;
     float*     async_out_acq[ASYNC_SLOTS] = {};   // the caller's acquisition buffer of the slot's view
-    long long  async_out_n[ASYNC_SLOTS] = {};
     long long  u16_views = 0, u16_fallbacks = 0;  // statistics (mvsim_get_transfer_stats)
-    mvsim::DevBuf sync_u16;                       // the same transfer for the synchronous host-buffer entry points (down_counts)
-    void*      sync_u16_host = nullptr;
-    size_t     sync_u16_host_bytes = 0;
     hipEvent_t ev_h2d[ASYNC_SLOTS] = {}, ev_compute[ASYNC_SLOTS] = {}, ev_d2h[ASYNC_SLOTS] = {};
     bool       async_inflight[ASYNC_SLOTS] = {};
     long long  async_ticket[ASYNC_SLOTS] = {};
@@ -313,12 +328,27 @@ struct mvsim_ctx {
     int   nranks = 1, rank = 0;
 };
 
-inline mvsim_ctx::mvsim_ctx()
+// Every device workspace a context owns -- the ONE list: the constructor (allocation epoch), mvsim_destroy and mvsim_release_caches
+// are written against it.  Traits say where the three have always differed:
+//   WS_KEPT      partials, partials_e: mvsim_release_caches keeps them (the fixed-size scalar / partial-sum slots of PARTIALS_BYTES and
+//                SUM_BLOCKS doubles, no cache that grows with a volume); mvsim_destroy frees them like everything else.
+//   WS_NO_EPOCH  beads_buf: carries no allocation epoch -- no captured view graph holds an address inside the bead renderer's buffers.
+enum { WS_KEPT = 1, WS_NO_EPOCH = 2 };
+template <class F> inline void mvsim_ctx::each_workspace(F&& f)
 {
     for (mvsim::DevBuf* b : {&vol_a, &vol_b, &vol_c, &out_buf, &psf_dev, &stencil_psf, &fft_real, &fft_spec_img, &fft_spec_psf, &fft_work,
-                             &pqueue, &view_tab, &sphere_list, &weight_img, &plane_flags, &host_gt, &host_rot, &host_att, &host_con, &partials, &partials_e, &cfft_f, &cfft_g,
-                             &cfft_g1, &cfft_g2, &partials_z, &async_gt[0], &async_gt[1], &async_acq[0], &async_acq[1], &async_u16[0], &async_u16[1], &sync_u16})
-        b->epoch = &alloc_epoch;
+                             &pqueue, &view_tab, &sphere_list, &weight_img, &plane_flags, &host_gt, &host_rot, &host_att, &host_con, &cfft_f, &cfft_g,
+                             &cfft_g1, &cfft_g2, &partials_z, &async_gt[0], &async_gt[1], &async_acq[0], &async_acq[1], &async_counts[0].dev,
+                             &async_counts[1].dev, &sync_counts.dev})
+        f(*b, 0);
+    f(partials, WS_KEPT);
+    f(partials_e, WS_KEPT);
+    for (mvsim::DevBuf& b : beads_buf) f(b, WS_NO_EPOCH);
+}
+
+inline mvsim_ctx::mvsim_ctx()
+{
+    each_workspace([this](mvsim::DevBuf& b, int traits) { if (!(traits & WS_NO_EPOCH)) b.epoch = &alloc_epoch; });
 }
 
 namespace mvsim {
@@ -371,14 +401,13 @@ int launch_downsample2x(hipStream_t s, const float* in, const int64_t dim[3], fl
 int draw_spheres_dev(mvsim_ctx* ctx, float* img, const int64_t dim[3], double min_value, double max_value, int scale,
                      int half_pixel_offset, uint64_t* rnd_state, int64_t* n_spheres);
 int splat_spheres_dev(mvsim_ctx* ctx, float* img, const int64_t dim[3], const mvsim_sphere* spheres, int64_t n);
-// SimulateBeads.renderPoints on device outputs (beads.hip); arguments validated by the caller (api.cpp)
+// SimulateBeads.renderPoints on device outputs (beads.hip); arguments validated by the caller (api_sims.cpp)
 int render_beads_dev(mvsim_ctx* ctx, const double* xyz, const int64_t* view_offsets, int64_t n, const double* m12, int nviews,
                      const int64_t dim[3], const int64_t imin[3], const double sigma[3], float* const* out_f32, uint16_t* const* out_u16);
 int beads_normalize_dev(mvsim_ctx* ctx, float* img, int64_t n);
 void beads_release(mvsim_ctx* ctx);
-// the refraction simulator (aberrations.hip); arguments validated by the caller (api.cpp), volumes on the device
+// the refraction simulator (aberrations.hip); arguments validated by the caller (api_sims.cpp), volumes on the device
 void aberr_inject_geometry(const double sigma[3], int size[3], double tss[3]);
-uint64_t aberr_random_jump(uint64_t state, uint64_t steps);
 int aberr_inject_dev(mvsim_ctx* ctx, float* image, float* weight, const int64_t dim[3], const double sigma[3], const double* xyz,
                      const double* inten, const float* val, int64_t n, double sumw);
 int aberr_refract3d_dev(mvsim_ctx* ctx, const float* img, const float* ri_img, const int64_t dim[3], int illum, int z, const double abc[3],

@@ -18,6 +18,7 @@
 // (nested truncated radii, x fastest).  (long)Math.sqrt of an exact integer equals the integer floor square root,
 // which is what isqrt() computes without floating-point rounding questions.
 #include "common.h"
+#include "jrandom.h"
 
 #include <cmath>
 #include <vector>
@@ -25,29 +26,6 @@
 namespace mvsim {
 
 namespace {
-
-// java.util.Random (JDK specification): 48-bit LCG
-struct JRandom {
-    uint64_t s;
-    int32_t next(int bits)
-    {
-        s = (s * 0x5DEECE66DULL + 0xBULL) & ((1ULL << 48) - 1);
-        return (int32_t)((int64_t)s >> (48 - bits));
-    }
-    int32_t next_int(int32_t bound)
-    {
-        int32_t r = next(31);
-        const int32_t m = bound - 1;
-        if ((bound & m) == 0) return (int32_t)(((int64_t)bound * (int64_t)r) >> 31);
-        for (int32_t u = r; (int32_t)((uint32_t)u - (uint32_t)(r = u % bound) + (uint32_t)m) < 0; u = next(31)) {}
-        return r;
-    }
-    double next_double()
-    {
-        const int64_t hi = (int64_t)next(26) << 27;
-        return (double)(hi + next(27)) * 0x1.0p-53;
-    }
-};
 
 inline int64_t isqrt_host(int64_t v)
 {
@@ -158,7 +136,7 @@ int draw_spheres_dev(mvsim_ctx* ctx, float* img, const int64_t dim[3], double mi
     int64_t modulus = 1;
     for (int d = 0; d < 3; ++d) modulus *= 7 * (int64_t)scale;
 
-    JRandom rnd{*rnd_state & ((1ULL << 48) - 1)};
+    JRandom rnd{*rnd_state & JR_MASK};
     std::vector<SphereItem> items;
     const int off_xy = half_pixel_offset ? 1 : 0;
     for (int64_t dz = -R; dz <= R; ++dz) {

@@ -75,7 +75,7 @@ def acquired(nz, inc):
 
 
 def slab_planes(case):
-    """(first acquired source plane, acquired planes, compact?) of a slab case (api.cpp: slab_finish_enqueue)."""
+    """(first acquired source plane, acquired planes, compact?) of a slab case (api_view.cpp: slab_finish_enqueue)."""
     z0, z1 = case.slab
     k0, k1 = (z0 + case.inc - 1) // case.inc, (z1 + case.inc - 1) // case.inc
     return k0 * case.inc, k1 - k0, case.inc > 1 and z0 % case.inc == 0
@@ -94,7 +94,7 @@ def launch_args(case):
         return (nx, ny, nz), case.inc, 0, 0, 0 if case.entry == "extract_dev" else 1, share_of(case.queue, plane * nzo)
     share = share_of(case.queue, plane * nzo)
     if case.entry in ("view", "views"):
-        # an untiled view convolves only the acquired planes (compact) when the queue samples them (api.cpp: view_enqueue)
+        # an untiled view convolves only the acquired planes (compact) when the queue samples them (api_view.cpp: view_enqueue)
         if case.inc > 1 and on:
             return (nx, ny, nzo), 1, case.inc, 0, 1, share
         return (nx, ny, nz), case.inc, 0, 0, 1, share

@@ -1524,6 +1524,50 @@ def test_async_acquisitions_cross_pcie_as_uint16_counts(mvs, synth):
                 assert 0 < want.max() < 65535 and np.all(want == np.round(want))
 
 
+def test_synchronous_counts_cross_pcie_as_uint16(mvs):
+    """The synchronous host-buffer entry points (down_counts) send sampled outputs of 2^20 values and more over PCIe as uint16 counts
+    too: the result equals the float32 transfer (acq_transfer=f32) bit for bit -- at the threshold, five values past it (the widening's
+    tail), and with one lambda of 10^5 among them (a count beyond 65 535: the automatic float32 fallback) --, mvsim_get_transfer_stats
+    moves by (1, 0) or (1, 1), and 2^20 - 1 values never take the path.  mvsim_release_caches frees the staging pair; the next call
+    builds it again, with the same result, and the statistics go on from where they were."""
+    snr = float(np.sqrt(5.0))                                     # poissonMul = (snr / sqrt 5)^2 = 1: the values ARE the lambdas
+    n = 1 << 20
+    lam = (4.0 + 2.0 * np.random.default_rng(20).random(n + 5)).astype(np.float32)
+    bright = lam[:n].copy()
+    bright[n // 2] = 1.0e5
+    vol = lam[:n].reshape(64, 128, 128)                           # extract_slices at inc 1: exactly 2^20 outputs
+    with mvs.Context(0) as c:
+        def sample(x, transfer):
+            c.set_option("acq_transfer", transfer)
+            if x.ndim == 3:
+                return c.extract_slices(x, 1, snr, SEED, stream=3)
+            y = x.copy()
+            c.poisson_process(y, snr, SEED, stream=3)
+            return y
+
+        def check(name, x, moved):
+            start = c.transfer_stats()
+            want = sample(x, "f32")
+            before = c.transfer_stats()
+            got = sample(x, "auto")
+            after = c.transfer_stats()
+            print(name, "stats", start, before, after, "max count", float(want.max()))
+            assert start == before, name                          # float32 transfers are not counted
+            assert got.shape == want.shape and np.array_equal(got, want), name
+            assert (after[0] - before[0], after[1] - before[1]) == moved, (name, before, after)
+            return got
+
+        first = check("2^20", lam[:n], (1, 0))
+        assert 0 < first.max() < 65535 and np.all(first == np.round(first))
+        check("2^20 + 5", lam, (1, 0))
+        assert check("one lambda of 1e5", bright, (1, 1)).max() > 65535
+        check("extract_slices 128 x 128 x 64", vol, (1, 0))
+        check("2^20 - 1", lam[:n - 1], (0, 0))
+        c.release_caches()
+        again = check("2^20 after release_caches", lam[:n], (1, 0))
+        assert np.array_equal(again, first)
+
+
 def test_simulate_views_with_host_buffers(mvs, synth):
     """mvsim_simulate_views: the view loop of `main` (SimulateMultiViewDataset.java:567-585) in ONE call with host buffers -- ground
     truth up once, the views stacked, the acquisitions back together as 16-bit counts -- equals one mvsim_simulate_view call per view,

@@ -407,6 +407,37 @@ def test_c_abi_host_only_leg_under_sanitizers(tmp_path):
     assert r.returncode == 0 and "host-only sanitizer run ok" in r.stdout, r.stdout + r.stderr
 
 
+@pytest.mark.parametrize("sanitizer", ["address,undefined", "thread"])
+def test_host_pool_and_generator_headers_under_sanitizers(tmp_path, sanitizer):
+    """tests/c_abi/host_pool_main.cpp: csrc/host_pool.h and csrc/jrandom.h compiled by plain g++ (no HIP, no libmvsim.so) into a
+    program of their own -- every widened value against a scalar loop for sizes around the 8-value step and the 2^20-value chunk,
+    aligned and unaligned destinations, 1 / 3 / 16 threads, two callers of the pool at once; java.util.Random against the JDK's
+    known answers of tests/golden/jdk_vectors.json and jump(s, k) against k single steps.  Once under ASan + UBSan, once under
+    ThreadSanitizer.  A child process, nothing preloaded."""
+    import json
+    import shutil
+    import subprocess
+    kat = json.load(open(os.path.join(ROOT, "tests", "golden", "jdk_vectors.json")))
+    exe = str(tmp_path / "host_pool_main")
+    cmd = [shutil.which("g++") or "g++", "-std=c++17", "-g", "-O1", "-fsanitize=" + sanitizer, "-fno-sanitize-recover=all", "-Wall", "-Wextra",
+           "-Werror", "-pthread", "-I" + os.path.join(ROOT, "multiview-simulation_amd", "csrc"),
+           os.path.join(ROOT, "tests", "c_abi", "host_pool_main.cpp"), "-o", exe]
+    b = subprocess.run(cmd, capture_output=True, text=True)
+    assert b.returncode == 0, b.stdout + b.stderr
+    args = [str(kat["seed"]), str(kat["random0_nextInt"]), "20", "D"] + [float(x).hex() for x in kat["nextDouble4"]] + \
+           ["I"] + [str(x) for x in kat["nextInt20_6"]]
+    r = subprocess.run([exe] + args, capture_output=True, text=True)
+    if r.returncode != 0 and not r.stdout and shutil.which("setarch") and \
+            ("unexpected memory mapping" in r.stderr or "ThreadSanitizer" not in r.stderr):
+        # The sanitizer's runtime gave up before main(), with "unexpected memory mapping" or with a bare SIGSEGV and no report: older
+        # ThreadSanitizer runtimes cannot place their shadow under a kernel that randomises mappings over more than 28 bits.  Same
+        # program, this one process without address randomisation; a fault of the program itself comes back in this run.
+        r = subprocess.run(["setarch", os.uname().machine, "-R", exe] + args, capture_output=True, text=True)
+    assert r.returncode == 0 and "host pool and generator run ok" in r.stdout, \
+        f"host_pool_main under -fsanitize={sanitizer}: exit {r.returncode} (setarch for the run without address randomisation: " \
+        f"{shutil.which('setarch')})\n" + r.stdout + r.stderr
+
+
 def test_jni_shim_covers_every_native_method():
     """Source-only Java layer (no JDK in the image): at least keep MvsimNative.java and java/jni/mvsim_jni.cpp in step --
     every `static native` method has exactly one JNI_FN definition, and the shim only calls C-ABI symbols the header
