@@ -399,7 +399,7 @@ static int views_enqueue_batched(mvsim_ctx* ctx, const float* gt, const int64_t 
     tail.corr_n = n; tail.min_value = p0.min_value; tail.target_average = p0.target_average;
     int64_t P[3];
     if (!custom_fft_sizes(dim, kdim, P, ctx->opt)) { set_error("stacked views: no hand-written FFT size"); return MVSIM_EINVAL; }
-    MVSIM_TRY(custom_fft_convolve(ctx, ctx->vol_b.as<float>(), dim, reinterpret_cast<const float*>(dp + off_p), kdim, P, con, &tail));
+    MVSIM_TRY(custom_fft_convolve(ctx, ctx->vol_b.as<float>(), dim, reinterpret_cast<const float*>(dp + off_p), kdim, con, &tail));
     if (!tail.corr_done || tail.zstride != zstride) { set_error("stacked views: the convolution did not deliver the factors / planes asked for"); return MVSIM_EHIP; }
 
     ev_begin(ctx, ST_EXTRACT);
@@ -604,7 +604,7 @@ static int slab_convolve_enqueue(mvsim_ctx* ctx, const float* gt, const int64_t 
     tail.zstride = (p->inc > 1 && z0 % p->inc == 0) ? p->inc : 1;
     tail.x_done = x_done;
     ctx->slab_z0 = ctx->slab_z1 = -1;
-    MVSIM_TRY(custom_fft_convolve_slab(ctx, x_done ? nullptr : ctx->vol_b.as<float>(), dim, ctx->psf_dev.as<float>(), kdim, P, slab,
+    MVSIM_TRY(custom_fft_convolve_slab(ctx, x_done ? nullptr : ctx->vol_b.as<float>(), dim, ctx->psf_dev.as<float>(), kdim, slab,
                                        ctx->vol_a.as<float>(), &tail));
     ctx->slab_z0 = z0; ctx->slab_z1 = z1; ctx->slab_zstride = tail.zstride;
     return MVSIM_OK;

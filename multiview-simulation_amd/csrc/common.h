@@ -5,6 +5,7 @@
 #include <rocfft/rocfft.h>
 #include <roctracer/roctx.h>
 
+#include <algorithm>
 #include <array>
 #include <cstdarg>
 #include <cstdint>
@@ -490,8 +491,29 @@ bool custom_fft_sizes(const int64_t dim[3], const int64_t kdim[3], int64_t P[3],
 // orders a pending tail (extract + Poisson of the last view, on the tail stream) in front of whatever is enqueued on
 // ctx->stream next
 int  join_tail(mvsim_ctx* ctx);
+// The geometry of one hand-written convolution, everything that follows from (dim, kdim, options) alone: conv_plan() derives it (false
+// where custom_fft_sizes is) and nothing else does -- the fused rotate + x transform, the stacked-view test, the fused tail and the driver read it.
+struct ConvPlan {
+    int     n[3], k[3];             // volume and PSF extents
+    int64_t P[3];                   // padded lengths (custom_fft_sizes)
+    int     px, py, pz, M;          // ... as ints; M = Px / 2, the half length of the x passes
+    int     tile_y, tile_z;         // lines per tile of the y and z FFT passes
+    bool    zdirect;                // z pass: direct convolution with the Kz taps, unless the PSF is deep or fft_zpass=fft
+    bool    ymirror;                // pass A transforms the Ny rows of a plane only, pass B reads the y halo from their mirror images
+    bool    early;                  // adjustImage's sum from the z pass instead of pass E
+    bool    zinline_auto;           // fft_zpass=auto takes the inline FFT z pass for whole single views
+    int     hxp, pyb;               // complex row pitch of the spectrum (M + 1 rounded up to the widest tile); rows of a plane in the z-blocked layout
+    int     e_rows;                 // rows per block of pass E
+    // bytes of each spectrum buffer, F and G: nz_in planes enter the z pass, nz_out leave it at a pitch of nz_pitch planes per view
+    size_t spectrum_bytes(int nz_in, int nz_out, int nz_pitch, int views) const
+    {
+        const size_t planes = zdirect ? (size_t)views * std::max(nz_in, std::max(nz_out, nz_pitch)) : (size_t)pz;
+        return (size_t)hxp * (zdirect ? pyb : py) * planes * sizeof(float2);
+    }
+};
+bool conv_plan(const int64_t dim[3], const int64_t kdim[3], const Options& opt, ConvPlan* pl);
 int  custom_fft_convolve(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const float* psf,
-                         const int64_t kdim[3], const int64_t P[3], float* out, ConvTail* tail);
+                         const int64_t kdim[3], float* out, ConvTail* tail);
 // z-slab form (direct z pass only): `img` holds the planes [z_in0, z_in0 + nz_in) of a volume with dim[2] planes,
 // `out` receives the planes [z_out0, z_out0 + nz_out); every plane the Kz taps reach (mirrored at the global faces)
 // must lie inside the input range.  The sum left in the context's scalar slot is the sum of the output planes.
@@ -499,7 +521,7 @@ struct SlabRange {
     int z_in0, nz_in, z_out0, nz_out;
 };
 int  custom_fft_convolve_slab(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const float* psf,
-                              const int64_t kdim[3], const int64_t P[3], const SlabRange& slab, float* out, ConvTail* tail);
+                              const int64_t kdim[3], const SlabRange& slab, float* out, ConvTail* tail);
 void custom_fft_release(mvsim_ctx* ctx);
 bool custom_fft_geometry(const int64_t dim[3], const int64_t kdim[3], int64_t g[5], const Options& opt);
 // {blocks, items per segment} of the fused tail (pass E adjusts, extracts and samples); false when the view would not be fused

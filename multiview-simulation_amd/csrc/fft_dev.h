@@ -424,7 +424,9 @@ struct RotFftArgs {
     int*   plane_nz;         // [nz], zeroed by the caller: set to 1 for every plane that holds a non-zero attenuated voxel (null: not wanted)
 };
 
-bool rot_fftx_has_plan(int M);
+// half lengths the fused kernel is instantiated for (rows of up to 1024 voxels with PSFs of up to 64 taps); the plans --
+// radices and with them the layout of the twiddle table -- are the size table's own
+constexpr bool rot_fftx_len_ok(int len) { return len >= 72 && len <= 576; }
 int  launch_rot_fftx(mvsim_ctx* ctx, int M, const RotFftArgs& a, bool write_out);
 
 }  // namespace fft

@@ -19,6 +19,7 @@
 #include "fft_dev.h"
 #include "poisson_dev.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -1414,23 +1415,6 @@ __global__ __launch_bounds__(ZT, ZBLOCKS_PER_CU) void k_zconv_strided(ZConvArgs 
     }
 }
 
-struct PlanDesc {
-    int len;
-    int nrad;
-    int rad[5];
-};
-static const PlanDesc kPlans[] = {
-#define X(L, ...) {L, (int)(sizeof((int[]){__VA_ARGS__}) / sizeof(int)), {__VA_ARGS__}},
-    MVSIM_FFT_SIZES(X)
-#undef X
-};
-
-static const int kSizes[] = {
-#define X(L, ...) L,
-    MVSIM_FFT_SIZES(X)
-#undef X
-};
-
 template <class K> static int set_lds(mvsim_ctx* ctx, K kernel, size_t bytes)
 {
     return ensure_lds_attr(ctx, reinterpret_cast<const void*>(kernel), bytes);
@@ -1575,7 +1559,7 @@ static int launch_r2c_t(mvsim_ctx* ctx, const float* src, const SrcMap& map, flo
 template <class PLAN>
 static int launch_c2r_t(mvsim_ctx* ctx, const float2* srcc, float* out, const float2* tw, const float2* twx, int hxp,
                         int py, int nx, int ny, long long rows, float scale, double* partial, int* nblocks, const C2RFuse* fuse,
-                        const C2REmpty& em = C2REmpty{})
+                        const C2REmpty& em)
 {
     using C = CfgX<PLAN::len>;
     const long long groups = (rows + C::NL - 1) / C::NL;
@@ -1594,18 +1578,6 @@ static int launch_c2r_t(mvsim_ctx* ctx, const float2* srcc, float* out, const fl
     }
     MVSIM_HIP(hipGetLastError());
     return MVSIM_OK;
-}
-
-// rows per block of pass E for this half length (the queue segments of the fused tail are per block)
-template <class PLAN> static int c2r_rows_per_block_t() { return CfgX<PLAN::len>::NL; }
-static int c2r_rows_per_block(int M)
-{
-    switch (M) {
-#define X(LL, ...) case LL: return c2r_rows_per_block_t<Plan<LL, __VA_ARGS__>>();
-        MVSIM_FFT_SIZES(X)
-#undef X
-    }
-    return 0;
 }
 
 // the half-length plans k_fft_lines_split is instantiated for: 2 LH is a table length whose own tile leaves a CU room for one block only,
@@ -1627,119 +1599,83 @@ template <int LH> constexpr bool split_half_ok()
 template <int LH, int... Rs>
 static int launch_lines_split_t(mvsim_ctx* ctx, int mode, const LinesArgs& a, const float2* tw2, int tiles, int nouter)
 {
-    if constexpr (LH >= 1024 && LH <= 1120 && split_half_ok<LH>()) {
-        using PLANH = Plan<LH, Rs...>;
-        using C = Cfg<LH>;
-        // `tiles` counts tiles of the whole length's width (8 columns); the half length's tiles may be 16 wide
-        constexpr int WIDE = C::NL / Cfg<2 * LH>::NL;
-        if (tiles % WIDE) { set_error("custom FFT: %d tiles of 8 columns do not pair up", tiles); return MVSIM_EINVAL; }
-        dim3 grid(tiles / WIDE, nouter), block(C::T);
-        if (mode == FWD) {
-            MVSIM_TRY(set_lds(ctx, k_fft_lines_split<PLANH, FWD>, C::LDS));
-            hipLaunchKernelGGL((k_fft_lines_split<PLANH, FWD>), grid, block, C::LDS, ctx->stream, a, tw2);
-        } else {
-            MVSIM_TRY(set_lds(ctx, k_fft_lines_split<PLANH, INV>, C::LDS));
-            hipLaunchKernelGGL((k_fft_lines_split<PLANH, INV>), grid, block, C::LDS, ctx->stream, a, tw2);
-        }
-        MVSIM_HIP(hipGetLastError());
-        return MVSIM_OK;
+    using PLANH = Plan<LH, Rs...>;
+    using C = Cfg<LH>;
+    // `tiles` counts tiles of the whole length's width (8 columns); the half length's tiles may be 16 wide
+    constexpr int WIDE = C::NL / Cfg<2 * LH>::NL;
+    if (tiles % WIDE) { set_error("custom FFT: %d tiles of 8 columns do not pair up", tiles); return MVSIM_EINVAL; }
+    dim3 grid(tiles / WIDE, nouter), block(C::T);
+    if (mode == FWD) {
+        MVSIM_TRY(set_lds(ctx, k_fft_lines_split<PLANH, FWD>, C::LDS));
+        hipLaunchKernelGGL((k_fft_lines_split<PLANH, FWD>), grid, block, C::LDS, ctx->stream, a, tw2);
+    } else {
+        MVSIM_TRY(set_lds(ctx, k_fft_lines_split<PLANH, INV>, C::LDS));
+        hipLaunchKernelGGL((k_fft_lines_split<PLANH, INV>), grid, block, C::LDS, ctx->stream, a, tw2);
     }
-    set_error("custom FFT: no split form for half length %d", LH);
-    return MVSIM_EINVAL;
+    MVSIM_HIP(hipGetLastError());
+    return MVSIM_OK;
 }
 
-static bool lines_split_available(int L)
+// ---------------------------------------------------------------------------------- the length table
+// One entry per length of MVSIM_FFT_SIZES, ascending: everything the host asks about a length or launches for it.
+struct LenEntry {
+    int len, nrad, rad[5];
+    int nl;                 // Cfg<len>::NL: lines per tile of the y and z passes
+    int nlx;                // CfgX<len>::NL: rows per block of the x passes with this HALF length (the fused tail's queue segments are per block)
+    int (*lines)(mvsim_ctx*, int mode, bool sparse, const LinesArgs&, int tiles, int nouter);
+    // lines of 2 len points as two transforms of this length (k_fft_lines_split); null where that kernel is not instantiated
+    int (*lines_split)(mvsim_ctx*, int mode, const LinesArgs&, const float2* tw2, int tiles, int nouter);
+    int (*r2c)(mvsim_ctx*, const float* src, const SrcMap&, float2* dst, const float2* tw, const float2* twx, int hxp, long long rows);
+    int (*c2r)(mvsim_ctx*, const float2* srcc, float* out, const float2* tw, const float2* twx, int hxp, int py, int nx, int ny,
+               long long rows, float scale, double* partial, int* nblocks, const C2RFuse* fuse, const C2REmpty& em);
+};
+
+template <int LH, int... Rs> constexpr decltype(LenEntry::lines_split) lines_split_of()
 {
-    if (L % 2) return false;
-    switch (L / 2) {
-#define X(LL, ...) case LL: if constexpr (LL >= 1024 && LL <= 1120) return split_half_ok<LL>(); else return false;
-        MVSIM_FFT_SIZES(X)
-#undef X
-    }
-    return false;
+    if constexpr (LH >= 1024 && LH <= 1120 && split_half_ok<LH>()) return &launch_lines_split_t<LH, Rs...>;
+    else return nullptr;
 }
 
-static bool lines_has_plan(int L)
-{
-    switch (L) {
-#define X(LL, ...) case LL: return true;
-        MVSIM_FFT_SIZES(X)
+static constexpr LenEntry kLens[] = {
+#define X(L, ...)                                                                                                             \
+    {L, (int)(sizeof((int[]){__VA_ARGS__}) / sizeof(int)), {__VA_ARGS__}, Cfg<L>::NL, CfgX<L>::NL,                            \
+     &launch_lines_t<Plan<L, __VA_ARGS__>>, lines_split_of<L, __VA_ARGS__>(), &launch_r2c_t<Plan<L, __VA_ARGS__>>,            \
+     &launch_c2r_t<Plan<L, __VA_ARGS__>>},
+    MVSIM_FFT_SIZES(X)
 #undef X
-    }
-    return false;
+};
+
+// the smallest table length >= need (null past the table), and the entry of length L itself
+static const LenEntry* pick_len(int64_t need)
+{
+    const LenEntry* e = std::lower_bound(std::begin(kLens), std::end(kLens), need, [](const LenEntry& x, int64_t v) { return x.len < v; });
+    return e == std::end(kLens) ? nullptr : e;
 }
+static const LenEntry* find_len(int L)
+{
+    const LenEntry* e = pick_len(L);
+    return e && e->len == L ? e : nullptr;
+}
+
+static int lines_per_tile(int L) { const LenEntry* e = find_len(L); return e ? e->nl : 16; }
 
 static int launch_lines(mvsim_ctx* s, int L, int mode, bool sparse, const LinesArgs& a0, int tiles, int nouter)
 {
+    const LenEntry* e = find_len(L);
+    if (!e) { set_error("custom FFT: unsupported length %d", L); return MVSIM_EINVAL; }
     LinesArgs a = a0;
     a.pair_tiles = (s->opt.exp & 4) ? 0 : 1;              // exp bit 4: 8-column tiles in plain grid order (A/B, tools/ab_env.sh)
     // lines of one block per CU: the image's y passes as two half-length transforms (k_fft_lines_split) unless exp bit 8 asks for the
     // one-block form; the PSF's sparse passes and the z-pass forms keep k_fft_lines
-    if ((mode == FWD || mode == INV) && !sparse && !a.dst_tile_major && !(s->opt.exp & 8) && lines_has_plan(L) && lines_split_available(L) &&
-        tiles % 2 == 0 && (!a.src_mirror || (a.lmap.mode == 0 && a.lmap.b < a.lmap.n && a.lmap.a - a.lmap.n < a.lmap.n))) {
-        const float2 *twh = nullptr, *tw2 = nullptr;
-        MVSIM_TRY(ensure_twiddles(s, L / 2, 0, &twh));
+    const LenEntry* h = L % 2 ? nullptr : find_len(L / 2);
+    if ((mode == FWD || mode == INV) && !sparse && !a.dst_tile_major && !(s->opt.exp & 8) && h && h->lines_split && tiles % 2 == 0 &&
+        (!a.src_mirror || (a.lmap.mode == 0 && a.lmap.b < a.lmap.n && a.lmap.a - a.lmap.n < a.lmap.n))) {
+        const float2* tw2 = nullptr;
+        MVSIM_TRY(ensure_twiddles(s, L / 2, 0, &a.tw));
         MVSIM_TRY(ensure_twiddles(s, L, 1, &tw2));
-        a.tw = twh;
-        switch (L / 2) {
-#define X(LL, ...) case LL: return launch_lines_split_t<LL, __VA_ARGS__>(s, mode, a, tw2, tiles, nouter);
-            MVSIM_FFT_SIZES(X)
-#undef X
-        }
+        return h->lines_split(s, mode, a, tw2, tiles, nouter);
     }
-    switch (L) {
-#define X(LL, ...) \
-    case LL: return launch_lines_t<Plan<LL, __VA_ARGS__>>(s, mode, sparse, a, tiles, nouter);
-        MVSIM_FFT_SIZES(X)
-#undef X
-    }
-    set_error("custom FFT: unsupported length %d", L);
-    return MVSIM_EINVAL;
-}
-
-static int launch_r2c(mvsim_ctx* s, int M, const float* src, const SrcMap& map, float2* dst, const float2* tw,
-                      const float2* twx, int hxp, long long rows)
-{
-    switch (M) {
-#define X(LL, ...) \
-    case LL: return launch_r2c_t<Plan<LL, __VA_ARGS__>>(s, src, map, dst, tw, twx, hxp, rows);
-        MVSIM_FFT_SIZES(X)
-#undef X
-    }
-    set_error("custom FFT: unsupported half length %d", M);
-    return MVSIM_EINVAL;
-}
-
-static int launch_c2r(mvsim_ctx* s, int M, const float2* srcc, float* out, const float2* tw, const float2* twx, int hxp,
-                      int py, int nx, int ny, long long rows, float scale, double* partial, int* nblocks, const C2RFuse* fuse,
-                        const C2REmpty& em = C2REmpty{})
-{
-    switch (M) {
-#define X(LL, ...) \
-    case LL: return launch_c2r_t<Plan<LL, __VA_ARGS__>>(s, srcc, out, tw, twx, hxp, py, nx, ny, rows, scale, partial, nblocks, fuse, em);
-        MVSIM_FFT_SIZES(X)
-#undef X
-    }
-    set_error("custom FFT: unsupported half length %d", M);
-    return MVSIM_EINVAL;
-}
-
-template <int L> static constexpr int nl_of() { return Cfg<L>::NL; }
-static int lines_per_tile(int L)
-{
-    switch (L) {
-#define X(LL, ...) case LL: return nl_of<LL>();
-        MVSIM_FFT_SIZES(X)
-#undef X
-    }
-    return 16;
-}
-
-static int pick_size(int64_t need)
-{
-    for (int v : kSizes)
-        if (v >= need) return v;
-    return 0;
+    return e->lines(s, mode, sparse, a, tiles, nouter);
 }
 
 }  // namespace fft
@@ -1748,18 +1684,33 @@ static int pick_size(int64_t need)
 bool custom_fft_sizes(const int64_t dim[3], const int64_t kdim[3], int64_t P[3], const Options& opt)
 {
     if (opt.rocfft) return false;
-    for (int d = 0; d < 3; ++d) {
+    for (int d = 0; d < 3; ++d) {                                  // x: twice the half length M
         const int64_t need = dim[d] + kdim[d] - 1;
-        if (d == 0) {
-            const int m = fft::pick_size((need + 1) / 2);
-            if (!m) return false;
-            P[0] = 2 * (int64_t)m;
-        } else {
-            const int v = fft::pick_size(need);
-            if (!v) return false;
-            P[d] = v;
-        }
+        const fft::LenEntry* e = fft::pick_len(d == 0 ? (need + 1) / 2 : need);
+        if (!e) return false;
+        P[d] = d == 0 ? 2 * (int64_t)e->len : e->len;
     }
+    return true;
+}
+
+// The one place the geometry of the hand-written convolution is derived (ConvPlan, common.h).
+bool conv_plan(const int64_t dim[3], const int64_t kdim[3], const Options& opt, ConvPlan* pl)
+{
+    using namespace fft;
+    if (!custom_fft_sizes(dim, kdim, pl->P, opt)) return false;
+    for (int d = 0; d < 3; ++d) { pl->n[d] = (int)dim[d]; pl->k[d] = (int)kdim[d]; }
+    pl->px = (int)pl->P[0]; pl->py = (int)pl->P[1]; pl->pz = (int)pl->P[2]; pl->M = pl->px / 2;
+    pl->tile_y = lines_per_tile(pl->py); pl->tile_z = lines_per_tile(pl->pz);
+    const int ny = pl->n[1], ky = pl->k[1], kz = pl->k[2];
+    pl->zdirect = opt.zpass == 2 ? false : kz <= 64;
+    pl->ymirror = pl->zdirect && ny > 1 && ky / 2 < ny && ky - 1 - ky / 2 < ny;   // one reflection reaches every halo row
+    pl->early = pl->zdirect && opt.early_sum;
+    // measured (profiles/r04_zpass_sweep.txt, see zpass_inline): deep PSFs on z lengths of 512 .. 576
+    pl->zinline_auto = opt.zpass == 0 && kz >= MVSIM_ZINLINE_MIN_KZ && pl->pz >= 512 && pl->tile_z == 16;
+    const int tw_max = std::max(pl->tile_y, pl->zdirect ? NLZ : pl->tile_z);
+    pl->hxp = (pl->M + 1 + tw_max - 1) / tw_max * tw_max;
+    pl->pyb = (pl->py + ZB - 1) / ZB * ZB;
+    pl->e_rows = find_len(pl->M)->nlx;
     return true;
 }
 
@@ -1777,8 +1728,7 @@ static int ensure_twiddles(mvsim_ctx* ctx, int L, int kind, const float2** out)
             h[k] = make_float2((float)std::cos(a), (float)std::sin(a));
         }
     } else {
-        const fft::PlanDesc* pd = nullptr;
-        for (const auto& d : fft::kPlans) if (d.len == L) pd = &d;
+        const fft::LenEntry* pd = fft::find_len(L);
         if (!pd) { set_error("custom FFT: no plan for length %d", L); return MVSIM_EINVAL; }
         int P = 1, off = 0;
         for (int i = 0; i < pd->nrad; ++i) {
@@ -1840,21 +1790,21 @@ static int ensure_box_weights(mvsim_ctx* ctx, int N, int P, int len, bool half, 
 }
 
 // Geometry of the fused tail: pass E blocks own queue segments that can hold every voxel of their rows.
-bool fused_tail_geometry(const int64_t dim[3], const int64_t kdim[3], int inc, bool con_wanted, const Options& opt,
-                                long long* blocks, unsigned int* segcap)
+static bool fused_tail_of(const ConvPlan& pl, int inc, bool con_wanted, long long* blocks, unsigned int* segcap)
 {
-    int64_t P[3];
-    if (!custom_fft_sizes(dim, kdim, P, opt)) return false;
-    const bool zdirect = opt.zpass == 2 ? false : kdim[2] <= 64;
-    if (!zdirect || !opt.early_sum || (dim[0] & 3) != 0) return false;
-    const int nr = fft::c2r_rows_per_block((int)(P[0] / 2));
-    if (nr <= 0) return false;
-    const long long nk = con_wanted ? dim[2] : (dim[2] - 1) / inc + 1;
-    const long long rows = dim[1] * nk;
-    if (rows * dim[0] >= (1ll << 32)) return false;               // work items carry the output position in 32 bits
-    *blocks = (rows + nr - 1) / nr;
-    *segcap = (unsigned int)(nr * dim[0]);
+    if (!pl.early || (pl.n[0] & 3) != 0) return false;
+    const long long nk = con_wanted ? pl.n[2] : (pl.n[2] - 1) / inc + 1;
+    const long long rows = pl.n[1] * nk;
+    if (rows * pl.n[0] >= (1ll << 32)) return false;               // work items carry the output position in 32 bits
+    *blocks = (rows + pl.e_rows - 1) / pl.e_rows;
+    *segcap = (unsigned int)(pl.e_rows * pl.n[0]);
     return true;
+}
+
+bool fused_tail_geometry(const int64_t dim[3], const int64_t kdim[3], int inc, bool con_wanted, const Options& opt, long long* blocks, unsigned int* segcap)
+{
+    ConvPlan pl;
+    return conv_plan(dim, kdim, opt, &pl) && fused_tail_of(pl, inc, con_wanted, blocks, segcap);
 }
 
 size_t fused_tail_queue_bytes(const int64_t dim[3], const int64_t kdim[3], int inc, bool con_wanted, const Options& opt)
@@ -1882,31 +1832,17 @@ void custom_fft_release(mvsim_ctx* ctx)
 // {Px, Py, Pz, Hxp, direct z pass?} of the hand-written path for this volume / PSF (what the passes move through HBM)
 bool custom_fft_geometry(const int64_t dim[3], const int64_t kdim[3], int64_t g[5], const Options& opt)
 {
-    using namespace fft;
-    int64_t P[3];
-    if (!custom_fft_sizes(dim, kdim, P, opt)) return false;
-    const bool zdirect = opt.zpass == 2 ? false : kdim[2] <= 64;
-    const int tile_y = lines_per_tile((int)P[1]), tile_z = lines_per_tile((int)P[2]);
-    int tw_max = tile_y > tile_z ? tile_y : tile_z;
-    if (zdirect) tw_max = tile_y > NLZ ? tile_y : NLZ;
-    const int M = (int)(P[0] / 2);
-    g[0] = P[0]; g[1] = P[1]; g[2] = zdirect ? dim[2] : P[2];
-    g[3] = ((M + 1 + tw_max - 1) / tw_max) * tw_max;
-    g[4] = zdirect ? 1 : 0;
+    ConvPlan pl;
+    if (!conv_plan(dim, kdim, opt, &pl)) return false;
+    g[0] = pl.px; g[1] = pl.py; g[2] = pl.zdirect ? pl.n[2] : pl.pz; g[3] = pl.hxp; g[4] = pl.zdirect ? 1 : 0;
     return true;
 }
 
 bool custom_fft_batchable(const mvsim_ctx* ctx, const int64_t dim[3], const int64_t kdim[3])
 {
-    using namespace fft;
     const Options& o = ctx->opt;
-    int64_t P[3];
-    if (!custom_fft_sizes(dim, kdim, P, o)) return false;
-    const int ny = (int)dim[1], ky = (int)kdim[1], kz = (int)kdim[2];
-    const bool zdirect = o.zpass == 2 ? false : kz <= 64;
-    if (!zdirect || !o.early_sum || o.fuse_tail || o.zpass == 3) return false;
-    if (o.zpass == 0 && kz >= MVSIM_ZINLINE_MIN_KZ && P[2] >= 512 && lines_per_tile((int)P[2]) == 16) return false;   // the inline FFT z pass
-    return ny > 1 && ky / 2 < ny && ky - 1 - ky / 2 < ny;         // one reflection reaches every halo row (ymirror)
+    ConvPlan pl;
+    return conv_plan(dim, kdim, o, &pl) && pl.early && !o.fuse_tail && o.zpass != 3 && !pl.zinline_auto && pl.ymirror;
 }
 
 // Rotate (about x) + attenuate + pass A as one kernel (rotate_fft.hip) when the view's geometry allows it: the attenuated
@@ -1925,26 +1861,20 @@ int rotate_attenuate_fftx(mvsim_ctx* ctx, const float* gt, float* rot_or_null, f
     const bool x_identity = inv.m[0] == 1.0 && inv.m[1] == 0.0 && inv.m[2] == 0.0 && inv.m[3] == 0.0 &&
                             inv.m[4] == 0.0 && inv.m[8] == 0.0;
     if (!x_identity) return MVSIM_OK;
-    int64_t P[3];
-    if (!custom_fft_sizes(dim, kdim, P, ctx->opt)) return MVSIM_OK;
-    const int nx = (int)dim[0], ny = (int)dim[1], nz = (int)dim[2];
+    ConvPlan pl;
+    if (!conv_plan(dim, kdim, ctx->opt, &pl)) return MVSIM_OK;
+    const int nx = pl.n[0], ny = pl.n[1], nz = pl.n[2], kx = pl.k[0];
     if (nzl < 0) { z_first = 0; nzl = nz; }
     if (z_first < 0 || nzl < 1 || z_first + nzl > nz) return MVSIM_OK;
-    const int kx = (int)kdim[0], ky = (int)kdim[1], kz = (int)kdim[2];
-    const bool zdirect = ctx->opt.zpass == 2 ? false : kz <= 64;
     // pass B must be reading the mirrored halo rows from their mirror images (pass A then transforms the Ny rows of a plane
     // only -- what this kernel produces), the padded x row must be one reflection deep, one block must span the row
-    const bool ymirror = zdirect && ny > 1 && ky / 2 < ny && ky - 1 - ky / 2 < ny;
-    if (!ymirror || nx > 1024 || nx < 64 || kx > nx || nx > ny) return MVSIM_OK;
-    const int px = (int)P[0], py = (int)P[1], M = px / 2;
-    if (!rot_fftx_has_plan(M)) return MVSIM_OK;
+    if (!pl.ymirror || nx > 1024 || nx < 64 || kx > nx || nx > ny) return MVSIM_OK;
+    const int px = pl.px, py = pl.py, M = pl.M, hxp = pl.hxp;
+    if (!rot_fftx_len_ok(M)) return MVSIM_OK;
     // auto: from two waves per SIMD of columns up (below that the kernel is a handful of serial waves, like its parent)
     if (ctx->opt.fused_fftx == 2 && (int64_t)nx * nzl < 131072) return MVSIM_OK;
-    const int tile_y = lines_per_tile(py);
-    const int tw_max = tile_y > NLZ ? tile_y : NLZ;
-    const int hxp = ((M + 1 + tw_max - 1) / tw_max) * tw_max;
-    const int pyb = (py + ZB - 1) / ZB * ZB;
-    const size_t cbytes = (size_t)hxp * pyb * nzl * sizeof(float2);    // the size custom_fft_convolve_slab reserves
+    // the driver finds the spectrum in F and must not move it: it checks its own size against this one (ConvTail::x_done)
+    const size_t cbytes = pl.spectrum_bytes(nzl, 0, 0, 1);
     MVSIM_TRY(ctx->cfft_f.reserve(cbytes));
     MVSIM_TRY(ctx->cfft_g.reserve(cbytes));
     const float2 *tw_m, *tw_px;
@@ -1982,109 +1912,67 @@ int rotate_attenuate_fftx(mvsim_ctx* ctx, const float* gt, float* rot_or_null, f
     return MVSIM_OK;
 }
 
-int custom_fft_convolve(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const float* psf,
-                        const int64_t kdim[3], const int64_t P[3], float* out, ConvTail* tail)
+// ---------------------------------------------------------------------------------- the driver
+namespace fft {
+// What one call has settled before it enqueues anything, for the stages below.
+struct ConvRun {
+    const ConvPlan& pl;
+    SlabRange slab;                 // nz_in: planes the image spectrum holds when zdirect; nz_out: planes that leave the z pass
+    const LenEntry* xlen;           // the x passes' half length M
+    bool is_slab;
+    long long plane;                // elements of a plane of the plane-major spectrum: hxp * py
+    int V, zstride;                 // stacked views; passes D and E produce the planes k * zstride only
+    int nzp;                        // plane pitch of a view in the z pass's output: its planes k * zstride at multiples of zstride of the stacked index
+    int nk;                         // planes 0, zstride, 2 zstride, ... of every stacked view: what passes D and E see
+    int zs_chunk, zs_frows;         // k_zconv_strided's tile (chunk 0: this call keeps k_zconv)
+    size_t zs_lds;
+    bool zinline;                   // the z pass as FFT -> product -> inverse FFT per tile (CONVZ)
+    long long corr_n;               // adjustImage's factor rides in the reduction of the sum (0: not asked for)
+    float corr_min, corr_target;
+    const float2 *tw_m, *tw_px, *tw_py, *tw_pz;
+    float2 *F, *G, *G1, *G2;
+    double* scal;
+    const int *pnz, *pnz_dil;       // planes the fused rotate kernel found empty (null: no flags): raw, dilated by the taps' reach,
+    const unsigned int* pnz_bits;   // and as the z pass's bit string
+};
+
+// compact PSF intermediates: G1 [kz][ky][hxp] (x transformed), G2 [kz][py][hxp] (x,y transformed), G the full spectrum (FFT z pass only)
+static int psf_passes(mvsim_ctx* ctx, const ConvRun& r, const float* psf)
 {
-    const SlabRange whole{0, (int)dim[2], 0, (int)dim[2]};
-    return custom_fft_convolve_slab(ctx, img, dim, psf, kdim, P, whole, out, tail);
+    const ConvPlan& pl = r.pl;
+    const int kx = pl.k[0], ky = pl.k[1], kz = pl.k[2], hxp = pl.hxp, V = r.V;
+    SrcMap m{};
+    m.x = DimMap{kx, pl.px, kx - kx / 2, kx / 2, 1, kx / 2};   // embed along x with wrap-around
+    m.y = DimMap{ky, ky, ky, 0, 1, 0};                         // compact: identity
+    m.z = DimMap{kz * V, kz * V, kz * V, 0, 1, 0};             // (stacked PSFs: V x Kz planes of taps)
+    MVSIM_TRY(r.xlen->r2c(ctx, psf, m, r.G1, r.tw_m, r.tw_px, hxp, (long long)ky * kz * V));
+    LinesArgs a{};
+    a.src = r.G1; a.dst = r.G2; a.spec = nullptr; a.tw = r.tw_py;
+    a.src_es = hxp; a.src_outer = (long long)hxp * ky;          // per kz plane
+    a.dst_es = hxp; a.dst_outer = r.plane;
+    if (pl.zdirect) { a.dst_outer = (long long)ZB * hxp; a.dst_blk = (long long)kz * V * ZB * hxp; }   // the z pass reads its taps z-blocked
+    a.lmap = DimMap{ky, pl.py, ky - ky / 2, ky / 2, 1, ky / 2};
+    MVSIM_TRY(launch_lines(ctx, pl.py, FWD, true, a, hxp / pl.tile_y, kz * V));
+    if (pl.zdirect) return MVSIM_OK;
+    LinesArgs c{};
+    c.src = r.G2; c.dst = r.G; c.spec = nullptr; c.tw = r.tw_pz;
+    c.src_es = r.plane; c.src_outer = hxp;                         // per ky row
+    c.dst_es = r.plane; c.dst_outer = hxp;
+    c.lmap = DimMap{kz, pl.pz, kz - kz / 2, kz / 2, 1, kz / 2};
+    c.dst_tile_major = 1;                                         // consumed line by line in pass C
+    return launch_lines(ctx, pl.pz, FWD, true, c, hxp / pl.tile_z, pl.py);
 }
 
-int custom_fft_convolve_slab(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const float* psf,
-                             const int64_t kdim[3], const int64_t P[3], const SlabRange& slab, float* out, ConvTail* tail)
+// ---- PSF spectrum.  The embedded kernel is zero outside Kx*Ky*Kz taps, so the x pass runs on the
+//      Ky*Kz non-zero rows only, the y pass on the Kz non-zero planes only (sparse loads), and the z
+//      pass expands Kz planes to the full spectrum.
+// It depends on nothing the image passes A and B produce and is a handful of small launches, so it runs on the
+// context's side stream beside them (fork here, join before the z pass reads G2 / G: ctx->psf_on_side).
+// Only where it pays: the fork and the join cost ~10 us of cross-stream dependency, more than the spectrum of a small view.
+static int psf_spectrum(mvsim_ctx* ctx, const ConvRun& r, const float* psf)
 {
-    using namespace fft;
-    const bool is_slab = slab.nz_in != (int)dim[2] || slab.nz_out != (int)dim[2];
-    // stacked views (ConvTail::views = V > 1; the caller has asked custom_fft_batchable): `img` holds V attenuated volumes back to back,
-    // `psf` V PSFs, `out` receives V convolved volumes (compact planes: V x nk), the context's scalar pairs 0 .. V-1 the sums and factors.
-    // Passes A, B, D, E and the PSF's passes work on planes (rows) and simply see V x as many; the z pass carries the view in its grid.
-    const int V = (tail && tail->views > 1) ? tail->views : 1;
-    const int px = (int)P[0], py = (int)P[1], pz = (int)P[2];
-    const int kx = (int)kdim[0], ky = (int)kdim[1], kz = (int)kdim[2];
-    const int M = px / 2;
-    const int tile_y = lines_per_tile(py), tile_z = lines_per_tile(pz);
-    // z pass: direct convolution with the Kz taps (k_zconv) unless the PSF is deep or the FFT formulation is asked for
-    const bool zdirect = ctx->opt.zpass == 2 ? false : kz <= 64;
-    const bool early = zdirect && ctx->opt.early_sum;             // adjustImage's sum from pass C' instead of pass E
-    // with the sum known before passes D and E, they only have to produce the planes extractSlices reads
-    // (a z slab may ask for it too: its first output plane is then a multiple of the stride -- the caller's promise -- so that the planes
-    // k * zstride of the SLAB are planes k' * zstride of the view)
-    int zstride = (tail && early && tail->zstride > 1 && (!is_slab || slab.z_out0 % tail->zstride == 0)) ? tail->zstride : 1;
-    // fused tail: pass E adjusts, extracts and samples (needs the sum first, whole rows of float4 groups, aligned outputs)
-    long long fblocks = 0;
-    unsigned int fsegcap = 0;
-    bool fuse = tail && tail->want_fuse && early && !is_slab && tail->acq &&
-                fused_tail_geometry(dim, kdim, tail->inc, tail->con_adj != nullptr, ctx->opt, &fblocks, &fsegcap) &&
-                ((reinterpret_cast<uintptr_t>(tail->acq) | reinterpret_cast<uintptr_t>(tail->con_adj)) & 15) == 0;
-    if (fuse) zstride = tail->con_adj ? 1 : tail->inc;
-    if (tail) { tail->zstride = zstride; tail->fused = fuse; }
-    // adjustImage's factor rides in the reduction of the sum when the caller described it (a view; not the stage operator)
-    const long long corr_n = (tail && tail->corr_n > 0 && !is_slab) ? tail->corr_n : 0;
-    const float corr_min = tail ? tail->min_value : 0.f, corr_target = tail ? tail->target_average : 1.f;
-    if (tail) tail->corr_done = corr_n > 0;
-    if (is_slab && !zdirect) {
-        set_error("z-slab tiling needs the direct z pass (PSF depth %d > 64 or option fft_zpass=fft)", kz);
-        return MVSIM_EINVAL;
-    }
-    if (V > 1 && (is_slab || !zdirect || !early || fuse || (tail && (tail->x_done || tail->plane_nz)))) {
-        set_error("stacked views need the direct z pass with the early sum on whole views");
-        return MVSIM_EINVAL;
-    }
-    const int nzs = slab.nz_in;                                   // planes the image spectrum holds when zdirect
-    const int nzo = slab.nz_out;                                  // planes that leave the z pass
-    int tw_max = tile_y > tile_z ? tile_y : tile_z;
-    if (zdirect) tw_max = tile_y > NLZ ? tile_y : NLZ;
-    const int hxp = ((M + 1 + tw_max - 1) / tw_max) * tw_max;
-    const int pyb = (py + ZB - 1) / ZB * ZB;                        // rows of a plane in the z-blocked layout
-    const int nkv = (nzo - 1) / zstride + 1;                        // planes per view that leave passes D and E
-    const int nzp = V > 1 ? nkv * zstride : nzo;                    // plane pitch of a view in the z pass's output: the planes k * zstride of
-                                                                    // every view at multiples of zstride of the stacked index (pass D's stride)
-    const size_t cbytes = (size_t)hxp * (zdirect ? pyb : py) * (zdirect ? (size_t)V * std::max(nzs, nzp) : (size_t)pz) * sizeof(float2);
-    const long long rows_out_early = (long long)dim[1] * nzo * V;
-    MVSIM_TRY(ctx->cfft_f.reserve(cbytes));
-    MVSIM_TRY(ctx->cfft_g.reserve(cbytes));
-    // compact PSF intermediates: G1 [kz][ky][hxp] (x transformed), G2 [kz][py][hxp] (x,y transformed)
-    MVSIM_TRY(ctx->cfft_g1.reserve((size_t)V * hxp * ky * kz * sizeof(float2)));
-    MVSIM_TRY(ctx->cfft_g2.reserve((size_t)V * hxp * pyb * kz * sizeof(float2)));
-    MVSIM_TRY(ctx->partials.reserve(PARTIALS_BYTES));
-    MVSIM_TRY(ctx->partials_e.reserve((size_t)((rows_out_early + 3) / 4 + 16) * sizeof(double)));
-    double* scal = scal_of(ctx);
-
-    // the z pass on the unpadded spectrum as FFT -> product -> inverse FFT with the PSF's z spectrum computed per tile (CONVZ): from
-    // MVSIM_ZINLINE_MIN_KZ taps up the Kz-tap direct convolution is bound by its FMAs and this form by HBM (profiles/r04_zpass_sweep.txt)
-    // Measured, whole views with 31 x 31 x Kz PSFs (profiles/r04_zpass_sweep.txt): 2048 x 2048 x 512 (padded z length 576: tiles of 16
-    // lines, 128-byte rows) -- pass C 8.1 ms whatever Kz against 8.1 / 9.0 / 10.2 ms for the direct form at Kz = 41 / 51 / 63; 1024^3
-    // (length 1120: tiles of 8 lines, 64-byte rows, one line per wave) -- 5.6 ms against 3.9 / 4.4 / 4.9 ms.  Hence auto = deep PSFs on
-    // z lengths of 512 .. 576 (the sizes measured to win); everything else keeps the direct form unless asked.
-    // compact planes: the direct form computes 1 / zstride of the planes (k_zconv_strided) and is then ahead of the inline FFT at every depth
-    int zs_frows = 0;
-    size_t zs_lds = 0;
-    const int zs_chunk = (zdirect && zstride > 1 && ctx->opt.zconv_strided && ctx->opt.zpass != 3)
-                             ? zconv_strided_chunk(slab.nz_out, kz, zstride, (ctx->opt.exp & 2) != 0, &zs_frows, &zs_lds) : 0;
-    const bool zinline = zdirect && !is_slab && zs_chunk == 0 && V == 1 &&
-                         (ctx->opt.zpass == 3 || (ctx->opt.zpass == 0 && kz >= MVSIM_ZINLINE_MIN_KZ && pz >= 512 && lines_per_tile(pz) == 16));
-    const float2 *tw_m, *tw_px, *tw_py, *tw_pz;
-    MVSIM_TRY(ensure_twiddles(ctx, M, 0, &tw_m));
-    MVSIM_TRY(ensure_twiddles(ctx, px, 1, &tw_px));
-    MVSIM_TRY(ensure_twiddles(ctx, py, 0, &tw_py));
-    tw_pz = nullptr;
-    if (!zdirect || zinline) MVSIM_TRY(ensure_twiddles(ctx, pz, 0, &tw_pz));
-
-    float2* F = ctx->cfft_f.as<float2>();
-    float2* G = ctx->cfft_g.as<float2>();
-    float2* G1 = ctx->cfft_g1.as<float2>();
-    float2* G2 = ctx->cfft_g2.as<float2>();
     hipStream_t s = ctx->stream;
-    const long long rows_all = (long long)py * pz;
-    const long long plane = (long long)hxp * py;
-    const DimMap ident_none = DimMap{0, 0, 0, 0, 1, 0};
-
-    // ---- PSF spectrum G.  The embedded kernel is zero outside Kx*Ky*Kz taps, so the x pass runs on the
-    //      Ky*Kz non-zero rows only, the y pass on the Kz non-zero planes only (sparse loads), and the z
-    //      pass expands Kz planes to the full spectrum.
-    // It depends on nothing the image passes A and B produce and is a handful of small launches, so it runs on the
-    // context's side stream beside them (fork here, join before the z pass reads G2 / G).
-    // Only where it pays: the fork and the join cost ~10 us of cross-stream dependency, more than the spectrum of a small view.
-    const bool side = ctx->opt.psf_overlap && (int64_t)dim[0] * dim[1] * dim[2] >= (int64_t)1 << 24;
+    const bool side = ctx->opt.psf_overlap && (int64_t)r.pl.n[0] * r.pl.n[1] * r.pl.n[2] >= (int64_t)1 << 24;
     ctx->psf_on_side = side;
     if (side) {
         if (!ctx->side_stream) {
@@ -2096,234 +1984,334 @@ int custom_fft_convolve_slab(mvsim_ctx* ctx, const float* img, const int64_t dim
         MVSIM_HIP(hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
         ctx->stream = ctx->side_stream;                 // the launch helpers enqueue on ctx->stream
     }
-    int psf_rc = MVSIM_OK;
     ev_begin(ctx, ST_PSF);
-    do {
-        SrcMap m{};
-        m.x = DimMap{kx, px, kx - kx / 2, kx / 2, 1, kx / 2};   // embed along x with wrap-around
-        m.y = DimMap{ky, ky, ky, 0, 1, 0};                       // compact: identity
-        m.z = DimMap{kz * V, kz * V, kz * V, 0, 1, 0};             // (stacked PSFs: V x Kz planes of taps)
-        if ((psf_rc = launch_r2c(ctx, M, psf, m, G1, tw_m, tw_px, hxp, (long long)ky * kz * V)) != MVSIM_OK) break;
-        LinesArgs a{};
-        a.src = G1; a.dst = G2; a.spec = nullptr; a.tw = tw_py;
-        a.src_es = hxp; a.src_outer = (long long)hxp * ky;          // per kz plane
-        a.dst_es = hxp; a.dst_outer = plane;
-        if (zdirect) { a.dst_outer = (long long)ZB * hxp; a.dst_blk = (long long)kz * V * ZB * hxp; }   // the z pass reads its taps z-blocked
-        a.lmap = DimMap{ky, py, ky - ky / 2, ky / 2, 1, ky / 2};
-        if ((psf_rc = launch_lines(ctx, py, FWD, true, a, hxp / tile_y, kz * V)) != MVSIM_OK) break;
-        if (!zdirect) {
-            LinesArgs c{};
-            c.src = G2; c.dst = G; c.spec = nullptr; c.tw = tw_pz;
-            c.src_es = plane; c.src_outer = hxp;                         // per ky row
-            c.dst_es = plane; c.dst_outer = hxp;
-            c.lmap = DimMap{kz, pz, kz - kz / 2, kz / 2, 1, kz / 2};
-            c.dst_tile_major = 1;                                         // consumed line by line in pass C
-            psf_rc = launch_lines(ctx, pz, FWD, true, c, hxp / tile_z, py);
-        }
-    } while (false);
+    const int rc = psf_passes(ctx, r, psf);
     ev_end(ctx, ST_PSF);
     if (side) {
         // always joined, also after a failed launch: a stream capture must not end with the side stream dangling
         ctx->stream = s;
         MVSIM_HIP(hipEventRecord(ctx->ev_join, ctx->side_stream));
     }
-    MVSIM_TRY(psf_rc);
+    return rc;
+}
 
-    // ---- image: A, B, C (with product), D, E
-    ev_begin(ctx, ST_CONVOLVE);
-    {
-        SrcMap m{};
-        const int n[3] = {(int)dim[0], (int)dim[1], (int)dim[2]};
-        const int Pd[3] = {px, py, pz};
-        DimMap* dm[3] = {&m.x, &m.y, &m.z};
-        for (int d = 0; d < 3; ++d) {
-            const int c = (int)(kdim[d] / 2);
-            const int left = (int)(kdim[d] - 1 - kdim[d] / 2);
-            *dm[d] = DimMap{n[d], Pd[d], n[d] + c, left, 0, 0};
-        }
-        if (zdirect) m.z = DimMap{nzs * V, nzs * V, nzs * V, 0, 0, 0};   // no z padding: k_zconv mirrors through an index map
-        // direct z pass: the mirrored halo rows along y are copies of rows pass A transforms anyway, so it transforms the Ny
-        // rows of a plane only and pass B reads the halo positions from their mirror images (same bytes, from L2)
-        SrcMap ma = m;
-        const bool ymirror = zdirect && m.y.n > 1 && m.y.a - m.y.n < m.y.n && m.y.b < m.y.n;   // one reflection reaches every halo row
-        if (ymirror) { ma.y = DimMap{m.y.n, m.y.P, m.y.n, 0, 0, 0}; ma.enum_y = m.y.n; }   // and visits no other row
-        if (tail && tail->x_done) {
-            // the fused rotate + attenuate + x transform has left the spectrum of the attenuated rows in F already
-            // (a slab's fused kernel has computed its nz_in input planes -- the slab and its halo -- and left them in F from plane 0)
-            if (!(zdirect && ymirror) || V != 1) { set_error("x_done without the geometry of the fused x transform"); return MVSIM_EINVAL; }
-        } else {
-            ev_begin(ctx, ST_PASS_A);
-            MVSIM_TRY(launch_r2c(ctx, M, img, ma, F, tw_m, tw_px, hxp, zdirect ? (long long)(ymirror ? m.y.n : py) * nzs * V : rows_all));
-            ev_end(ctx, ST_PASS_A);
-        }
-        // zero gap of the padded volume: y in [Ny + cy, Py - lefty), z in [Nz + cz, Pz - leftz).  Pass A does not
-        // transform (or write) rows there, pass B skips the gap planes and does not load gap rows, pass C does
-        // not load gap planes.
-        const int ygap_lo = m.y.a, ygap_hi = py - m.y.b, zgap_lo = m.z.a, zgap_hi = pz - m.z.b;
-        LinesArgs b{};
-        b.src = F; b.dst = F; b.tw = tw_py; b.src_es = b.dst_es = hxp; b.src_outer = b.dst_outer = plane;
-        b.lmap = ident_none;
-        if (ymirror) { b.lmap = m.y; b.src_mirror = 1; }
-        b.gap_lo = ygap_lo; b.gap_hi = ygap_hi;
-        b.outer_skip_lo = zgap_lo; b.outer_skip_len = zgap_hi > zgap_lo ? zgap_hi - zgap_lo : 0;
-        if (zdirect) {
-            // out of place into the z-blocked layout the z pass reads and writes: G[(ky >> ZBS)][z][ky & (ZB-1)][kx]
-            b.outer_skip_lo = 1 << 30; b.outer_skip_len = 0;
-            b.dst = G; b.dst_outer = (long long)ZB * hxp; b.dst_blk = (long long)nzs * V * ZB * hxp;
-        }
-        float2* Fz = F;                                               // where passes D and E find the z-convolved spectrum
-        const int* em_flags = nullptr;                                // planes passes D and E skip (see pnz below)
-        const int nzd = zdirect ? nzo : (int)dim[2];                  // planes z >= Nz are never read
-        const int nk = ((nzd - 1) / zstride + 1) * V;                 // planes 0, zstride, 2 zstride, ... (of every stacked view)
-        {
-        // planes the fused rotate kernel found empty: B skips them, C' does not load them and skips tiles made of nothing else, D and E
-        // skip the planes whose taps reach nothing but empty planes (exact: their spectra are zero) -- a specimen in empty space
-        const int* pnz = (tail && tail->x_done && tail->plane_nz && zdirect && !zinline && !is_slab && !fuse)
-                             ? tail->plane_nz : nullptr;
-        const int* pnz_dil = nullptr;
-        const unsigned int* pnz_bits = nullptr;
-        if (pnz) {
-            // ctx->plane_flags = [flags (nz)][dilated (nz)][bit string (nwords)] (rotate_attenuate_fftx reserves all three)
-            int* base = ctx->plane_flags.as<int>();
-            const int nwords = ((int)dim[2] + 2 * NZ_EXT + 64 + 31) / 32 + ZNIT + 2;
-            // one block, ~9 us: beside pass B on the side stream when there is one (pass B reads the raw flags; the bit string and the
-            // dilated flags are for passes C', D and E, behind the join)
-            hipLaunchKernelGGL(k_plane_flags_finish, dim3(1), dim3(1024), 0, side ? ctx->side_stream : s, pnz, (int)dim[2], kz, kz / 2,
-                               reinterpret_cast<unsigned int*>(base + 2 * dim[2]), nwords, base + dim[2], ctx->empty_hint);
-            MVSIM_HIP(hipGetLastError());
-            if (side) MVSIM_HIP(hipEventRecord(ctx->ev_join, ctx->side_stream));
-            pnz_dil = base + dim[2];
-            pnz_bits = reinterpret_cast<const unsigned int*>(base + 2 * dim[2]);
-            b.nzflags = pnz; b.nz_stride = 1;
-        }
-        ev_begin(ctx, ST_PASS_B);
-        MVSIM_TRY(launch_lines(ctx, py, FWD, false, b, hxp / tile_y, zdirect ? nzs * V : pz - b.outer_skip_len));
-        ev_end(ctx, ST_PASS_B);
-        b.lmap = ident_none; b.src_mirror = 0;
-        if (side) MVSIM_HIP(hipStreamWaitEvent(s, ctx->ev_join, 0));    // the z pass reads the PSF spectrum
-        ev_begin(ctx, ST_PASS_C);
-        b.gap_lo = b.gap_hi = 0; b.outer_skip_lo = 1 << 30; b.outer_skip_len = 0;
-        if (zinline) {
-            LinesArgs c{};
-            c.src = G; c.dst = F; c.tw = tw_pz;
-            c.src_es = c.dst_es = (long long)ZB * hxp; c.src_outer = c.dst_outer = hxp;
-            c.src_oblk = (long long)nzs * ZB * hxp; c.dst_oblk = (long long)nzo * ZB * hxp;
-            c.lmap = DimMap{(int)dim[2], pz, (int)dim[2] + kz / 2, kz - 1 - kz / 2, 0, 0};
-            c.src_mirror = 1;
-            c.gap_lo = (int)dim[2] + kz / 2; c.gap_hi = pz - (kz - 1 - kz / 2);
-            c.outer_skip_lo = 1 << 30;
-            c.store_limit = (int)dim[2];
-            c.taps = G2; c.taps_es = (long long)ZB * hxp; c.taps_outer = hxp; c.taps_oblk = (long long)kz * ZB * hxp;
-            c.pmap = DimMap{kz, pz, kz - kz / 2, kz / 2, 1, kz / 2};
-            const float scale_f = (float)(0.25 / ((double)px * (double)py * (double)pz));
-            const long long zblocks = (long long)(hxp / tile_z) * py;
-            if (early) {
-                MVSIM_TRY(ensure_box_weights(ctx, (int)dim[0], px, hxp, true, &c.wx));
-                MVSIM_TRY(ensure_box_weights(ctx, (int)dim[1], py, py, false, &c.wy));
-                MVSIM_TRY(ctx->partials_z.reserve((size_t)zblocks * sizeof(double)));
-                c.sum_partial = ctx->partials_z.as<double>();
-            }
-            MVSIM_TRY(launch_lines(ctx, pz, CONVZ, false, c, hxp / tile_z, py));
-            if (early) {
-                hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, s, c.sum_partial, zblocks, scal, (double)scale_f,
-                                   corr_n, corr_min, corr_target);
-                MVSIM_HIP(hipGetLastError());
-            }
-            Fz = G;
-        } else if (zdirect) {
-            ZConvArgs z{};
-            z.src = G; z.dst = F; z.taps = G2; z.hxp = hxp; z.nz = nzo; z.kz = kz; z.c = kz / 2;
-            z.zs = (long long)ZB * hxp; z.src_blk = (long long)nzs * V * ZB * hxp; z.dst_blk = (long long)nzp * V * ZB * hxp;
-            z.taps_blk = (long long)kz * V * ZB * hxp;
-            z.src_view = (long long)nzs * z.zs; z.dst_view = (long long)nzp * z.zs; z.taps_view = (long long)kz * z.zs;
-            z.nz_global = (int)dim[2]; z.z_in0 = slab.z_in0; z.z_out0 = slab.z_out0;
-            z.zc = zs_chunk > 0 ? zs_chunk : zconv_chunk(nzo, kz);
-            z.stride = zs_chunk > 0 ? zstride : 1; z.frows = zs_frows;
-            z.nzbits = pnz_bits;
-            const float scale_f = (float)(0.25 / ((double)px * (double)py));
-            long long zblocks = 0;
-            if (early) {
-                MVSIM_TRY(ensure_box_weights(ctx, (int)dim[0], px, hxp, true, &z.wx));
-                MVSIM_TRY(ensure_box_weights(ctx, (int)dim[1], py, py, false, &z.wy));
-                zblocks = zconv_blocks(z, py);
-                MVSIM_TRY(ctx->partials_z.reserve((size_t)zblocks * V * sizeof(double)));
-                z.sum_partial = ctx->partials_z.as<double>();
-            }
-            if (zs_chunk > 0) MVSIM_TRY(launch_zconv_strided(ctx, z, py, zs_lds, V));
-            else MVSIM_TRY(launch_zconv(ctx, z, py, V));
-            if (early) {
-                // same factor pass E applies to every voxel (a float), so that the two sums estimate the same quantity
-                hipLaunchKernelGGL(k_reduce_partials, dim3(V), dim3(1024), 0, s, z.sum_partial, zblocks, scal, (double)scale_f,
-                                   corr_n, corr_min, corr_target);
-                MVSIM_HIP(hipGetLastError());
-            }
-            Fz = G;                                                   // pass D: F (z-blocked) -> G (plane-major), out of place
-        } else {
-        LinesArgs c{};
-        c.src = F; c.dst = F; c.spec = G; c.tw = tw_pz;
-        c.src_es = c.dst_es = c.spec_es = plane; c.src_outer = c.dst_outer = c.spec_outer = hxp;
-        c.lmap = ident_none;
-        c.gap_lo = zgap_lo; c.gap_hi = zgap_hi;
-        c.outer_skip_lo = 1 << 30;
-        c.store_limit = (int)dim[2];                                  // pass D only reads planes z < Nz
-        MVSIM_TRY(launch_lines(ctx, pz, CONV, false, c, hxp / tile_z, py));
-        }
-        ev_end(ctx, ST_PASS_C);
-        b.src = b.dst = Fz;
-        b.tw = tw_py;
-        b.store_limit = (int)dim[1];                                  // pass E only reads rows y < Ny
-        b.src_outer = b.dst_outer = plane * zstride;
-        b.dst_blk = 0;
-        if (zdirect) { b.src = F; b.src_outer = (long long)ZB * hxp * zstride; b.src_blk = (long long)nzp * V * ZB * hxp; }
-        b.nzflags = nullptr;
-        if (pnz) { b.nzflags = pnz_dil; b.nz_stride = zstride; em_flags = pnz_dil; }
-        ev_begin(ctx, ST_PASS_D);
-        MVSIM_TRY(launch_lines(ctx, py, INV, false, b, hxp / tile_y, nk));
-        ev_end(ctx, ST_PASS_D);
-        b.nzflags = nullptr;
-        }
-        C2RFuse fz{};
-        if (fuse) {
-            // adjustImage's factor must exist before pass E runs: (target - min) / (sum / n) from the early sum
-            if (!tail->corr_done) {
-                ev_begin(ctx, ST_ADJUST);
-                MVSIM_TRY(launch_adjust_corr(s, scal, (int64_t)dim[0] * dim[1] * dim[2], tail->min_value, tail->target_average));
-                ev_end(ctx, ST_ADJUST);
-            }
-            fz.scal = scal; fz.min_value = tail->min_value; fz.con = tail->con_adj; fz.acq = tail->acq;
-            fz.acq_every = tail->con_adj ? tail->inc : 1; fz.idx_zstride = zstride; fz.noise = tail->noise ? 1 : 0;
-            fz.mul = tail->mul; fz.k0 = (uint32_t)tail->seed; fz.k1 = (uint32_t)(tail->seed >> 32); fz.stream = tail->stream;
-            if (tail->noise) {
-                const size_t counts = ((size_t)QCOUNT_WORDS * fblocks * sizeof(unsigned int) + 255) & ~(size_t)255;
-                if (ctx->pqueue.bytes < counts + (size_t)fblocks * fsegcap * sizeof(PItem)) {
-                    set_error("fused tail: queue workspace not reserved");
-                    return MVSIM_EINVAL;
-                }
-                fz.qcount = ctx->pqueue.as<unsigned int>();
-                fz.queue = reinterpret_cast<PItem*>(ctx->pqueue.as<char>() + counts);
-                fz.segcap = fsegcap;
-            }
-        }
-        ev_begin(ctx, ST_PASS_E);
-        // both half spectra carry the factor 2 left in by pass A (see k_fft_x_r2c): 2 * 2 = 4
-        const float scale = (float)(0.25 / ((double)px * (double)py * ((zdirect && !zinline) ? 1.0 : (double)pz)));
-        int nblk = 0;
-        MVSIM_TRY(launch_c2r(ctx, M, Fz, out, tw_m, tw_px, hxp, py * zstride, (int)dim[0], (int)dim[1], (long long)dim[1] * nk, scale,
-                             early ? nullptr : ctx->partials_e.as<double>(), &nblk, fuse ? &fz : nullptr,
-                             C2REmpty{em_flags, zstride}));
-        if (fuse && nblk != (int)fblocks) { set_error("fused tail: block count mismatch"); return MVSIM_EINVAL; }
-        if (!early) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, s, ctx->partials_e.as<double>(), (long long)nblk, scal, 1.0,
-                                       corr_n, corr_min, corr_target);
+// Pass A.  Direct z pass: no z padding (k_zconv mirrors through an index map), and the mirrored halo rows along y are copies of rows
+// pass A transforms anyway, so it transforms the Ny rows of a r.plane only and pass B reads the halo positions from their mirror
+// images (same bytes, from L2).
+static int pass_a(mvsim_ctx* ctx, const ConvRun& r, const float* img)
+{
+    const ConvPlan& pl = r.pl;
+    const int planes = r.slab.nz_in * r.V;
+    SrcMap m{};
+    DimMap* dm[3] = {&m.x, &m.y, &m.z};
+    for (int d = 0; d < 3; ++d) *dm[d] = DimMap{pl.n[d], (int)pl.P[d], pl.n[d] + pl.k[d] / 2, pl.k[d] - 1 - pl.k[d] / 2, 0, 0};
+    if (pl.zdirect) m.z = DimMap{planes, planes, planes, 0, 0, 0};
+    if (pl.ymirror) { m.y = DimMap{pl.n[1], pl.py, pl.n[1], 0, 0, 0}; m.enum_y = pl.n[1]; }   // ... and visits no other row
+    const long long rows = pl.zdirect ? (long long)(pl.ymirror ? pl.n[1] : pl.py) * planes : (long long)pl.py * pl.pz;
+    ev_begin(ctx, ST_PASS_A);
+    MVSIM_TRY(r.xlen->r2c(ctx, img, m, r.F, r.tw_m, r.tw_px, pl.hxp, rows));
+    ev_end(ctx, ST_PASS_A);
+    return MVSIM_OK;
+}
+
+// Planes the fused rotate kernel found empty: B skips them, C' does not load them and skips tiles made of nothing else, D and E
+// skip the planes whose taps reach nothing but empty planes (exact: their spectra are zero) -- a specimen in empty space.
+// ctx->plane_flags = [flags (nz)][dilated (nz)][bit string (nwords)] (rotate_attenuate_fftx reserves all three)
+static int plane_flags_setup(mvsim_ctx* ctx, ConvRun& r, const int* pnz)
+{
+    const int nz = r.pl.n[2], kz = r.pl.k[2];
+    int* base = ctx->plane_flags.as<int>();
+    const int nwords = (nz + 2 * NZ_EXT + 64 + 31) / 32 + ZNIT + 2;
+    // one block, ~9 us: beside pass B on the side stream when there is one (pass B reads the raw flags; the bit string and the
+    // dilated flags are for passes C', D and E, behind the join)
+    const bool side = ctx->psf_on_side;
+    hipLaunchKernelGGL(k_plane_flags_finish, dim3(1), dim3(1024), 0, side ? ctx->side_stream : ctx->stream, pnz, nz, kz, kz / 2,
+                       reinterpret_cast<unsigned int*>(base + 2 * nz), nwords, base + nz, ctx->empty_hint);
+    MVSIM_HIP(hipGetLastError());
+    if (side) MVSIM_HIP(hipEventRecord(ctx->ev_join, ctx->side_stream));
+    r.pnz = pnz;
+    r.pnz_dil = base + nz;
+    r.pnz_bits = reinterpret_cast<const unsigned int*>(base + 2 * nz);
+    return MVSIM_OK;
+}
+
+// Pass B: F -> F in place, or (direct z pass) out of place into the z-blocked layout the z pass reads and writes:
+// G[(ky >> ZBS)][z][ky & (ZB-1)][kx].
+// Zero gap of the padded volume: y in [Ny + cy, Py - lefty), z in [Nz + cz, Pz - leftz).  Pass A does not transform (or write) rows
+// there, pass B skips the gap planes and does not load gap rows, pass C does not load gap planes.
+static int pass_b(mvsim_ctx* ctx, const ConvRun& r)
+{
+    const ConvPlan& pl = r.pl;
+    const int hxp = pl.hxp, ny = pl.n[1], ky = pl.k[1], kz = pl.k[2];
+    LinesArgs b{};
+    b.src = r.F; b.dst = r.F; b.tw = r.tw_py; b.src_es = b.dst_es = hxp; b.src_outer = b.dst_outer = r.plane;
+    b.lmap = DimMap{0, 0, 0, 0, 1, 0};
+    if (pl.ymirror) { b.lmap = DimMap{ny, pl.py, ny + ky / 2, ky - 1 - ky / 2, 0, 0}; b.src_mirror = 1; }
+    b.gap_lo = ny + ky / 2; b.gap_hi = pl.py - (ky - 1 - ky / 2);
+    if (pl.zdirect) {
+        b.outer_skip_lo = 1 << 30;
+        b.dst = r.G; b.dst_outer = (long long)ZB * hxp; b.dst_blk = (long long)r.slab.nz_in * r.V * ZB * hxp;
+    } else {
+        b.outer_skip_lo = pl.n[2] + kz / 2;
+        b.outer_skip_len = std::max(0, pl.pz - (kz - 1 - kz / 2) - b.outer_skip_lo);
+    }
+    if (r.pnz) { b.nzflags = r.pnz; b.nz_stride = 1; }
+    ev_begin(ctx, ST_PASS_B);
+    MVSIM_TRY(launch_lines(ctx, pl.py, FWD, false, b, hxp / pl.tile_y, pl.zdirect ? r.slab.nz_in * r.V : pl.pz - b.outer_skip_len));
+    ev_end(ctx, ST_PASS_B);
+    return MVSIM_OK;
+}
+
+// The z pass on the unpadded spectrum as FFT -> product -> inverse FFT with the PSF's z spectrum computed per tile (CONVZ): from
+// MVSIM_ZINLINE_MIN_KZ taps up the Kz-tap direct convolution is bound by its FMAs and this form by HBM.
+// Measured, whole views with 31 x 31 x Kz PSFs (profiles/r04_zpass_sweep.txt): 2048 x 2048 x 512 (padded z length 576: tiles of 16
+// lines, 128-byte rows) -- pass C 8.1 ms whatever Kz against 8.1 / 9.0 / 10.2 ms for the direct form at Kz = 41 / 51 / 63; 1024^3
+// (length 1120: tiles of 8 lines, 64-byte rows, one line per wave) -- 5.6 ms against 3.9 / 4.4 / 4.9 ms.  Hence auto = deep PSFs on
+// z lengths of 512 .. 576 (the sizes measured to win; ConvPlan::zinline_auto); everything else keeps the direct form unless asked.
+// Compact planes: the direct form computes 1 / zstride of the planes (k_zconv_strided) and is then ahead of this one at every depth.
+// G (z-blocked) -> F (z-blocked).
+static int zpass_inline(mvsim_ctx* ctx, const ConvRun& r)
+{
+    const ConvPlan& pl = r.pl;
+    const int nz = pl.n[2], kz = pl.k[2], pz = pl.pz, hxp = pl.hxp;
+    LinesArgs c{};
+    c.src = r.G; c.dst = r.F; c.tw = r.tw_pz;
+    c.src_es = c.dst_es = (long long)ZB * hxp; c.src_outer = c.dst_outer = hxp;
+    c.src_oblk = (long long)r.slab.nz_in * ZB * hxp; c.dst_oblk = (long long)r.slab.nz_out * ZB * hxp;
+    c.lmap = DimMap{nz, pz, nz + kz / 2, kz - 1 - kz / 2, 0, 0};
+    c.src_mirror = 1;
+    c.gap_lo = nz + kz / 2; c.gap_hi = pz - (kz - 1 - kz / 2);
+    c.outer_skip_lo = 1 << 30;
+    c.store_limit = nz;
+    c.taps = r.G2; c.taps_es = (long long)ZB * hxp; c.taps_outer = hxp; c.taps_oblk = (long long)kz * ZB * hxp;
+    c.pmap = DimMap{kz, pz, kz - kz / 2, kz / 2, 1, kz / 2};
+    const float scale_f = (float)(0.25 / ((double)pl.px * (double)pl.py * (double)pz));
+    const long long zblocks = (long long)(hxp / pl.tile_z) * pl.py;
+    if (pl.early) {
+        MVSIM_TRY(ensure_box_weights(ctx, pl.n[0], pl.px, hxp, true, &c.wx));
+        MVSIM_TRY(ensure_box_weights(ctx, pl.n[1], pl.py, pl.py, false, &c.wy));
+        MVSIM_TRY(ctx->partials_z.reserve((size_t)zblocks * sizeof(double)));
+        c.sum_partial = ctx->partials_z.as<double>();
+    }
+    MVSIM_TRY(launch_lines(ctx, pz, CONVZ, false, c, hxp / pl.tile_z, pl.py));
+    if (pl.early) {
+        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, ctx->stream, c.sum_partial, zblocks, r.scal, (double)scale_f,
+                           r.corr_n, r.corr_min, r.corr_target);
         MVSIM_HIP(hipGetLastError());
-        ev_end(ctx, ST_PASS_E);
-        if (fuse && tail->noise) {
-            ev_end(ctx, ST_CONVOLVE);
-            ev_begin(ctx, ST_EXTRACT);
-            MVSIM_TRY(launch_poisson_resolve(s, tail->acq, fz.queue, fz.qcount, (int)fblocks, fsegcap, tail->mul, tail->seed, tail->stream,
-                                             (long long)dim[0] * dim[1], fz.acq_every * fz.idx_zstride, 0));
-            ev_end(ctx, ST_EXTRACT);
-            return MVSIM_OK;
+    }
+    return MVSIM_OK;
+}
+
+// The direct z pass, every r.plane (k_zconv) or the planes k * zstride only (k_zconv_strided): G (z-blocked) -> F (z-blocked)
+static int zpass_direct(mvsim_ctx* ctx, const ConvRun& r)
+{
+    const ConvPlan& pl = r.pl;
+    const int kz = pl.k[2], hxp = pl.hxp, V = r.V;
+    ZConvArgs z{};
+    z.src = r.G; z.dst = r.F; z.taps = r.G2; z.hxp = hxp; z.nz = r.slab.nz_out; z.kz = kz; z.c = kz / 2;
+    z.zs = (long long)ZB * hxp; z.src_blk = (long long)r.slab.nz_in * V * ZB * hxp; z.dst_blk = (long long)r.nzp * V * ZB * hxp;
+    z.taps_blk = (long long)kz * V * ZB * hxp;
+    z.src_view = (long long)r.slab.nz_in * z.zs; z.dst_view = (long long)r.nzp * z.zs; z.taps_view = (long long)kz * z.zs;
+    z.nz_global = pl.n[2]; z.z_in0 = r.slab.z_in0; z.z_out0 = r.slab.z_out0;
+    z.zc = r.zs_chunk > 0 ? r.zs_chunk : zconv_chunk(r.slab.nz_out, kz);
+    z.stride = r.zs_chunk > 0 ? r.zstride : 1; z.frows = r.zs_frows;
+    z.nzbits = r.pnz_bits;
+    const float scale_f = (float)(0.25 / ((double)pl.px * (double)pl.py));
+    long long zblocks = 0;
+    if (pl.early) {
+        MVSIM_TRY(ensure_box_weights(ctx, pl.n[0], pl.px, hxp, true, &z.wx));
+        MVSIM_TRY(ensure_box_weights(ctx, pl.n[1], pl.py, pl.py, false, &z.wy));
+        zblocks = zconv_blocks(z, pl.py);
+        MVSIM_TRY(ctx->partials_z.reserve((size_t)zblocks * V * sizeof(double)));
+        z.sum_partial = ctx->partials_z.as<double>();
+    }
+    if (r.zs_chunk > 0) MVSIM_TRY(launch_zconv_strided(ctx, z, pl.py, r.zs_lds, V));
+    else MVSIM_TRY(launch_zconv(ctx, z, pl.py, V));
+    if (pl.early) {
+        // same factor pass E applies to every voxel (a float), so that the two sums estimate the same quantity
+        hipLaunchKernelGGL(k_reduce_partials, dim3(V), dim3(1024), 0, ctx->stream, z.sum_partial, zblocks, r.scal, (double)scale_f,
+                           r.corr_n, r.corr_min, r.corr_target);
+        MVSIM_HIP(hipGetLastError());
+    }
+    return MVSIM_OK;
+}
+
+// The z pass on the z-padded spectrum: FFT, product with the PSF's spectrum G, inverse FFT, in place in F
+static int zpass_fft(mvsim_ctx* ctx, const ConvRun& r)
+{
+    const ConvPlan& pl = r.pl;
+    const int nz = pl.n[2], kz = pl.k[2], hxp = pl.hxp;
+    LinesArgs c{};
+    c.src = r.F; c.dst = r.F; c.spec = r.G; c.tw = r.tw_pz;
+    c.src_es = c.dst_es = c.spec_es = r.plane; c.src_outer = c.dst_outer = c.spec_outer = hxp;
+    c.lmap = DimMap{0, 0, 0, 0, 1, 0};
+    c.gap_lo = nz + kz / 2; c.gap_hi = pl.pz - (kz - 1 - kz / 2);
+    c.outer_skip_lo = 1 << 30;
+    c.store_limit = nz;                                           // pass D only reads planes z < Nz
+    return launch_lines(ctx, pl.pz, CONV, false, c, hxp / pl.tile_z, pl.py);
+}
+
+// Pass D: the planes k * zstride, from F (z-blocked after a direct or inline z pass) into `dst` (plane-major)
+static int pass_d(mvsim_ctx* ctx, const ConvRun& r, float2* dst)
+{
+    const ConvPlan& pl = r.pl;
+    const int hxp = pl.hxp;
+    LinesArgs d{};
+    d.src = r.F; d.dst = dst; d.tw = r.tw_py; d.src_es = d.dst_es = hxp;
+    d.src_outer = d.dst_outer = r.plane * r.zstride;
+    if (pl.zdirect) { d.src_outer = (long long)ZB * hxp * r.zstride; d.src_blk = (long long)r.nzp * r.V * ZB * hxp; }
+    d.lmap = DimMap{0, 0, 0, 0, 1, 0};
+    d.outer_skip_lo = 1 << 30;
+    d.store_limit = pl.n[1];                                      // pass E only reads rows y < Ny
+    if (r.pnz) { d.nzflags = r.pnz_dil; d.nz_stride = r.zstride; }
+    ev_begin(ctx, ST_PASS_D);
+    MVSIM_TRY(launch_lines(ctx, pl.py, INV, false, d, hxp / pl.tile_y, r.nk));
+    ev_end(ctx, ST_PASS_D);
+    return MVSIM_OK;
+}
+
+// Fused tail: what pass E needs to adjust, extract and sample.  adjustImage's factor must exist before pass E runs:
+// (target - min) / (sum / n) from the early sum.
+static int fused_tail_args(mvsim_ctx* ctx, const ConvRun& r, const ConvTail& tail, long long fblocks, unsigned int fsegcap, C2RFuse* fz)
+{
+    if (!tail.corr_done) {
+        ev_begin(ctx, ST_ADJUST);
+        MVSIM_TRY(launch_adjust_corr(ctx->stream, r.scal, (int64_t)r.pl.n[0] * r.pl.n[1] * r.pl.n[2], tail.min_value, tail.target_average));
+        ev_end(ctx, ST_ADJUST);
+    }
+    fz->scal = r.scal; fz->min_value = tail.min_value; fz->con = tail.con_adj; fz->acq = tail.acq;
+    fz->acq_every = tail.con_adj ? tail.inc : 1; fz->idx_zstride = r.zstride; fz->noise = tail.noise ? 1 : 0;
+    fz->mul = tail.mul; fz->k0 = (uint32_t)tail.seed; fz->k1 = (uint32_t)(tail.seed >> 32); fz->stream = tail.stream;
+    if (tail.noise) {
+        const size_t counts = ((size_t)QCOUNT_WORDS * fblocks * sizeof(unsigned int) + 255) & ~(size_t)255;
+        if (ctx->pqueue.bytes < counts + (size_t)fblocks * fsegcap * sizeof(PItem)) {
+            set_error("fused tail: queue workspace not reserved");
+            return MVSIM_EINVAL;
         }
+        fz->qcount = ctx->pqueue.as<unsigned int>();
+        fz->queue = reinterpret_cast<PItem*>(ctx->pqueue.as<char>() + counts);
+        fz->segcap = fsegcap;
+    }
+    return MVSIM_OK;
+}
+}  // namespace fft
+
+int custom_fft_convolve(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const float* psf,
+                        const int64_t kdim[3], float* out, ConvTail* tail)
+{
+    const SlabRange whole{0, (int)dim[2], 0, (int)dim[2]};
+    return custom_fft_convolve_slab(ctx, img, dim, psf, kdim, whole, out, tail);
+}
+
+// Decide; PSF spectrum; image: A, B, C (with product), D, E.
+int custom_fft_convolve_slab(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const float* psf,
+                             const int64_t kdim[3], const SlabRange& slab, float* out, ConvTail* tail)
+{
+    using namespace fft;
+    ConvPlan pl;
+    if (!conv_plan(dim, kdim, ctx->opt, &pl)) { set_error("custom FFT: no hand-written size for this volume / PSF"); return MVSIM_EINVAL; }
+    const Options& o = ctx->opt;
+    const int kz = pl.k[2];
+    ConvRun r{pl, slab, find_len(pl.M)};
+    r.plane = (long long)pl.hxp * pl.py;
+    r.is_slab = slab.nz_in != pl.n[2] || slab.nz_out != pl.n[2];
+    // stacked views (ConvTail::views = V > 1; the caller has asked custom_fft_batchable): `img` holds V attenuated volumes back to back,
+    // `psf` V PSFs, `out` receives V convolved volumes (compact planes: V x nk), the context's scalar pairs 0 .. V-1 the sums and factors.
+    // Passes A, B, D, E and the PSF's passes work on planes (rows) and simply see V x as many; the z pass carries the view in its grid.
+    r.V = (tail && tail->views > 1) ? tail->views : 1;
+    // with the sum known before passes D and E (early), they only have to produce the planes extractSlices reads
+    // (a z slab may ask for it too: its first output plane is then a multiple of the stride -- the caller's promise -- so that the planes
+    // k * zstride of the SLAB are planes k' * zstride of the view)
+    r.zstride = (tail && pl.early && tail->zstride > 1 && (!r.is_slab || slab.z_out0 % tail->zstride == 0)) ? tail->zstride : 1;
+    // fused tail: pass E adjusts, extracts and samples (needs the sum first, whole rows of float4 groups, aligned outputs)
+    long long fblocks = 0;
+    unsigned int fsegcap = 0;
+    const bool fuse = tail && tail->want_fuse && !r.is_slab && tail->acq &&
+                      fused_tail_of(pl, tail->inc, tail->con_adj != nullptr, &fblocks, &fsegcap) &&
+                      ((reinterpret_cast<uintptr_t>(tail->acq) | reinterpret_cast<uintptr_t>(tail->con_adj)) & 15) == 0;
+    if (fuse) r.zstride = tail->con_adj ? 1 : tail->inc;
+    if (tail) { tail->zstride = r.zstride; tail->fused = fuse; }
+    // adjustImage's factor rides in the reduction of the sum when the caller described it (a view; not the stage operator)
+    r.corr_n = (tail && tail->corr_n > 0 && !r.is_slab) ? tail->corr_n : 0;
+    r.corr_min = tail ? tail->min_value : 0.f; r.corr_target = tail ? tail->target_average : 1.f;
+    if (tail) tail->corr_done = r.corr_n > 0;
+    const bool x_done = tail && tail->x_done;
+    if (r.is_slab && !pl.zdirect) {
+        set_error("z-slab tiling needs the direct z pass (PSF depth %d > 64 or option fft_zpass=fft)", kz);
+        return MVSIM_EINVAL;
+    }
+    if (r.V > 1 && (r.is_slab || !pl.early || fuse || x_done || tail->plane_nz)) {
+        set_error("stacked views need the direct z pass with the early sum on whole views");
+        return MVSIM_EINVAL;
+    }
+    const int nkv = (r.slab.nz_out - 1) / r.zstride + 1;            // planes per view that leave passes D and E
+    r.nzp = r.V > 1 ? nkv * r.zstride : r.slab.nz_out;
+    r.nk = nkv * r.V;                                               // (FFT z pass: whole views only, nzo = Nz; planes z >= Nz are never read)
+    const size_t cbytes = pl.spectrum_bytes(r.slab.nz_in, r.slab.nz_out, r.nzp, r.V);
+    const long long rows_out_early = (long long)pl.n[1] * r.slab.nz_out * r.V;
+    // the fused rotate + attenuate + x transform has left the spectrum of the attenuated rows in F already (a slab's: its nz_in input
+    // planes -- the slab and its halo -- from plane 0): F must stay where it is
+    if (x_done && cbytes > ctx->cfft_f.bytes) {
+        set_error("custom FFT: the spectrum needs %zu bytes, the fused x transform left it in %zu", cbytes, ctx->cfft_f.bytes);
+        return MVSIM_EINVAL;
+    }
+    if (!x_done) MVSIM_TRY(ctx->cfft_f.reserve(cbytes));
+    MVSIM_TRY(ctx->cfft_g.reserve(cbytes));
+    MVSIM_TRY(ctx->cfft_g1.reserve((size_t)r.V * pl.hxp * pl.k[1] * kz * sizeof(float2)));
+    MVSIM_TRY(ctx->cfft_g2.reserve((size_t)r.V * pl.hxp * pl.pyb * kz * sizeof(float2)));
+    MVSIM_TRY(ctx->partials.reserve(PARTIALS_BYTES));
+    MVSIM_TRY(ctx->partials_e.reserve((size_t)((rows_out_early + 3) / 4 + 16) * sizeof(double)));
+    r.scal = scal_of(ctx);
+    r.zs_chunk = (pl.zdirect && r.zstride > 1 && o.zconv_strided && o.zpass != 3)
+                     ? zconv_strided_chunk(slab.nz_out, kz, r.zstride, (o.exp & 2) != 0, &r.zs_frows, &r.zs_lds) : 0;
+    r.zinline = pl.zdirect && !r.is_slab && r.zs_chunk == 0 && r.V == 1 && (o.zpass == 3 || pl.zinline_auto);
+    MVSIM_TRY(ensure_twiddles(ctx, pl.M, 0, &r.tw_m));
+    MVSIM_TRY(ensure_twiddles(ctx, pl.px, 1, &r.tw_px));
+    MVSIM_TRY(ensure_twiddles(ctx, pl.py, 0, &r.tw_py));
+    if (!pl.zdirect || r.zinline) MVSIM_TRY(ensure_twiddles(ctx, pl.pz, 0, &r.tw_pz));
+    r.F = ctx->cfft_f.as<float2>(); r.G = ctx->cfft_g.as<float2>();
+    r.G1 = ctx->cfft_g1.as<float2>(); r.G2 = ctx->cfft_g2.as<float2>();
+    hipStream_t s = ctx->stream;
+
+    MVSIM_TRY(psf_spectrum(ctx, r, psf));
+
+    ev_begin(ctx, ST_CONVOLVE);
+    if (x_done) {
+        if (!pl.ymirror || r.V != 1) { set_error("x_done without the geometry of the fused x transform"); return MVSIM_EINVAL; }
+    } else {
+        MVSIM_TRY(pass_a(ctx, r, img));
+    }
+    if (x_done && tail->plane_nz && !r.zinline && !r.is_slab && !fuse) MVSIM_TRY(plane_flags_setup(ctx, r, tail->plane_nz));
+    MVSIM_TRY(pass_b(ctx, r));
+    if (ctx->psf_on_side) MVSIM_HIP(hipStreamWaitEvent(s, ctx->ev_join, 0));    // the z pass reads the PSF spectrum
+    ev_begin(ctx, ST_PASS_C);
+    if (r.zinline) MVSIM_TRY(zpass_inline(ctx, r));
+    else if (pl.zdirect) MVSIM_TRY(zpass_direct(ctx, r));
+    else MVSIM_TRY(zpass_fft(ctx, r));
+    ev_end(ctx, ST_PASS_C);
+    float2* Fz = pl.zdirect ? r.G : r.F;                            // where pass D leaves the z-convolved spectrum for pass E
+    MVSIM_TRY(pass_d(ctx, r, Fz));
+    C2RFuse fz{};
+    if (fuse) MVSIM_TRY(fused_tail_args(ctx, r, *tail, fblocks, fsegcap, &fz));
+    ev_begin(ctx, ST_PASS_E);
+    // both half spectra carry the factor 2 left in by pass A (see k_fft_x_r2c): 2 * 2 = 4
+    const float scale = (float)(0.25 / ((double)pl.px * (double)pl.py * ((pl.zdirect && !r.zinline) ? 1.0 : (double)pl.pz)));
+    int nblk = 0;
+    MVSIM_TRY(r.xlen->c2r(ctx, Fz, out, r.tw_m, r.tw_px, pl.hxp, pl.py * r.zstride, pl.n[0], pl.n[1], (long long)pl.n[1] * r.nk, scale,
+                         pl.early ? nullptr : ctx->partials_e.as<double>(), &nblk, fuse ? &fz : nullptr,
+                         C2REmpty{r.pnz_dil, r.zstride}));
+    if (fuse && nblk != (int)fblocks) { set_error("fused tail: block count mismatch"); return MVSIM_EINVAL; }
+    if (!pl.early) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, s, ctx->partials_e.as<double>(), (long long)nblk, r.scal, 1.0,
+                                      r.corr_n, r.corr_min, r.corr_target);
+    MVSIM_HIP(hipGetLastError());
+    ev_end(ctx, ST_PASS_E);
+    if (fuse && tail->noise) {
+        ev_end(ctx, ST_CONVOLVE);
+        ev_begin(ctx, ST_EXTRACT);
+        MVSIM_TRY(launch_poisson_resolve(s, tail->acq, fz.queue, fz.qcount, (int)fblocks, fsegcap, tail->mul, tail->seed, tail->stream,
+                                         (long long)pl.n[0] * pl.n[1], fz.acq_every * fz.idx_zstride, 0));
+        ev_end(ctx, ST_EXTRACT);
+        return MVSIM_OK;
     }
     ev_end(ctx, ST_CONVOLVE);
     return MVSIM_OK;

@@ -404,20 +404,6 @@ static int launch_rot_fftx_t(mvsim_ctx* ctx, const RotFftArgs& a, bool write_out
     return MVSIM_OK;
 }
 
-// half lengths the fused kernel is instantiated for (rows of up to 1024 voxels with PSFs of up to 64 taps); the plans --
-// radices and with them the layout of the twiddle table -- are the size table's own
-constexpr bool rot_fftx_len_ok(int len) { return len >= 72 && len <= 576; }
-
-bool rot_fftx_has_plan(int M)
-{
-    switch (M) {
-#define X(LL, ...) case LL: return rot_fftx_len_ok(LL);
-        MVSIM_FFT_SIZES(X)
-#undef X
-    }
-    return false;
-}
-
 template <int LL, int... Rs>
 static int launch_rot_fftx_pick(mvsim_ctx* ctx, const RotFftArgs& a, bool write_out)
 {

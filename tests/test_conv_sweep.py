@@ -7,8 +7,11 @@ Convolution cases are held to the oracle's exact fp64 direct sum on every voxel 
 the fused kernel bit for bit to the separate kernels.  The CPU tests check that the sweep's table is the library's, that the
 cases cover every instance, and that the inputs would expose the classic convolution mistakes."""
 import ctypes as C
+import json
 import os
 import re
+import subprocess
+import sys
 import zlib
 from collections import defaultdict
 
@@ -70,6 +73,54 @@ def test_stencil_geometry_restatement_matches_the_library(mvs):
     for kd in sorted(kdims):
         g = _stencil_geometry(mvs, kd)
         assert tuple(g[:3]) == S.stencil_geometry(kd), kd
+
+
+GEOMETRY_EDGES = (1, 2, 15, 16, 17, 63, 64, 512, 513, 576, 577, 1024, 1121, 2048, 2240, 2241, 4481)
+GEOMETRY_PSF_XY = (1, 31, 100)
+GEOMETRY_PSF_Z = (1, 47, 48, 64, 65, 100)          # around the inline z pass's first depth and the direct z pass's last
+
+
+def _geometry_sweep(mvs, zfft):
+    """(cases, cases without a hand-written size, mismatches) of mvsim_fft_geometry against the restatement of
+    conv_sweep_cases (pick, pick_x, hxp, lines_per_tile, NLZ): the cross product of the edge sizes and 20 000 seeded shapes."""
+    fn = mvs._lib.load().mvsim_fft_geometry
+    pick = {need: S.pick(need) for need in range(1, 4600)}
+    rng = np.random.default_rng(SEED)
+    rnd = np.concatenate([rng.integers(1, 2300, (20000, 3)), rng.integers(1, 101, (20000, 3))], axis=1).tolist()
+    edges = [(x, y, z, kx, ky, kz) for x in GEOMETRY_EDGES for y in GEOMETRY_EDGES for z in GEOMETRY_EDGES
+             for kx in GEOMETRY_PSF_XY for ky in GEOMETRY_PSF_XY for kz in GEOMETRY_PSF_Z]
+    dim, kdim, g = _i64([0] * 3), _i64([0] * 3), _i64([0] * 5)
+    none, bad = 0, []
+    for c in edges + rnd:
+        dim[:], kdim[:] = c[:3], c[3:]
+        got = list(g) if fn(dim, kdim, g) == 0 else None
+        m, py, pz = (pick[(c[0] + c[3]) // 2], pick[c[1] + c[4] - 1], pick[c[2] + c[5] - 1])      # pick_x: ceil((n + k - 1) / 2)
+        want = None
+        if m and py and pz:
+            zdirect = not zfft and c[5] <= 64
+            want = [2 * m, py, c[2] if zdirect else pz, S.hxp(2 * m, py, pz, zdirect), int(zdirect)]
+        none += want is None
+        if got != want and len(bad) < 10:
+            bad.append((c, got, want))
+    return len(edges) + len(rnd), none, bad
+
+
+def test_fft_geometry_matches_the_restatement(mvs):
+    """The plan of the hand-written convolution (conv_plan, read through mvsim_fft_geometry) against the sweep's restatement, with
+    the default options here and with MVSIM_FFT_ZPASS=fft in a child process (the environment is read once per process)."""
+    code = ("import importlib, json; from tests import test_conv_sweep as T; "
+            "print(json.dumps(T._geometry_sweep(importlib.import_module('multiview-simulation_amd'), True)))")
+    env = {k: v for k, v in os.environ.items() if not k.startswith("MVSIM_")}
+    child = subprocess.Popen([sys.executable, "-c", code], cwd=ROOT, env=dict(env, MVSIM_FFT_ZPASS="fft"), stdout=subprocess.PIPE,
+                             stderr=subprocess.PIPE, text=True)
+    results = {"default": _geometry_sweep(mvs, os.environ.get("MVSIM_FFT_ZPASS") == "fft")}
+    out, err = child.communicate(timeout=120)
+    assert child.returncode == 0, err[-2000:]
+    results["fft_zpass=fft"] = json.loads(out.splitlines()[-1])
+    for name, (n, none, bad) in results.items():
+        print(f"{name}: {n} cases, {none} without a hand-written size, {len(bad)} mismatches")
+        assert not bad, (name, bad)
+        assert n > 200000 and 2 * none < n, (name, n, none)       # ... and not by comparing None with None
 
 
 def _fused_reachable():
