@@ -261,6 +261,9 @@ class Context(ContextAberrations):
                                                  seed & 0xFFFFFFFFFFFFFFFF, stream, index_offset))
 
     def make_isotropic(self, img, inc: int) -> np.ndarray:
+        """makeIsotropic (SMVD:144-171).  Contract: finite voxels.  k_make_isotropic drops the six interpolator taps whose weight is
+        exactly 0, the reference multiplies them by 0, so an inf or NaN neighbour in x or y poisons the reference's voxel and not
+        this one.  Acquisitions are finite counts."""
         v = _as_volume(img)
         nz, ny, nx = v.shape
         if inc < 1:
@@ -669,6 +672,14 @@ class Context(ContextAberrations):
         _lib.check(self._L.mvsim_adjust_image_dev(self._h, C.c_void_p(dptr), n, min_value, target_average,
                                                   C.byref(corr) if want_corr else None))
         return corr.value if want_corr else None
+
+    def make_isotropic_dev(self, in_dptr, dim_xyz, inc, out_dptr):
+        """``out_dptr`` holds mvsim_isotropic_nz(Nz, inc) planes; asynchronous on the stream."""
+        _lib.check(self._L.mvsim_make_isotropic_dev(self._h, C.c_void_p(in_dptr), (C.c_int64 * 3)(*dim_xyz), int(inc),
+                                                    C.c_void_p(out_dptr)))
+
+    def compute_weight_image_dev(self, dim_xyz, out_dptr):
+        _lib.check(self._L.mvsim_compute_weight_image_dev(self._h, (C.c_int64 * 3)(*dim_xyz), C.c_void_p(out_dptr)))
 
     def extract_slices_dev(self, in_dptr, dim_xyz, inc, snr, seed, stream, out_dptr):
         _lib.check(self._L.mvsim_extract_slices_dev(self._h, C.c_void_p(in_dptr), (C.c_int64 * 3)(*dim_xyz), inc, snr,
