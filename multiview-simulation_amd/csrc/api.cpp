@@ -1,7 +1,7 @@
 // C ABI of libmvsim (include/mvsim.h), part 1: errors, options, context lifetime, memory, the stage operators on device buffers
 // and the statistics / geometry / timing queries.  The per-view pipeline is api_view.cpp, the host-buffer entry points are
 // api_host.cpp, the phantom / bead / refraction-simulator wrappers api_sims.cpp.  Host orchestration only -- every voxel of
-// arithmetic happens in the HIP kernels (kernels.hip, fftconv.hip, stencil.hip).
+// arithmetic happens in the HIP kernels (kernels.hip, extract.hip, fftconv.hip, stencil.hip).
 #include "api_internal.h"
 
 #include <cstdlib>
@@ -245,7 +245,7 @@ int set_device(mvsim_ctx* ctx, bool keep_tail)
 // The queue share of the context's next sampled view (QueueMode).  Option given: that.  Auto: what this context's views have needed so
 // far -- k_poisson_refused leaves the sixteenths the fullest refused segment would have needed in a page-locked word, read here without
 // synchronising: a view whose segments refuse voxels still gives the right counts (slower), and the views after it get the larger queue.
-int queue_mode_next(mvsim_ctx* ctx, QueueMode* qm)
+static int queue_mode_next(mvsim_ctx* ctx, QueueMode* qm)
 {
     qm->share = 0; qm->hint = nullptr;
     if (ctx->opt.poisson_queue != 1) return MVSIM_OK;
@@ -255,6 +255,34 @@ int queue_mode_next(mvsim_ctx* ctx, QueueMode* qm)
     qm->share = QUEUE_SHARE_AUTO + ctx->queue_share_learned;
     qm->hint = ctx->queue_hint;
     return MVSIM_OK;
+}
+
+int extract_stage_plan(mvsim_ctx* ctx, const ExtractGeom& g, const ExtractOps& ops, ExtractPlan* pl, bool views_aligned16)
+{
+    const bool aligned16 = ops.nviews > 0 ? views_aligned16 : (reinterpret_cast<uintptr_t>(ops.in + g.in_offset) | reinterpret_cast<uintptr_t>(ops.out)) % 16 == 0;
+    QueueMode qm;
+    MVSIM_TRY(queue_mode_next(ctx, &qm));                 // (whether or not the launch samples: the learned share follows the hint word)
+    *pl = extract_plan(g, aligned16, ops.noise, qm);
+    if (ops.noise) MVSIM_TRY(ctx->pqueue.reserve(ops.nviews > 0 ? pl->layout.view_stride() * (size_t)ops.nviews : pl->layout.total_bytes));
+    return MVSIM_OK;
+}
+
+int extract_stage_run(mvsim_ctx* ctx, const ExtractPlan& pl, ExtractOps& ops)
+{
+    if (ops.nviews == 0) ops.queue_ws = ops.noise ? ctx->pqueue.p : nullptr;
+    ev_begin(ctx, ST_EXTRACT);
+    MVSIM_TRY(launch_extract(ctx->stream, pl, ops));
+    ev_end(ctx, ST_EXTRACT);
+    const int64_t path[5] = {pl.kernel, pl.checked ? 1 : 0, pl.blocks, pl.segcap, ops.nviews > 0 ? ops.nviews : 1};
+    std::memcpy(ctx->extract_path, path, sizeof(path));
+    return MVSIM_OK;
+}
+
+int extract_stage(mvsim_ctx* ctx, const ExtractGeom& g, ExtractOps& ops)
+{
+    ExtractPlan pl;
+    MVSIM_TRY(extract_stage_plan(ctx, g, ops, &pl));
+    return extract_stage_run(ctx, pl, ops);
 }
 
 // Tools.normImage on the host (Tools.java:112-132), in place (Q5): double sum, (float)(v / sum).
@@ -645,16 +673,11 @@ int mvsim_extract_slices_dev(mvsim_ctx* ctx, const float* in, const int64_t dim[
     MVSIM_TRY(check_dim(dim));
     MVSIM_CHECK_ARG(in && out, "null buffer");
     MVSIM_CHECK_ARG(inc >= 1, "inc must be >= 1");
-    const bool noise = snr >= 0.0f;   // SMVD:211
-    void* qws = nullptr;
-    QueueMode qm;
-    MVSIM_TRY(queue_mode_next(ctx, &qm));
-    if (noise) { MVSIM_TRY(ctx->pqueue.reserve(poisson_queue_bytes_planes(dim[0] * dim[1], mvsim_extract_nz(dim[2], inc), qm.share))); qws = ctx->pqueue.p; }
-    ev_begin(ctx, ST_EXTRACT);
-    MVSIM_TRY(launch_extract(ctx->stream, in, out, dim, inc, false, nullptr, 0.0f, noise,
-                             mvsim_poisson_mul((double)snr), seed, stream, 0, qws, qm, 0, ctx->extract_path));
-    ev_end(ctx, ST_EXTRACT);
-    return MVSIM_OK;
+    ExtractOps ops;
+    ops.in = in; ops.out = out;
+    ops.noise = snr >= 0.0f;   // SMVD:211
+    ops.mul = mvsim_poisson_mul((double)snr); ops.seed = seed; ops.stream = stream;
+    return extract_stage(ctx, ExtractGeom::strided(dim, inc), ops);
 }
 
 int mvsim_make_isotropic_dev(mvsim_ctx* ctx, const float* in, const int64_t dim[3], int inc, float* out)
@@ -788,15 +811,13 @@ int mvsim_fused_tail_geometry(mvsim_ctx* ctx, const int64_t dim[3], const int64_
     MVSIM_CHECK_ARG(ctx != nullptr && dim && kdim && out, "null pointer");
     MVSIM_TRY(check_dim(dim));
     MVSIM_CHECK_ARG(inc >= 1, "inc must be >= 1");
-    long long blocks = 0;
-    unsigned int segcap = 0;
+    ExtractPlan fp{};
     // what view_enqueue asks of a noisy view before it offers the convolution its tail
-    if (!ctx->opt.fuse_tail || ctx->opt.poisson_queue != 1 || !fused_tail_geometry(dim, kdim, inc, want_con != 0, ctx->opt, &blocks, &segcap)) {
+    if (!ctx->opt.fuse_tail || ctx->opt.poisson_queue != 1 || !fused_tail_geometry(dim, kdim, inc, want_con != 0, ctx->opt, &fp)) {
         set_error("this view would not take the fused tail");
         return MVSIM_EINVAL;
     }
-    out[0] = blocks;
-    out[1] = segcap;
+    out[0] = fp.blocks; out[1] = fp.segcap;
     return MVSIM_OK;
 }
 

@@ -223,13 +223,12 @@ int mvsim_poisson_process(mvsim_ctx* ctx, float* img, int64_t n, double snr, uin
     MVSIM_TRY(up(ctx, ctx->vol_a, img, bytes));
     MVSIM_TRY(ctx->out_buf.reserve(bytes));
     const int64_t dim[3] = {n, 1, 1};
-    QueueMode qm;
-    MVSIM_TRY(queue_mode_next(ctx, &qm));
-    MVSIM_TRY(ctx->pqueue.reserve(poisson_queue_bytes_planes(n, 1, qm.share)));
-    ev_begin(ctx, ST_EXTRACT);
-    MVSIM_TRY(launch_extract(ctx->stream, ctx->vol_a.as<float>(), ctx->out_buf.as<float>(), dim, 1, false, nullptr,
-                             0.0f, true, mvsim_poisson_mul(snr), seed, stream, index_offset, ctx->pqueue.p, qm, 0, ctx->extract_path));
-    ev_end(ctx, ST_EXTRACT);
+    ExtractGeom g = ExtractGeom::strided(dim, 1);
+    g.index_offset = index_offset;
+    ExtractOps ops;
+    ops.in = ctx->vol_a.as<float>(); ops.out = ctx->out_buf.as<float>();
+    ops.noise = true; ops.mul = mvsim_poisson_mul(snr); ops.seed = seed; ops.stream = stream;
+    MVSIM_TRY(extract_stage(ctx, g, ops));
     return down_counts(ctx, img, ctx->out_buf.as<float>(), n, true);
 }
 

@@ -14,7 +14,12 @@ namespace mvsim {
 
 // every entry point starts here: the device, and a pending tail ordered in front of what the call enqueues (api.cpp)
 int set_device(mvsim_ctx* ctx, bool keep_tail = false);
-int queue_mode_next(mvsim_ctx* ctx, QueueMode* qm);
+// The one way to a context's extract + Poisson stage (api.cpp): the queue mode of this launch, its plan, the queue workspace, the launch
+// between the stage's markers on ctx->stream, the form taken left in ctx->extract_path; ops.queue_ws is the stage's to fill.  In two steps
+// where the plan is needed first: stacked views (the queue regions of their table; views_aligned16 = every view's buffers), view_enqueue.
+int extract_stage_plan(mvsim_ctx* ctx, const ExtractGeom& g, const ExtractOps& ops, ExtractPlan* pl, bool views_aligned16 = false);
+int extract_stage_run(mvsim_ctx* ctx, const ExtractPlan& pl, ExtractOps& ops);
+int extract_stage(mvsim_ctx* ctx, const ExtractGeom& g, ExtractOps& ops);
 int host_threads_of(const mvsim_ctx* ctx);
 void psf_normalise_host(float* psf_host, int64_t n);
 int psf_prepare(mvsim_ctx* ctx, float* psf_host, const int64_t kdim[3], const int64_t dim[3]);

@@ -86,7 +86,6 @@ static int view_enqueue(mvsim_ctx* ctx, const float* gt, const int64_t dim[3], c
     // only every inc-th plane is acquired: when the adjusted volume itself is not asked for, the last two passes of the
     // convolution need not produce the other planes (the convolution says whether it could honour that)
     ConvTail tail;
-    const long long plane_vox = (long long)dim[0] * dim[1];
     tail.zstride = (!materialise && p->inc > 1 && (!noise || ctx->opt.poisson_queue == 1)) ? p->inc : 1;
     tail.corr_n = n; tail.min_value = p->min_value; tail.target_average = p->target_average;
     tail.x_done = x_done;
@@ -104,10 +103,7 @@ static int view_enqueue(mvsim_ctx* ctx, const float* gt, const int64_t dim[3], c
     }
     MVSIM_TRY(convolve_dev_impl(ctx, att, dim, kdim, method, con, &tail));
     if (tail.fused) {                  // pass E adjusted, extracted and sampled (phase 1); the resolver is enqueued behind it
-        long long fb = 0;
-        unsigned int fs = 0;
-        (void)fused_tail_geometry(dim, kdim, p->inc, materialise, ctx->opt, &fb, &fs);
-        const int64_t fused[5] = {EXTRACT_FUSED_TAIL, 0, fb, noise ? (int64_t)fs : 0, 1};
+        const int64_t fused[5] = {EXTRACT_FUSED_TAIL, 0, tail.fused_blocks, noise ? (int64_t)tail.fused_segcap : 0, 1};
         std::memcpy(ctx->extract_path, fused, sizeof(fused));
         return MVSIM_OK;
     }
@@ -118,11 +114,14 @@ static int view_enqueue(mvsim_ctx* ctx, const float* gt, const int64_t dim[3], c
     if (materialise) MVSIM_TRY(launch_adjust_apply(ctx->stream, con, n, scal, p->min_value));
     ev_end(ctx, ST_ADJUST);
 
-    void* qws = nullptr;
     const int64_t n_out = dim[0] * dim[1] * mvsim_extract_nz(dim[2], p->inc);
-    QueueMode qm;
-    MVSIM_TRY(queue_mode_next(ctx, &qm));
-    if (noise) { MVSIM_TRY(ctx->pqueue.reserve(poisson_queue_bytes_planes(dim[0] * dim[1], mvsim_extract_nz(dim[2], p->inc), qm.share))); qws = ctx->pqueue.p; }
+    ExtractOps ops;
+    ops.in = con; ops.out = o->acq; ops.scal = scal;
+    ops.min_value = p->min_value; ops.noise = noise; ops.mul = mvsim_poisson_mul((double)p->snr); ops.seed = p->seed; ops.stream = p->stream;
+    ops.adjust = !materialise;             // a materialised volume is adjusted already
+    // compact: `con` holds the acquired planes only (read in order, the RNG counted in source planes).  The queue grows here, before the tail forks
+    ExtractPlan xpl;
+    MVSIM_TRY(extract_stage_plan(ctx, tail.zstride > 1 ? ExtractGeom::compact(dim, p->inc) : ExtractGeom::strided(dim, p->inc), ops, &xpl));
     // The tail runs on a stream of its own and is joined by whatever the context does next (join_tail): the next view's
     // rotate+attenuate leaves most of the chip idle and runs beside it.
     // (not beside the fused rotate + attenuate + x transform of the next view: that kernel is bound by vector issue like the
@@ -140,17 +139,7 @@ static int view_enqueue(mvsim_ctx* ctx, const float* gt, const int64_t dim[3], c
         tail_on = ctx->tail_stream;
     }
     StreamSwap swap(ctx, tail_on);
-    ev_begin(ctx, ST_EXTRACT);
-    if (tail.zstride > 1) {
-        // `con` holds the acquired planes only: read them in order, count the RNG in source planes
-        const int64_t cdim[3] = {dim[0], dim[1], mvsim_extract_nz(dim[2], p->inc)};
-        MVSIM_TRY(launch_extract(ctx->stream, con, o->acq, cdim, 1, true, scal, p->min_value, noise,
-                                 mvsim_poisson_mul((double)p->snr), p->seed, p->stream, 0, qws, qm, p->inc, ctx->extract_path));
-    } else {
-        MVSIM_TRY(launch_extract(ctx->stream, con, o->acq, dim, p->inc, !materialise, scal, p->min_value, noise,
-                                 mvsim_poisson_mul((double)p->snr), p->seed, p->stream, 0, qws, qm, 0, ctx->extract_path));
-    }
-    ev_end(ctx, ST_EXTRACT);
+    MVSIM_TRY(extract_stage_run(ctx, xpl, ops));
     if (overlap_ok) {
         MVSIM_HIP(hipEventRecord(ctx->ev_tail, ctx->tail_stream));
         ctx->tail_pending = true;
@@ -330,7 +319,6 @@ static int views_enqueue_batched(mvsim_ctx* ctx, const float* gt, const int64_t 
     const mvsim_view_params& p0 = params[0];
     const bool noise = p0.snr >= 0.0f;
     const int64_t nzo = mvsim_extract_nz(dim[2], p0.inc), plane_vox = dim[0] * dim[1];
-    const int64_t n_out = plane_vox * nzo;
     ev_next(ctx);
     // one upload for everything the views bring: [V inverse models][V extract tables][V normalised PSFs]
     const size_t tab_a = (size_t)V * sizeof(Affine), tab_e = (size_t)V * sizeof(ExtractView);
@@ -341,10 +329,14 @@ static int views_enqueue_batched(mvsim_ctx* ctx, const float* gt, const int64_t 
     const int zstride = p0.inc > 1 ? p0.inc : 1;                                        // (as view_enqueue: only the planes extractSlices reads)
     const int64_t con_planes = zstride > 1 ? nzo : dim[2];
     MVSIM_TRY(ctx->vol_a.reserve((size_t)V * plane_vox * con_planes * sizeof(float)));  // con[v]
-    QueueMode qm;
-    MVSIM_TRY(queue_mode_next(ctx, &qm));
-    const size_t qbytes = noise ? ((poisson_queue_bytes_planes(plane_vox, nzo, qm.share) + 255) & ~(size_t)255) : 0;
-    if (noise) MVSIM_TRY(ctx->pqueue.reserve(qbytes * V));
+    float* con = ctx->vol_a.as<float>();
+    bool vec_all = true;
+    for (int v = 0; v < V; ++v)
+        vec_all = vec_all && ((reinterpret_cast<uintptr_t>(con + (size_t)v * plane_vox * con_planes) | reinterpret_cast<uintptr_t>(outs[v].acq)) % 16 == 0);
+    ExtractPlan xpl;                                                                    // `con` holds the acquired planes only where zstride > 1
+    ExtractOps xops;
+    xops.nviews = V; xops.adjust = true; xops.min_value = p0.min_value; xops.noise = noise; xops.mul = mvsim_poisson_mul((double)p0.snr);
+    MVSIM_TRY(extract_stage_plan(ctx, zstride > 1 ? ExtractGeom::compact(dim, p0.inc) : ExtractGeom::strided(dim, p0.inc), xops, &xpl, vec_all));
     double *partial, *scal0;
     MVSIM_TRY(scal_ptr(ctx, &partial, &scal0));
     int slot = 0;
@@ -353,8 +345,6 @@ static int views_enqueue_batched(mvsim_ctx* ctx, const float* gt, const int64_t 
     char* dp = ctx->view_tab.as<char>();
     Affine* atab = reinterpret_cast<Affine*>(hp);
     ExtractView* etab = reinterpret_cast<ExtractView*>(hp + off_e);
-    float* con = ctx->vol_a.as<float>();
-    bool vec_all = true;
     for (int v = 0; v < V; ++v) {
         double m[12];
         axis_rotation_host(dim, 0, params[v].degrees, m);
@@ -363,10 +353,9 @@ static int views_enqueue_batched(mvsim_ctx* ctx, const float* gt, const int64_t 
         e.in = con + (size_t)v * plane_vox * con_planes;
         e.out = outs[v].acq;
         e.scal = scal_of(ctx, v);
-        e.queue = nullptr; e.qcount = nullptr;
-        if (noise) poisson_queue_split(ctx->pqueue.as<char>() + (size_t)v * qbytes, &e.queue, &e.qcount);
+        const QueueLayout::Region q = xpl.layout.region(noise ? ctx->pqueue.p : nullptr, v);
+        e.queue = q.items; e.qcount = q.counts;
         e.k0 = (uint32_t)params[v].seed; e.k1 = (uint32_t)(params[v].seed >> 32); e.stream = params[v].stream; e.pad = 0;
-        vec_all = vec_all && ((reinterpret_cast<uintptr_t>(e.in) | reinterpret_cast<uintptr_t>(e.out)) % 16 == 0);
     }
     // Tools.normImage of the V PSFs (in place, Q5) and their copy into the upload block: one host thread per view -- a 51^3 stack is 0.13 ms of
     // summation and division, and nothing reaches the GPU before the last of them is done
@@ -402,18 +391,8 @@ static int views_enqueue_batched(mvsim_ctx* ctx, const float* gt, const int64_t 
     MVSIM_TRY(custom_fft_convolve(ctx, ctx->vol_b.as<float>(), dim, reinterpret_cast<const float*>(dp + off_p), kdim, con, &tail));
     if (!tail.corr_done || tail.zstride != zstride) { set_error("stacked views: the convolution did not deliver the factors / planes asked for"); return MVSIM_EHIP; }
 
-    ev_begin(ctx, ST_EXTRACT);
-    const ExtractView* evt = reinterpret_cast<const ExtractView*>(dp + off_e);
-    if (zstride > 1) {
-        const int64_t cdim[3] = {dim[0], dim[1], nzo};                                  // `con` holds the acquired planes only
-        MVSIM_TRY(launch_extract_views(ctx->stream, cdim, 1, true, p0.min_value, noise, mvsim_poisson_mul((double)p0.snr), qm,
-                                       p0.inc, V, evt, vec_all, ctx->extract_path));
-    } else {
-        MVSIM_TRY(launch_extract_views(ctx->stream, dim, p0.inc, true, p0.min_value, noise, mvsim_poisson_mul((double)p0.snr), qm,
-                                       0, V, evt, vec_all, ctx->extract_path));
-    }
-    ev_end(ctx, ST_EXTRACT);
-    return MVSIM_OK;
+    xops.vt = reinterpret_cast<const ExtractView*>(dp + off_e);
+    return extract_stage_run(ctx, xpl, xops);
 }
 
 int mvsim_simulate_views_dev(mvsim_ctx* ctx, const float* gt, const int64_t dim[3], float* const* psf_host, const int64_t kdim[3],
@@ -627,35 +606,18 @@ int mvsim_view_slab_convolve_dev(mvsim_ctx* ctx, const float* gt, const int64_t 
 static int slab_finish_enqueue(mvsim_ctx* ctx, const int64_t dim[3], const mvsim_view_params* p, int64_t z0, int64_t z1, float* acq,
                                int64_t* n_planes)
 {
-    const int64_t plane = dim[0] * dim[1];
     double *partial, *scal;
     MVSIM_TRY(scal_ptr(ctx, &partial, &scal));
     MVSIM_TRY(launch_adjust_corr(ctx->stream, scal, nvox(dim), p->min_value, p->target_average));
-    const int64_t k0 = (z0 + p->inc - 1) / p->inc, k1 = (z1 + p->inc - 1) / p->inc;     // acquired planes k: z0 <= k*inc < z1
-    if (n_planes) *n_planes = k1 - k0;
-    if (k1 <= k0) return MVSIM_OK;
-    QueueMode qm;
-    MVSIM_TRY(queue_mode_next(ctx, &qm));
-    if (ctx->slab_zstride > 1) {
-        // compact slab: vol_a holds the planes z0 + k * inc alone, in order (z0 is a multiple of inc: plane k0 * inc = z0)
-        const int64_t cdim[3] = {dim[0], dim[1], k1 - k0};
-        const bool noise_c = p->snr >= 0.0f;
-        void* q = nullptr;
-        if (noise_c) { MVSIM_TRY(ctx->pqueue.reserve(poisson_queue_bytes_planes(plane, k1 - k0, qm.share))); q = ctx->pqueue.p; }
-        return launch_extract(ctx->stream, ctx->vol_a.as<float>(), acq, cdim, 1, true, scal, p->min_value, noise_c, mvsim_poisson_mul((double)p->snr),
-                              p->seed, p->stream, (uint64_t)(z0 * plane), q, qm, p->inc, ctx->extract_path);
-    }
-    const int64_t first = k0 * p->inc;                      // global index of the first acquired source plane
-    const int64_t ldim[3] = {dim[0], dim[1], z1 - first};
-    const bool noise = p->snr >= 0.0f;
-    void* qws = nullptr;
-    if (noise) {
-        MVSIM_TRY(ctx->pqueue.reserve(poisson_queue_bytes_planes(plane, k1 - k0, qm.share)));
-        qws = ctx->pqueue.p;
-    }
-    return launch_extract(ctx->stream, ctx->vol_a.as<float>() + plane * (first - z0), acq, ldim, p->inc, true, scal,
-                          p->min_value, noise, mvsim_poisson_mul((double)p->snr), p->seed, p->stream,
-                          (uint64_t)(first * plane), qws, qm, 0, ctx->extract_path);
+    // compact slab: vol_a holds the planes z0 + k * inc alone, in order (z0 is a multiple of inc)
+    const ExtractGeom g = ExtractGeom::slab(dim, p->inc, z0, z1, ctx->slab_zstride > 1);
+    if (n_planes) *n_planes = g.nzo;
+    if (g.nzo == 0) return MVSIM_OK;
+    ExtractOps ops;
+    ops.in = ctx->vol_a.as<float>(); ops.out = acq; ops.scal = scal;
+    ops.adjust = true; ops.min_value = p->min_value; ops.noise = p->snr >= 0.0f; ops.mul = mvsim_poisson_mul((double)p->snr);
+    ops.seed = p->seed; ops.stream = p->stream;
+    return extract_stage(ctx, g, ops);
 }
 
 int mvsim_view_slab_finish_dev(mvsim_ctx* ctx, const int64_t dim[3], const mvsim_view_params* p, int64_t z0,

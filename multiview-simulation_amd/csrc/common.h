@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/mvsim.h"
+#include "extract_plan.h"
 
 // Attribution switches (tools/attribute_flags.sh, attribute_valu.sh, attribution_run.sh: builds that compile a part of a kernel's work
 // OUT -- and with it the correctness of the results -- to see what that part costs; the figures are in profiles/r04_attribution.txt).
@@ -193,15 +194,6 @@ struct Options {
     bool    skip_empty = true;         // convolution passes skip planes the fused rotate kernel found empty (exact; option for A/B runs)
     int64_t beads_pair_cap = (int64_t)1 << 28;   // bead renderer and volume injection: (brick, item) pairs one chunk may bin; larger calls run in chunks (beads.hip, aberrations.hip)
 };
-// How launch_extract samples.  share 0: one launch, no work queue.  1..16: work queue whose per-block segments hold that many sixteenths
-// of the block's voxels.  QUEUE_SHARE_AUTO + L (L = 0..16): the library's choice -- every voxel for queues of up to 64 MiB, else
-// max(QUEUE_SHARE_START, L) sixteenths, L being what this context's views have needed so far (api.cpp: queue_mode_next).
-constexpr int QUEUE_SHARE_AUTO = 32;
-constexpr int QUEUE_SHARE_START = 5;
-struct QueueMode {
-    int           share = 0;
-    unsigned int* hint  = nullptr;  // page-locked word k_poisson_refused raises to the sixteenths the fullest refused block would have needed
-};
 const Options& env_options();
 int parse_option(Options& o, const char* name, const char* value);   // MVSIM_OK / MVSIM_EINVAL
 
@@ -369,20 +361,7 @@ int launch_sum(hipStream_t s, const float* in, int64_t n, double* partial, doubl
 int launch_adjust_corr(hipStream_t s, double* scal, int64_t n, float min_value, float target);
 int launch_adjust_apply(hipStream_t s, float* img, int64_t n, const double* scal, float min_value);
 int launch_norm_apply(hipStream_t s, float* img, int64_t n, const double* scal);
-// extract (+ optional adjust using scal[1]) (+ optional Poisson).  in: Nx*Ny*Nz, out: Nx*Ny*nzo
-int launch_extract(hipStream_t s, const float* in, float* out, const int64_t dim[3], int inc, bool adjust,
-                   const double* scal, float min_value, bool noise, double mul, uint64_t seed,
-                   uint32_t stream, uint64_t index_offset, void* queue_ws, QueueMode queue_mode, int index_inc = 0,
-                   int64_t* path_out = nullptr);   // path_out: {extract_path's four words, views in the launch}
-// The sampler form launch_extract takes (kernels.hip: extract_path; mvsim_extract_path): path = {EXTRACT_K_*, segments can refuse,
-// blocks, items per segment}.  qshare: 0 = no work queue, else 1..16 sixteenths.
-enum { EXTRACT_K_SCALAR = 0, EXTRACT_K_VEC = 1, EXTRACT_K_NOISE2 = 2, EXTRACT_K_NOISE2_ANY = 3, EXTRACT_FUSED_TAIL = 4 };
-void extract_path(const int64_t dim[3], int inc, int index_inc, uint64_t index_offset, bool aligned16, int qshare, int64_t path[4]);
-// bytes of the Poisson work queue (HBM) for nzo planes of `plane` voxels whichever sampler kernel takes them (planes that are no
-// multiple of four voxels or unaligned buffers go group by group through k_extract_noise2_any, whose wave slots are padded per plane)
-size_t poisson_queue_bytes_planes(long long plane, long long nzo, int share);
-int poisson_queue_read_stats(const void* queue_ws, size_t bytes, long long stats[5]);
-// ---- stacked views (mvsim_simulate_views_dev): one launch per stage for V views of one ground truth; blockIdx.y / .z = view
+// ---- extract (+ adjust using scal[1]) (+ Poisson): extract.hip runs what extract_plan.h plans
 struct ExtractView {              // per-view operands of the extract + Poisson kernels (device table)
     const float*  in;             // the view's convolved planes
     float*        out;            // its acquisition
@@ -391,10 +370,27 @@ struct ExtractView {              // per-view operands of the extract + Poisson 
     unsigned int* qcount;         // ... and their counters
     uint32_t      k0, k1, stream, pad;
 };
+struct ExtractOps {               // the operands of one launch_extract
+    const float*  in = nullptr;   // the buffer the planes are read from (ExtractGeom::in_offset voxels in), the acquisition, the
+    float*        out = nullptr;  // [sum, adjustImage factor] pair and the queue workspace (QueueLayout) ...
+    const double* scal = nullptr;
+    void*         queue_ws = nullptr;
+    const ExtractView* vt = nullptr;   // ... or those of `nviews` stacked views, with their RNG keys, from a device table (blockIdx.y = view)
+    int           nviews = 0;
+    bool          adjust = false, noise = false;
+    float         min_value = 0.f;
+    double        mul = 0.0;
+    uint64_t      seed = 0;       // the RNG key and stream of the launch
+    uint32_t      stream = 0;
+};
+int launch_extract(hipStream_t s, const ExtractPlan& pl, const ExtractOps& o);
+int launch_resolve(hipStream_t s, const ExtractPlan& pl, const ExtractOps& o);   // the sampler's second launch alone (the fused tail)
+// mvsim_extract_path: the plan of nzo = (dim[2] - 1) / inc + 1 acquired planes as path = {EXTRACT_K_*, segments can refuse, blocks, items
+// per segment}.  index_inc: 0 = inc; qshare: 0 = no work queue, else 1..16 sixteenths.
+void extract_path(const int64_t dim[3], int inc, int index_inc, uint64_t index_offset, bool aligned16, int qshare, int64_t path[4]);
+int poisson_queue_read_stats(const void* queue_ws, size_t bytes, long long stats[5]);
+// ---- stacked views (mvsim_simulate_views_dev): one launch per stage for V views of one ground truth; blockIdx.y / .z = view
 int launch_rotate_attenuate_views(hipStream_t s, const float* in, float* att, const int64_t dim[3], const Affine* atab_dev, int nviews, double delta);
-void poisson_queue_split(void* queue_ws, void** queue_items, unsigned int** qcount);
-int launch_extract_views(hipStream_t s, const int64_t dim[3], int inc, bool adjust, float min_value, bool noise, double mul,
-                         QueueMode queue_mode, int index_inc, int nviews, const ExtractView* vt_dev, bool vec_all, int64_t* path_out = nullptr);
 int launch_pack_u16(hipStream_t s, const float* in, unsigned short* out16, int64_t n, unsigned int* flag);
 int launch_make_isotropic(hipStream_t s, const float* in, float* out, const int64_t dim[3], int inc);
 // phantom generator (phantom.hip)
@@ -460,8 +456,11 @@ struct ConvTail {
     double   mul = 0.0;
     uint64_t seed = 0;
     uint32_t stream = 0;
-    // out: true when the convolution did all of that (sum, factor in the context's scalar slots; acquisition complete)
+    // out: true when the convolution did all of that (sum, factor in the context's scalar slots; acquisition complete), and the
+    // blocks and items per segment of the queue pass E filled
     bool     fused = false;
+    long long    fused_blocks = 0;
+    unsigned int fused_segcap = 0;
     // in: pass A has run already -- the context's spectrum buffer holds the x transform of the image rows (fused rotate +
     // attenuate + x transform, rotate_fft.hip); `img` is not read
     bool     x_done = false;
@@ -475,9 +474,6 @@ struct ConvTail {
 };
 // bytes of queue workspace the fused tail needs for this geometry (0: the geometry has no fused tail)
 size_t fused_tail_queue_bytes(const int64_t dim[3], const int64_t kdim[3], int inc, bool con_wanted, const Options& opt);
-// plane / idx_inc / index_offset: how the RNG counter of an output element follows from its position (ResolveJob)
-int launch_poisson_resolve(hipStream_t s, float* out, void* queue_items, const unsigned int* qcount, int segments, unsigned int segcap,
-                           double mul, uint64_t seed, uint32_t stream, long long plane, int idx_inc, uint64_t index_offset);
 int comm_allreduce_f64_on_stream(mvsim_ctx* cc, double* value_dev, hipStream_t s);      // comm.cpp
 int rotate_attenuate_fftx(mvsim_ctx* ctx, const float* gt, float* rot_or_null, float* att_or_null, const int64_t dim[3],
                           const int64_t kdim[3], const Affine& inv, double delta, bool* done, const int** plane_nz = nullptr,
@@ -524,9 +520,8 @@ int  custom_fft_convolve_slab(mvsim_ctx* ctx, const float* img, const int64_t di
                               const int64_t kdim[3], const SlabRange& slab, float* out, ConvTail* tail);
 void custom_fft_release(mvsim_ctx* ctx);
 bool custom_fft_geometry(const int64_t dim[3], const int64_t kdim[3], int64_t g[5], const Options& opt);
-// {blocks, items per segment} of the fused tail (pass E adjusts, extracts and samples); false when the view would not be fused
-bool fused_tail_geometry(const int64_t dim[3], const int64_t kdim[3], int inc, bool con_wanted, const Options& opt, long long* blocks,
-                         unsigned int* segcap);
+// the plan of the fused tail (pass E adjusts, extracts and samples: blocks, items per segment, queue layout); false when the view would not be fused
+bool fused_tail_geometry(const int64_t dim[3], const int64_t kdim[3], int inc, bool con_wanted, const Options& opt, ExtractPlan* fp);
 // true when views of this geometry can run stacked through the hand-written passes (ConvTail::views > 1): direct z pass, early sum,
 // pass B reading the mirrored y halo from its mirror images, no inline-FFT z pass, no fused tail
 bool custom_fft_batchable(const mvsim_ctx* ctx, const int64_t dim[3], const int64_t kdim[3]);

@@ -1,0 +1,376 @@
+// The extract + Poisson stage (gfx950, wave64): extractSlices with adjustImage on the fly and the two-launch Poisson sampler -- the four
+// kernels of phase 1, the resolver, the walk over what full segments refused -- and the one launcher that runs an ExtractPlan
+// (extract_plan.h).  Device arithmetic: poisson_dev.h; design notes: DESIGN.md 4.4.
+#include <type_traits>
+#include <vector>
+
+#include "common.h"
+#include "poisson_dev.h"
+
+namespace mvsim {
+
+// ------------------------------------------------------------------------------------------------
+// extractSlices + adjust + Poisson (SimulateMultiViewDataset.java:195-251, Tools.java:73-86):
+// out[x,y,k] = f(in[x,y,k*inc]);  ADJUST applies the two adjustImage passes on the fly (fused
+// path: the scaled volume is never materialised); NOISE draws Poisson((double)v * mul).
+// ------------------------------------------------------------------------------------------------
+template <bool ADJUST, bool NOISE>
+__global__ __launch_bounds__(256) void k_extract(const float* __restrict__ in, float* __restrict__ out,
+                                                 long long plane, long long nzo, int inc, int idx_inc,
+                                                 const double* __restrict__ scal, float min_value, double mul,
+                                                 uint32_t k0, uint32_t k1, uint32_t stream,
+                                                 unsigned long long index_offset, const ExtractView* __restrict__ vt)
+{
+    if (vt) { const ExtractView e = vt[blockIdx.y]; in = e.in; out = e.out; scal = e.scal; k0 = e.k0; k1 = e.k1; stream = e.stream; }
+    double corr = 1.0;
+    if (ADJUST) corr = scal[1];
+    const long long total = plane * nzo;
+    const long long nthreads = (long long)gridDim.x * 256;
+    for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < total; o += nthreads) {
+        const long long k = o / plane;
+        const long long i = o - k * plane;
+        const long long src = k * inc * plane + i;
+        float v = in[src];
+        if (ADJUST) v = adjust_one(v, corr, min_value);
+        if (NOISE) v = poisson_counter((double)v * mul, k0, k1, stream, index_offset + (unsigned long long)(k * idx_inc * plane + i));
+        out[o] = v;
+    }
+}
+
+// Vector form: 4 consecutive voxels per lane (16-B loads/stores); the lane's 4 voxels are exactly one
+// Philox group.  Requires plane % 4 == 0, index_offset % 4 == 0 and 16-B aligned buffers.
+template <bool ADJUST, bool NOISE>
+__global__ __launch_bounds__(256) void k_extract4(const float* __restrict__ in, float* __restrict__ out,
+                                                  long long plane4, long long nzo, int inc, int idx_inc,
+                                                  const double* __restrict__ scal, float min_value, double mul,
+                                                  uint32_t k0, uint32_t k1, uint32_t stream,
+                                                  unsigned long long index_offset, const ExtractView* __restrict__ vt)
+{
+    if (vt) { const ExtractView e = vt[blockIdx.y]; in = e.in; out = e.out; scal = e.scal; k0 = e.k0; k1 = e.k1; stream = e.stream; }
+    double corr = 1.0;
+    if (ADJUST) corr = scal[1];
+    const long long total4 = plane4 * nzo;
+    const long long nthreads = (long long)gridDim.x * 256;
+    const float4* __restrict__ in4 = reinterpret_cast<const float4*>(in);
+    float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
+    const bool small32 = total4 < (1ll << 32);
+    for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < total4; o += nthreads) {
+        long long src4 = o, idx4 = o;                 // where the voxels are read / what the RNG counter says they are
+        if (inc != 1 || idx_inc != 1) {
+            const long long k = small32 ? (long long)((unsigned)o / (unsigned)plane4) : o / plane4;
+            src4 = k * inc * plane4 + (o - k * plane4);
+            idx4 = k * idx_inc * plane4 + (o - k * plane4);
+        }
+        float4 v = in4[src4];
+        if (ADJUST) {
+            v.x = adjust_one(v.x, corr, min_value);
+            v.y = adjust_one(v.y, corr, min_value);
+            v.z = adjust_one(v.z, corr, min_value);
+            v.w = adjust_one(v.w, corr, min_value);
+        }
+        if (NOISE)
+            v = poisson_counter4((double)v.x * mul, (double)v.y * mul, (double)v.z * mul, (double)v.w * mul, k0, k1,
+                                 stream, index_offset + 4ull * (unsigned long long)idx4);
+        out4[o] = v;
+    }
+}
+
+// Noise form for production sizes, two launches.
+//   k_extract4_noise2: every lane busy -- adjust, then phase 1 of the sampler (poisson_dev.h: poisson_phase1): the
+//                      "count is 0" shortcut of the low-lambda inversion, and the attempt-0 squeeze of PTRS run densely
+//                      over the wave's bright voxels (ballot compaction into a wave-private LDS list).  The ~1/3 of
+//                      bright voxels that still need the exact test or a retry, and the few low-lambda voxels whose
+//                      count may be >= 1, are appended to a work queue in HBM (per-block segments, LDS append counters:
+//                      one global counter would serialise at ~88 atomics/us chip-wide; bright items grow from the front
+//                      of the segment, inversion items from its back).
+//   k_poisson_resolve: one queue item per lane, looped until resolved; no LDS, no barriers, full occupancy, and
+//                      every lane starts with real work -- the divergent fp64 code (logs, divisions) no longer
+//                      runs once per voxel slot with 1-in-7 lanes active.
+// Same arithmetic per (voxel, attempt) as poisson_counter: bit-identical counts.
+template <bool ADJUST, bool CHECKED>
+__global__ __launch_bounds__(256) void k_extract4_noise2(const float* __restrict__ in, float* __restrict__ out,
+                                                         long long plane4, long long nzo, int inc, int idx_inc,
+                                                         const double* __restrict__ scal, float min_value, double mul,
+                                                         uint32_t k0, uint32_t k1, uint32_t stream,
+                                                         unsigned long long index_offset, PItem* __restrict__ queue,
+                                                         unsigned int* __restrict__ qcount, unsigned int segcap,
+                                                         const ExtractView* __restrict__ vt)
+{
+    if (vt) {
+        const ExtractView e = vt[blockIdx.y];
+        in = e.in; out = e.out; scal = e.scal; k0 = e.k0; k1 = e.k1; stream = e.stream;
+        queue = reinterpret_cast<PItem*>(e.queue); qcount = e.qcount;
+    }
+    __shared__ unsigned long long qctr;
+    __shared__ unsigned int qovf[2];
+    __shared__ P1Scratch scratch[4];
+    if (threadIdx.x == 0) { qctr = 0ull; qovf[0] = 0u; qovf[1] = 0u; }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    P1Args pa;
+    pa.mul = mul; pa.mulf = (float)mul; pa.k0 = k0; pa.k1 = k1; pa.stream = stream;
+    pa.seg = queue + (unsigned long long)blockIdx.x * segcap; pa.segcap = segcap; pa.ctr = &qctr; pa.ovf = qovf;
+    double corr = 1.0;
+    if (ADJUST) corr = scal[1];
+    const long long total4 = plane4 * nzo;
+    const long long nthreads = (long long)gridDim.x * 256;
+    const float4* __restrict__ in4 = reinterpret_cast<const float4*>(in);
+    float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
+    const bool small32 = total4 < (1ll << 32);
+    // the trip count is uniform per wave (lanes past the end carry invalid voxels): ballots need every lane
+    const long long wave_first = (long long)blockIdx.x * 256 + wave * 64;
+    for (long long o0 = wave_first; o0 < total4; o0 += nthreads) {
+        const long long o = o0 + lane;
+        const bool valid = o < total4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        long long src4 = o, idx4 = o;                 // where the voxels are read / what the RNG counter says they are
+        if (valid) {
+            if (inc != 1 || idx_inc != 1) {
+                const long long k = small32 ? (long long)((unsigned)o / (unsigned)plane4) : o / plane4;
+                src4 = k * inc * plane4 + (o - k * plane4);
+                idx4 = k * idx_inc * plane4 + (o - k * plane4);
+            }
+            v = in4[src4];
+            if (ADJUST) {
+                v.x = adjust_one(v.x, corr, min_value);
+                v.y = adjust_one(v.y, corr, min_value);
+                v.z = adjust_one(v.z, corr, min_value);
+                v.w = adjust_one(v.w, corr, min_value);
+            }
+        }
+        const float vv[4] = {v.x, v.y, v.z, v.w};
+        float ov[4];
+        poisson_phase1<CHECKED>(vv, valid, index_offset + 4ull * (unsigned long long)idx4, 4ull * (unsigned long long)o, pa, &scratch[wave], lane, ov);
+        if (valid) out4[o] = make_float4(ov[0], ov[1], ov[2], ov[3]);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        p1_publish(qcount + (size_t)QCOUNT_WORDS * blockIdx.x, qctr, qovf);
+        if (blockIdx.x == 0) p1_publish_header(qcount, gridDim.x, segcap);
+    }
+}
+
+// The same two-launch sampler for planes that are no multiple of four voxels (the reference's own 289^3 run: 83 521 voxels per
+// plane) or buffers that are not 16-byte aligned.  Philox groups are four consecutive voxels of the SOURCE index (poisson_dev.h),
+// and a plane then starts anywhere inside a group: a lane takes one group of one acquired plane -- up to four voxels, the ones
+// that fall inside the plane (scalar loads and stores under a mask; the others enter phase 1 as zeros, which it ignores) --, and the
+// 64 lanes of a wave take 64 consecutive groups of the SAME plane, so that a wave's outputs stay consecutive (what phase 1's pair
+// compaction assumes).  Same arithmetic per (voxel, attempt) as every other form: bit-identical counts.
+template <bool ADJUST, bool CHECKED>
+__global__ __launch_bounds__(256) void k_extract_noise2_any(const float* __restrict__ in, float* __restrict__ out,
+                                                            long long plane, long long nzo, int inc, int idx_inc,
+                                                            const double* __restrict__ scal, float min_value, double mul,
+                                                            uint32_t k0, uint32_t k1, uint32_t stream,
+                                                            unsigned long long index_offset, PItem* __restrict__ queue,
+                                                            unsigned int* __restrict__ qcount, unsigned int segcap,
+                                                            long long slots_per_plane, const ExtractView* __restrict__ vt)
+{
+    if (vt) {
+        const ExtractView e = vt[blockIdx.y];
+        in = e.in; out = e.out; scal = e.scal; k0 = e.k0; k1 = e.k1; stream = e.stream;
+        queue = reinterpret_cast<PItem*>(e.queue); qcount = e.qcount;
+    }
+    __shared__ unsigned long long qctr;
+    __shared__ unsigned int qovf[2];
+    __shared__ P1Scratch scratch[4];
+    if (threadIdx.x == 0) { qctr = 0ull; qovf[0] = 0u; qovf[1] = 0u; }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    P1Args pa;
+    pa.mul = mul; pa.mulf = (float)mul; pa.k0 = k0; pa.k1 = k1; pa.stream = stream;
+    pa.seg = queue + (unsigned long long)blockIdx.x * segcap; pa.segcap = segcap; pa.ctr = &qctr; pa.ovf = qovf;
+    double corr = 1.0;
+    if (ADJUST) corr = scal[1];
+    const long long slots = slots_per_plane * nzo;        // wave slots: 64 groups each
+    for (long long sl = (long long)blockIdx.x * 4 + wave; sl < slots; sl += (long long)gridDim.x * 4) {
+        const long long k = sl / slots_per_plane, jb = sl - k * slots_per_plane;
+        const unsigned long long ibase = index_offset + (unsigned long long)(k * idx_inc) * (unsigned long long)plane;   // RNG index of the plane's voxel 0
+        const unsigned long long g = (ibase >> 2) + (unsigned long long)(jb * 64 + lane);      // this lane's Philox group
+        const long long i0 = (long long)(4ull * g - ibase);                                   // its first voxel inside the plane (may be < 0)
+        const float* __restrict__ src = in + k * inc * plane;
+        float vv[4];
+        bool any = false;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const long long i = i0 + c;
+            const bool ok = i >= 0 && i < plane;
+            float v = 0.f;
+            if (ok) {
+                v = src[i];
+                if (ADJUST) v = adjust_one(v, corr, min_value);
+            }
+            vv[c] = ok ? v : 0.f;
+            any |= ok;
+        }
+        float ov[4];
+        // (output position of component 0; negative for a plane's first group when the plane starts inside it -- the valid components
+        // land at non-negative positions all the same, in 64-bit wrap-around arithmetic)
+        poisson_phase1<CHECKED>(vv, any, 4ull * g, (unsigned long long)(k * plane + i0), pa, &scratch[wave], lane, ov);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const long long i = i0 + c;
+            if (i >= 0 && i < plane) out[k * plane + i] = ov[c];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        p1_publish(qcount + (size_t)QCOUNT_WORDS * blockIdx.x, qctr, qovf);
+        if (blockIdx.x == 0) p1_publish_header(qcount, gridDim.x, segcap);
+    }
+}
+
+// One block per queue segment (same grid as k_extract4_noise2; the grid-stride walk of that kernel spreads the
+// bright voxels evenly over the segments).
+__global__ __launch_bounds__(256) void k_poisson_resolve(ResolveJob job, const ExtractView* __restrict__ vt)
+{
+    if (vt) {
+        const ExtractView e = vt[blockIdx.y];
+        job.out = e.out; job.queue = reinterpret_cast<const PItem*>(e.queue); job.qcount = e.qcount;
+        job.k0 = e.k0; job.k1 = e.k1; job.stream = e.stream;
+    }
+    __shared__ unsigned int ticket;
+    __shared__ double tab[RESOLVE_TAB];
+    resolve_segment_body(job, (long long)blockIdx.x, (int)threadIdx.x, &ticket, tab);
+}
+
+// Queues whose segments hold a SHARE of their blocks' voxels (poisson_queue_share < 16): the voxels a full segment refused, sampled
+// where they stand.  A kernel of its own so that this divergent fp64 code costs neither phase 1 nor the resolver a register; its blocks
+// return at once unless the resolver has recorded a refusal in the queue's header -- on the bench's volumes, always.
+constexpr int REFUSED_BLOCKS = 2048;
+constexpr unsigned int REFUSED_LIST = 4096;                // positions the block gathers before it samples them (16 KB of LDS)
+__global__ __launch_bounds__(256) void k_poisson_refused(ResolveJob job, int segments, unsigned int full_items, unsigned int* hint,
+                                                         const ExtractView* __restrict__ vt)
+{
+    if (vt) {
+        const ExtractView e = vt[blockIdx.y];
+        job.out = e.out; job.qcount = e.qcount; job.k0 = e.k0; job.k1 = e.k1; job.stream = e.stream;
+    }
+    if (job.qcount[QCOUNT_HEADER + 2] == 0u) return;                 // no block of this view was refused anything (the resolver's word)
+    __shared__ unsigned int list[REFUSED_LIST];
+    __shared__ unsigned int count;
+    const int t = (int)threadIdx.x;
+    if (t == 0) count = 0u;
+    __syncthreads();
+    // refused voxels are a few per cent of a block's voxels, scattered: sampled where the walk finds them, one lane in twenty would work.
+    // So the walk only gathers positions, and the list is sampled whenever another trip (1024 candidates) might not fit: all lanes busy.
+    auto flush = [&]() {
+        __syncthreads();                                              // the list is complete
+        const unsigned int m = count;
+        for (unsigned int i = (unsigned int)t; i < m; i += 256u) {
+            const unsigned int o = list[i];
+            job.out[o] = resolve_in_place(-job.out[o], job, resolve_index_of(job, o));
+        }
+        __syncthreads();                                              // every lane has read `count` and its entries
+        if (t == 0) count = 0u;
+        __syncthreads();
+    };
+    unsigned int need = 0u;                                           // sixteenths of its voxels the fullest of this block's segments had pending
+    for (int seg = (int)blockIdx.x; seg < segments; seg += (int)gridDim.x) {
+        const unsigned int* qc = job.qcount + (size_t)QCOUNT_WORDS * seg;
+        if (qc[2] == 0u) continue;                                    // block-uniform
+        const unsigned int sixteenths = (unsigned int)((16ull * (qc[0] + qc[1] + qc[2]) + full_items - 1u) / full_items);
+        need = sixteenths > need ? sixteenths : need;
+        for (long long trip = 0;; ++trip) {
+            if (!refused_collect(job, seg, trip, t, segments, list, &count)) break;      // block-uniform
+            __syncthreads();
+            const unsigned int gathered = count;                      // the same for every lane: read between two barriers
+            __syncthreads();
+            if (gathered + 1024u > REFUSED_LIST) flush();             // the next trip adds up to 1024 positions
+        }
+    }
+    flush();
+    // what a context on the automatic share builds its next queue with (api.cpp: queue_mode_next reads the word without synchronising)
+    if (t == 0 && hint && need != 0u) __hip_atomic_fetch_max(hint, need > 16u ? 16u : need, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// two run-time flags -> a kernel's two template arguments
+template <class F> static void dispatch2(bool a, bool b, F&& f)
+{
+    auto second = [&](auto A) { if (b) f(A, std::true_type{}); else f(A, std::false_type{}); };
+    if (a) second(std::true_type{}); else second(std::false_type{});
+}
+
+// The second launch of the sampler: one block per queue segment, and behind it -- where the segments can refuse (pl.checked) -- the walk
+// over what they refused.  The fused tail of the convolution, whose pass E has run phase 1, ends here too.
+int launch_resolve(hipStream_t s, const ExtractPlan& pl, const ExtractOps& o)
+{
+    const ExtractGeom& g = pl.geom;
+    const unsigned gy = o.nviews > 0 ? (unsigned)o.nviews : 1u;
+    const QueueLayout::Region q = pl.layout.region(o.queue_ws);
+    const bool any = pl.kernel == EXTRACT_K_NOISE2_ANY;
+    // how phase 1 walked the volume (ResolveJob): float4 groups, or wave slots of slots_per_plane per plane
+    const long long walk_n = pl.kernel == EXTRACT_K_NOISE2 ? g.plane * g.nzo / 4 : (any ? pl.slots_per_plane * g.nzo : 0);
+    const ResolveJob job{o.out, reinterpret_cast<const PItem*>(q.items), q.counts, pl.segcap, o.mul, (uint32_t)o.seed, (uint32_t)(o.seed >> 32), o.stream,
+                         (unsigned int)g.plane, (unsigned int)g.index_inc, (unsigned long long)g.index_offset, pl.checked ? (any ? 2 : 1) : 0,
+                         walk_n, any ? pl.slots_per_plane : 0};
+    hipLaunchKernelGGL(k_poisson_resolve, dim3(pl.blocks, gy), dim3(256), 0, s, job, o.vt);
+    if (job.walk != 0)
+        hipLaunchKernelGGL(k_poisson_refused, dim3(pl.blocks < REFUSED_BLOCKS ? pl.blocks : REFUSED_BLOCKS, gy), dim3(256), 0, s, job, pl.blocks,
+                           pl.full_items, pl.hint, o.vt);
+    MVSIM_HIP(hipGetLastError());
+    return MVSIM_OK;
+}
+
+int launch_extract(hipStream_t s, const ExtractPlan& pl, const ExtractOps& o)
+{
+    const ExtractGeom& g = pl.geom;
+    const dim3 grid(pl.blocks, o.nviews > 0 ? (unsigned)o.nviews : 1u), block(256);
+    const float* in = o.in ? o.in + g.in_offset : nullptr;
+    const uint32_t k0 = (uint32_t)o.seed, k1 = (uint32_t)(o.seed >> 32);
+    const unsigned long long offset = g.index_offset;
+    if (pl.kernel == EXTRACT_K_NOISE2 || pl.kernel == EXTRACT_K_NOISE2_ANY) {
+        const QueueLayout::Region q = pl.layout.region(o.queue_ws);
+        PItem* queue = reinterpret_cast<PItem*>(q.items);
+        dispatch2(o.adjust, pl.checked, [&](auto A, auto C) {
+            if (pl.kernel == EXTRACT_K_NOISE2)
+                hipLaunchKernelGGL((k_extract4_noise2<decltype(A)::value, decltype(C)::value>), grid, block, 0, s, in, o.out, g.plane / 4, g.nzo, g.inc,
+                                   g.index_inc, o.scal, o.min_value, o.mul, k0, k1, o.stream, offset, queue, q.counts, pl.segcap, o.vt);
+            else       // planes that are no multiple of four voxels / unaligned buffers: the same two launches, group by group
+                hipLaunchKernelGGL((k_extract_noise2_any<decltype(A)::value, decltype(C)::value>), grid, block, 0, s, in, o.out, g.plane, g.nzo, g.inc,
+                                   g.index_inc, o.scal, o.min_value, o.mul, k0, k1, o.stream, offset, queue, q.counts, pl.segcap, pl.slots_per_plane, o.vt);
+        });
+        return launch_resolve(s, pl, o);
+    }
+    dispatch2(o.adjust, o.noise, [&](auto A, auto N) {
+        if (pl.kernel == EXTRACT_K_VEC)
+            hipLaunchKernelGGL((k_extract4<decltype(A)::value, decltype(N)::value>), grid, block, 0, s, in, o.out, g.plane / 4, g.nzo, g.inc, g.index_inc,
+                               o.scal, o.min_value, o.mul, k0, k1, o.stream, offset, o.vt);
+        else
+            hipLaunchKernelGGL((k_extract<decltype(A)::value, decltype(N)::value>), grid, block, 0, s, in, o.out, g.plane, g.nzo, g.inc, g.index_inc,
+                               o.scal, o.min_value, o.mul, k0, k1, o.stream, offset, o.vt);
+    });
+    MVSIM_HIP(hipGetLastError());
+    return MVSIM_OK;
+}
+
+void extract_path(const int64_t dim[3], int inc, int index_inc, uint64_t index_offset, bool aligned16, int qshare, int64_t path[4])
+{
+    ExtractGeom g = ExtractGeom::strided(dim, inc);
+    if (index_inc > 0) g.index_inc = index_inc;
+    g.index_offset = index_offset;
+    const ExtractPlan pl = extract_plan(g, aligned16, true, QueueMode{qshare, nullptr});
+    path[0] = pl.kernel; path[1] = pl.checked ? 1 : 0; path[2] = pl.blocks; path[3] = pl.segcap;
+}
+
+// What the last two-launch sampler that used this workspace queued (mvsim_get_queue_stats): {items a segment holds, bright items,
+// inversion items, voxels refused and sampled in place, pending voxels of the fullest block}.  The caller has synchronised the stream.
+int poisson_queue_read_stats(const void* queue_ws, size_t bytes, long long stats[5])
+{
+    stats[0] = stats[1] = stats[2] = stats[3] = stats[4] = 0;
+    if (!queue_ws || bytes < QueueLayout(0, 0, true).total_bytes) return MVSIM_OK;   // not a queue of the two-launch sampler
+    std::vector<unsigned int> h((size_t)QCOUNT_HEADER + 2);
+    MVSIM_HIP(hipMemcpy(h.data(), queue_ws, h.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    const unsigned int blocks = h[QCOUNT_HEADER] <= (unsigned int)POISSON_MAX_BLOCKS ? h[QCOUNT_HEADER] : 0u;
+    stats[0] = h[(size_t)QCOUNT_HEADER + 1];
+    stats[1] = stats[2] = stats[3] = stats[4] = 0;
+    for (unsigned int b = 0; b < blocks; ++b) {
+        const long long f = h[(size_t)QCOUNT_WORDS * b], k = h[(size_t)QCOUNT_WORDS * b + 1], r = h[(size_t)QCOUNT_WORDS * b + 2];
+        stats[1] += f;
+        stats[2] += k;
+        stats[3] += r;
+        if (f + k + r > stats[4]) stats[4] = f + k + r;     // what the fullest block had to settle: the segment size that refuses nothing
+    }
+    return MVSIM_OK;
+}
+
+}  // namespace mvsim

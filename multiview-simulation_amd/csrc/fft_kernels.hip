@@ -1789,31 +1789,34 @@ static int ensure_box_weights(mvsim_ctx* ctx, int N, int P, int len, bool half, 
     return MVSIM_OK;
 }
 
-// Geometry of the fused tail: pass E blocks own queue segments that can hold every voxel of their rows.
-static bool fused_tail_of(const ConvPlan& pl, int inc, bool con_wanted, long long* blocks, unsigned int* segcap)
+// The plan of the fused tail: pass E blocks own queue segments that can hold every voxel of their rows (QueueLayout without the header:
+// there may be more than POISSON_MAX_BLOCKS of them), and the resolver counts the RNG in source planes, whichever planes pass E wrote.
+static bool fused_tail_of(const ConvPlan& pl, int inc, bool con_wanted, ExtractPlan* fp)
 {
     if (!pl.early || (pl.n[0] & 3) != 0) return false;
+    const int64_t dim[3] = {pl.n[0], pl.n[1], pl.n[2]};
     const long long nk = con_wanted ? pl.n[2] : (pl.n[2] - 1) / inc + 1;
     const long long rows = pl.n[1] * nk;
     if (rows * pl.n[0] >= (1ll << 32)) return false;               // work items carry the output position in 32 bits
-    *blocks = (rows + pl.e_rows - 1) / pl.e_rows;
-    *segcap = (unsigned int)(pl.e_rows * pl.n[0]);
+    *fp = ExtractPlan{};
+    fp->geom = ExtractGeom::compact(dim, inc);                     // (the acquisition's planes, whichever planes pass E walks)
+    fp->kernel = EXTRACT_FUSED_TAIL; fp->share = 16;
+    fp->blocks = (int)((rows + pl.e_rows - 1) / pl.e_rows);
+    fp->segcap = fp->full_items = (unsigned int)(pl.e_rows * pl.n[0]);
+    fp->layout = QueueLayout(fp->blocks, fp->segcap, false);
     return true;
 }
 
-bool fused_tail_geometry(const int64_t dim[3], const int64_t kdim[3], int inc, bool con_wanted, const Options& opt, long long* blocks, unsigned int* segcap)
+bool fused_tail_geometry(const int64_t dim[3], const int64_t kdim[3], int inc, bool con_wanted, const Options& opt, ExtractPlan* fp)
 {
     ConvPlan pl;
-    return conv_plan(dim, kdim, opt, &pl) && fused_tail_of(pl, inc, con_wanted, blocks, segcap);
+    return conv_plan(dim, kdim, opt, &pl) && fused_tail_of(pl, inc, con_wanted, fp);
 }
 
 size_t fused_tail_queue_bytes(const int64_t dim[3], const int64_t kdim[3], int inc, bool con_wanted, const Options& opt)
 {
-    long long blocks = 0;
-    unsigned int segcap = 0;
-    if (!fused_tail_geometry(dim, kdim, inc, con_wanted, opt, &blocks, &segcap)) return 0;
-    const size_t counts = ((size_t)QCOUNT_WORDS * blocks * sizeof(unsigned int) + 255) & ~(size_t)255;
-    return counts + (size_t)blocks * segcap * sizeof(PItem);
+    ExtractPlan fp{};
+    return fused_tail_geometry(dim, kdim, inc, con_wanted, opt, &fp) ? fp.layout.total_bytes : 0;
 }
 
 void custom_fft_release(mvsim_ctx* ctx)
@@ -2172,7 +2175,7 @@ static int pass_d(mvsim_ctx* ctx, const ConvRun& r, float2* dst)
 
 // Fused tail: what pass E needs to adjust, extract and sample.  adjustImage's factor must exist before pass E runs:
 // (target - min) / (sum / n) from the early sum.
-static int fused_tail_args(mvsim_ctx* ctx, const ConvRun& r, const ConvTail& tail, long long fblocks, unsigned int fsegcap, C2RFuse* fz)
+static int fused_tail_args(mvsim_ctx* ctx, const ConvRun& r, const ConvTail& tail, const ExtractPlan& fp, C2RFuse* fz)
 {
     if (!tail.corr_done) {
         ev_begin(ctx, ST_ADJUST);
@@ -2183,14 +2186,13 @@ static int fused_tail_args(mvsim_ctx* ctx, const ConvRun& r, const ConvTail& tai
     fz->acq_every = tail.con_adj ? tail.inc : 1; fz->idx_zstride = r.zstride; fz->noise = tail.noise ? 1 : 0;
     fz->mul = tail.mul; fz->k0 = (uint32_t)tail.seed; fz->k1 = (uint32_t)(tail.seed >> 32); fz->stream = tail.stream;
     if (tail.noise) {
-        const size_t counts = ((size_t)QCOUNT_WORDS * fblocks * sizeof(unsigned int) + 255) & ~(size_t)255;
-        if (ctx->pqueue.bytes < counts + (size_t)fblocks * fsegcap * sizeof(PItem)) {
+        if (ctx->pqueue.bytes < fp.layout.total_bytes) {
             set_error("fused tail: queue workspace not reserved");
             return MVSIM_EINVAL;
         }
-        fz->qcount = ctx->pqueue.as<unsigned int>();
-        fz->queue = reinterpret_cast<PItem*>(ctx->pqueue.as<char>() + counts);
-        fz->segcap = fsegcap;
+        const QueueLayout::Region q = fp.layout.region(ctx->pqueue.p);
+        fz->qcount = q.counts; fz->queue = reinterpret_cast<PItem*>(q.items);
+        fz->segcap = fp.segcap;
     }
     return MVSIM_OK;
 }
@@ -2224,13 +2226,12 @@ int custom_fft_convolve_slab(mvsim_ctx* ctx, const float* img, const int64_t dim
     // k * zstride of the SLAB are planes k' * zstride of the view)
     r.zstride = (tail && pl.early && tail->zstride > 1 && (!r.is_slab || slab.z_out0 % tail->zstride == 0)) ? tail->zstride : 1;
     // fused tail: pass E adjusts, extracts and samples (needs the sum first, whole rows of float4 groups, aligned outputs)
-    long long fblocks = 0;
-    unsigned int fsegcap = 0;
+    ExtractPlan fp{};
     const bool fuse = tail && tail->want_fuse && !r.is_slab && tail->acq &&
-                      fused_tail_of(pl, tail->inc, tail->con_adj != nullptr, &fblocks, &fsegcap) &&
+                      fused_tail_of(pl, tail->inc, tail->con_adj != nullptr, &fp) &&
                       ((reinterpret_cast<uintptr_t>(tail->acq) | reinterpret_cast<uintptr_t>(tail->con_adj)) & 15) == 0;
     if (fuse) r.zstride = tail->con_adj ? 1 : tail->inc;
-    if (tail) { tail->zstride = r.zstride; tail->fused = fuse; }
+    if (tail) { tail->zstride = r.zstride; tail->fused = fuse; tail->fused_blocks = fp.blocks; tail->fused_segcap = fp.segcap; }
     // adjustImage's factor rides in the reduction of the sum when the caller described it (a view; not the stage operator)
     r.corr_n = (tail && tail->corr_n > 0 && !r.is_slab) ? tail->corr_n : 0;
     r.corr_min = tail ? tail->min_value : 0.f; r.corr_target = tail ? tail->target_average : 1.f;
@@ -2292,7 +2293,7 @@ int custom_fft_convolve_slab(mvsim_ctx* ctx, const float* img, const int64_t dim
     float2* Fz = pl.zdirect ? r.G : r.F;                            // where pass D leaves the z-convolved spectrum for pass E
     MVSIM_TRY(pass_d(ctx, r, Fz));
     C2RFuse fz{};
-    if (fuse) MVSIM_TRY(fused_tail_args(ctx, r, *tail, fblocks, fsegcap, &fz));
+    if (fuse) MVSIM_TRY(fused_tail_args(ctx, r, *tail, fp, &fz));
     ev_begin(ctx, ST_PASS_E);
     // both half spectra carry the factor 2 left in by pass A (see k_fft_x_r2c): 2 * 2 = 4
     const float scale = (float)(0.25 / ((double)pl.px * (double)pl.py * ((pl.zdirect && !r.zinline) ? 1.0 : (double)pl.pz)));
@@ -2300,7 +2301,7 @@ int custom_fft_convolve_slab(mvsim_ctx* ctx, const float* img, const int64_t dim
     MVSIM_TRY(r.xlen->c2r(ctx, Fz, out, r.tw_m, r.tw_px, pl.hxp, pl.py * r.zstride, pl.n[0], pl.n[1], (long long)pl.n[1] * r.nk, scale,
                          pl.early ? nullptr : ctx->partials_e.as<double>(), &nblk, fuse ? &fz : nullptr,
                          C2REmpty{r.pnz_dil, r.zstride}));
-    if (fuse && nblk != (int)fblocks) { set_error("fused tail: block count mismatch"); return MVSIM_EINVAL; }
+    if (fuse && nblk != fp.blocks) { set_error("fused tail: block count mismatch"); return MVSIM_EINVAL; }
     if (!pl.early) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, s, ctx->partials_e.as<double>(), (long long)nblk, r.scal, 1.0,
                                       r.corr_n, r.corr_min, r.corr_target);
     MVSIM_HIP(hipGetLastError());
@@ -2308,8 +2309,9 @@ int custom_fft_convolve_slab(mvsim_ctx* ctx, const float* img, const int64_t dim
     if (fuse && tail->noise) {
         ev_end(ctx, ST_CONVOLVE);
         ev_begin(ctx, ST_EXTRACT);
-        MVSIM_TRY(launch_poisson_resolve(s, tail->acq, fz.queue, fz.qcount, (int)fblocks, fsegcap, tail->mul, tail->seed, tail->stream,
-                                         (long long)pl.n[0] * pl.n[1], fz.acq_every * fz.idx_zstride, 0));
+        ExtractOps ops;
+        ops.out = tail->acq; ops.queue_ws = ctx->pqueue.p; ops.mul = tail->mul; ops.seed = tail->seed; ops.stream = tail->stream;
+        MVSIM_TRY(launch_resolve(s, fp, ops));
         ev_end(ctx, ST_EXTRACT);
         return MVSIM_OK;
     }

@@ -1,8 +1,6 @@
-// Streaming kernels of the per-view path (gfx950, wave64): rotate, attenuate, sum/adjust,
-// slice extraction + Poisson, makeIsotropic, weight image.  All are HBM-bound; design notes and
+// Streaming kernels of the per-view path (gfx950, wave64): rotate, attenuate, sum/adjust, the 16-bit
+// pack of acquisitions, makeIsotropic, weight image (slice extraction + Poisson: extract.hip).  All are HBM-bound; design notes and
 // algorithmic bytes per voxel are in DESIGN.md.
-#include <vector>
-
 #include "common.h"
 #include "poisson_dev.h"
 
@@ -726,537 +724,6 @@ int launch_norm_apply(hipStream_t s, float* img, int64_t n, const double* scal)
     hipLaunchKernelGGL(k_norm_apply, dim3(blocks), dim3(256), 0, s, img, (long long)n, scal);
     MVSIM_HIP(hipGetLastError());
     return MVSIM_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// extractSlices + adjust + Poisson (SimulateMultiViewDataset.java:195-251, Tools.java:73-86):
-// out[x,y,k] = f(in[x,y,k*inc]);  ADJUST applies the two adjustImage passes on the fly (fused
-// path: the scaled volume is never materialised); NOISE draws Poisson((double)v * mul).
-// ------------------------------------------------------------------------------------------------
-template <bool ADJUST, bool NOISE>
-__global__ __launch_bounds__(256) void k_extract(const float* __restrict__ in, float* __restrict__ out,
-                                                 long long plane, long long nzo, int inc, int idx_inc,
-                                                 const double* __restrict__ scal, float min_value, double mul,
-                                                 uint32_t k0, uint32_t k1, uint32_t stream,
-                                                 unsigned long long index_offset, const ExtractView* __restrict__ vt)
-{
-    if (vt) { const ExtractView e = vt[blockIdx.y]; in = e.in; out = e.out; scal = e.scal; k0 = e.k0; k1 = e.k1; stream = e.stream; }
-    double corr = 1.0;
-    if (ADJUST) corr = scal[1];
-    const long long total = plane * nzo;
-    const long long nthreads = (long long)gridDim.x * 256;
-    for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < total; o += nthreads) {
-        const long long k = o / plane;
-        const long long i = o - k * plane;
-        const long long src = k * inc * plane + i;
-        float v = in[src];
-        if (ADJUST) v = adjust_one(v, corr, min_value);
-        if (NOISE) v = poisson_counter((double)v * mul, k0, k1, stream, index_offset + (unsigned long long)(k * idx_inc * plane + i));
-        out[o] = v;
-    }
-}
-
-// Vector form: 4 consecutive voxels per lane (16-B loads/stores); the lane's 4 voxels are exactly one
-// Philox group.  Requires plane % 4 == 0, index_offset % 4 == 0 and 16-B aligned buffers.
-template <bool ADJUST, bool NOISE>
-__global__ __launch_bounds__(256) void k_extract4(const float* __restrict__ in, float* __restrict__ out,
-                                                  long long plane4, long long nzo, int inc, int idx_inc,
-                                                  const double* __restrict__ scal, float min_value, double mul,
-                                                  uint32_t k0, uint32_t k1, uint32_t stream,
-                                                  unsigned long long index_offset, const ExtractView* __restrict__ vt)
-{
-    if (vt) { const ExtractView e = vt[blockIdx.y]; in = e.in; out = e.out; scal = e.scal; k0 = e.k0; k1 = e.k1; stream = e.stream; }
-    double corr = 1.0;
-    if (ADJUST) corr = scal[1];
-    const long long total4 = plane4 * nzo;
-    const long long nthreads = (long long)gridDim.x * 256;
-    const float4* __restrict__ in4 = reinterpret_cast<const float4*>(in);
-    float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
-    const bool small32 = total4 < (1ll << 32);
-    for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < total4; o += nthreads) {
-        long long src4 = o, idx4 = o;                 // where the voxels are read / what the RNG counter says they are
-        if (inc != 1 || idx_inc != 1) {
-            const long long k = small32 ? (long long)((unsigned)o / (unsigned)plane4) : o / plane4;
-            src4 = k * inc * plane4 + (o - k * plane4);
-            idx4 = k * idx_inc * plane4 + (o - k * plane4);
-        }
-        float4 v = in4[src4];
-        if (ADJUST) {
-            v.x = adjust_one(v.x, corr, min_value);
-            v.y = adjust_one(v.y, corr, min_value);
-            v.z = adjust_one(v.z, corr, min_value);
-            v.w = adjust_one(v.w, corr, min_value);
-        }
-        if (NOISE)
-            v = poisson_counter4((double)v.x * mul, (double)v.y * mul, (double)v.z * mul, (double)v.w * mul, k0, k1,
-                                 stream, index_offset + 4ull * (unsigned long long)idx4);
-        out4[o] = v;
-    }
-}
-
-// Noise form for production sizes, two launches.
-//   k_extract4_noise2: every lane busy -- adjust, then phase 1 of the sampler (poisson_dev.h: poisson_phase1): the
-//                      "count is 0" shortcut of the low-lambda inversion, and the attempt-0 squeeze of PTRS run densely
-//                      over the wave's bright voxels (ballot compaction into a wave-private LDS list).  The ~1/3 of
-//                      bright voxels that still need the exact test or a retry, and the few low-lambda voxels whose
-//                      count may be >= 1, are appended to a work queue in HBM (per-block segments, LDS append counters:
-//                      one global counter would serialise at ~88 atomics/us chip-wide; bright items grow from the front
-//                      of the segment, inversion items from its back).
-//   k_poisson_resolve: one queue item per lane, looped until resolved; no LDS, no barriers, full occupancy, and
-//                      every lane starts with real work -- the divergent fp64 code (logs, divisions) no longer
-//                      runs once per voxel slot with 1-in-7 lanes active.
-// Same arithmetic per (voxel, attempt) as poisson_counter: bit-identical counts.
-template <bool ADJUST, bool CHECKED>
-__global__ __launch_bounds__(256) void k_extract4_noise2(const float* __restrict__ in, float* __restrict__ out,
-                                                         long long plane4, long long nzo, int inc, int idx_inc,
-                                                         const double* __restrict__ scal, float min_value, double mul,
-                                                         uint32_t k0, uint32_t k1, uint32_t stream,
-                                                         unsigned long long index_offset, PItem* __restrict__ queue,
-                                                         unsigned int* __restrict__ qcount, unsigned int segcap,
-                                                         const ExtractView* __restrict__ vt)
-{
-    if (vt) {
-        const ExtractView e = vt[blockIdx.y];
-        in = e.in; out = e.out; scal = e.scal; k0 = e.k0; k1 = e.k1; stream = e.stream;
-        queue = reinterpret_cast<PItem*>(e.queue); qcount = e.qcount;
-    }
-    __shared__ unsigned long long qctr;
-    __shared__ unsigned int qovf[2];
-    __shared__ P1Scratch scratch[4];
-    if (threadIdx.x == 0) { qctr = 0ull; qovf[0] = 0u; qovf[1] = 0u; }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    P1Args pa;
-    pa.mul = mul; pa.mulf = (float)mul; pa.k0 = k0; pa.k1 = k1; pa.stream = stream;
-    pa.seg = queue + (unsigned long long)blockIdx.x * segcap; pa.segcap = segcap; pa.ctr = &qctr; pa.ovf = qovf;
-    double corr = 1.0;
-    if (ADJUST) corr = scal[1];
-    const long long total4 = plane4 * nzo;
-    const long long nthreads = (long long)gridDim.x * 256;
-    const float4* __restrict__ in4 = reinterpret_cast<const float4*>(in);
-    float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
-    const bool small32 = total4 < (1ll << 32);
-    // the trip count is uniform per wave (lanes past the end carry invalid voxels): ballots need every lane
-    const long long wave_first = (long long)blockIdx.x * 256 + wave * 64;
-    for (long long o0 = wave_first; o0 < total4; o0 += nthreads) {
-        const long long o = o0 + lane;
-        const bool valid = o < total4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        long long src4 = o, idx4 = o;                 // where the voxels are read / what the RNG counter says they are
-        if (valid) {
-            if (inc != 1 || idx_inc != 1) {
-                const long long k = small32 ? (long long)((unsigned)o / (unsigned)plane4) : o / plane4;
-                src4 = k * inc * plane4 + (o - k * plane4);
-                idx4 = k * idx_inc * plane4 + (o - k * plane4);
-            }
-            v = in4[src4];
-            if (ADJUST) {
-                v.x = adjust_one(v.x, corr, min_value);
-                v.y = adjust_one(v.y, corr, min_value);
-                v.z = adjust_one(v.z, corr, min_value);
-                v.w = adjust_one(v.w, corr, min_value);
-            }
-        }
-        const float vv[4] = {v.x, v.y, v.z, v.w};
-        float ov[4];
-        poisson_phase1<CHECKED>(vv, valid, index_offset + 4ull * (unsigned long long)idx4, 4ull * (unsigned long long)o, pa, &scratch[wave], lane, ov);
-        if (valid) out4[o] = make_float4(ov[0], ov[1], ov[2], ov[3]);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        p1_publish(qcount + (size_t)QCOUNT_WORDS * blockIdx.x, qctr, qovf);
-        if (blockIdx.x == 0) p1_publish_header(qcount, gridDim.x, segcap);
-    }
-}
-
-// The same two-launch sampler for planes that are no multiple of four voxels (the reference's own 289^3 run: 83 521 voxels per
-// plane) or buffers that are not 16-byte aligned.  Philox groups are four consecutive voxels of the SOURCE index (poisson_dev.h),
-// and a plane then starts anywhere inside a group: a lane takes one group of one acquired plane -- up to four voxels, the ones
-// that fall inside the plane (scalar loads and stores under a mask; the others enter phase 1 as zeros, which it ignores) --, and the
-// 64 lanes of a wave take 64 consecutive groups of the SAME plane, so that a wave's outputs stay consecutive (what phase 1's pair
-// compaction assumes).  Same arithmetic per (voxel, attempt) as every other form: bit-identical counts.
-template <bool ADJUST, bool CHECKED>
-__global__ __launch_bounds__(256) void k_extract_noise2_any(const float* __restrict__ in, float* __restrict__ out,
-                                                            long long plane, long long nzo, int inc, int idx_inc,
-                                                            const double* __restrict__ scal, float min_value, double mul,
-                                                            uint32_t k0, uint32_t k1, uint32_t stream,
-                                                            unsigned long long index_offset, PItem* __restrict__ queue,
-                                                            unsigned int* __restrict__ qcount, unsigned int segcap,
-                                                            long long slots_per_plane, const ExtractView* __restrict__ vt)
-{
-    if (vt) {
-        const ExtractView e = vt[blockIdx.y];
-        in = e.in; out = e.out; scal = e.scal; k0 = e.k0; k1 = e.k1; stream = e.stream;
-        queue = reinterpret_cast<PItem*>(e.queue); qcount = e.qcount;
-    }
-    __shared__ unsigned long long qctr;
-    __shared__ unsigned int qovf[2];
-    __shared__ P1Scratch scratch[4];
-    if (threadIdx.x == 0) { qctr = 0ull; qovf[0] = 0u; qovf[1] = 0u; }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    P1Args pa;
-    pa.mul = mul; pa.mulf = (float)mul; pa.k0 = k0; pa.k1 = k1; pa.stream = stream;
-    pa.seg = queue + (unsigned long long)blockIdx.x * segcap; pa.segcap = segcap; pa.ctr = &qctr; pa.ovf = qovf;
-    double corr = 1.0;
-    if (ADJUST) corr = scal[1];
-    const long long slots = slots_per_plane * nzo;        // wave slots: 64 groups each
-    for (long long sl = (long long)blockIdx.x * 4 + wave; sl < slots; sl += (long long)gridDim.x * 4) {
-        const long long k = sl / slots_per_plane, jb = sl - k * slots_per_plane;
-        const unsigned long long ibase = index_offset + (unsigned long long)(k * idx_inc) * (unsigned long long)plane;   // RNG index of the plane's voxel 0
-        const unsigned long long g = (ibase >> 2) + (unsigned long long)(jb * 64 + lane);      // this lane's Philox group
-        const long long i0 = (long long)(4ull * g - ibase);                                   // its first voxel inside the plane (may be < 0)
-        const float* __restrict__ src = in + k * inc * plane;
-        float vv[4];
-        bool any = false;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const long long i = i0 + c;
-            const bool ok = i >= 0 && i < plane;
-            float v = 0.f;
-            if (ok) {
-                v = src[i];
-                if (ADJUST) v = adjust_one(v, corr, min_value);
-            }
-            vv[c] = ok ? v : 0.f;
-            any |= ok;
-        }
-        float ov[4];
-        // (output position of component 0; negative for a plane's first group when the plane starts inside it -- the valid components
-        // land at non-negative positions all the same, in 64-bit wrap-around arithmetic)
-        poisson_phase1<CHECKED>(vv, any, 4ull * g, (unsigned long long)(k * plane + i0), pa, &scratch[wave], lane, ov);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const long long i = i0 + c;
-            if (i >= 0 && i < plane) out[k * plane + i] = ov[c];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        p1_publish(qcount + (size_t)QCOUNT_WORDS * blockIdx.x, qctr, qovf);
-        if (blockIdx.x == 0) p1_publish_header(qcount, gridDim.x, segcap);
-    }
-}
-
-// One block per queue segment (same grid as k_extract4_noise2; the grid-stride walk of that kernel spreads the
-// bright voxels evenly over the segments).
-__global__ __launch_bounds__(256) void k_poisson_resolve(ResolveJob job, const ExtractView* __restrict__ vt)
-{
-    if (vt) {
-        const ExtractView e = vt[blockIdx.y];
-        job.out = e.out; job.queue = reinterpret_cast<const PItem*>(e.queue); job.qcount = e.qcount;
-        job.k0 = e.k0; job.k1 = e.k1; job.stream = e.stream;
-    }
-    __shared__ unsigned int ticket;
-    __shared__ double tab[RESOLVE_TAB];
-    resolve_segment_body(job, (long long)blockIdx.x, (int)threadIdx.x, &ticket, tab);
-}
-
-// Queues whose segments hold a SHARE of their blocks' voxels (poisson_queue_share < 16): the voxels a full segment refused, sampled
-// where they stand.  A kernel of its own so that this divergent fp64 code costs neither phase 1 nor the resolver a register; its blocks
-// return at once unless the resolver has recorded a refusal in the queue's header -- on the bench's volumes, always.
-constexpr int REFUSED_BLOCKS = 2048;
-constexpr unsigned int REFUSED_LIST = 4096;                // positions the block gathers before it samples them (16 KB of LDS)
-__global__ __launch_bounds__(256) void k_poisson_refused(ResolveJob job, int segments, unsigned int full_items, unsigned int* hint,
-                                                         const ExtractView* __restrict__ vt)
-{
-    if (vt) {
-        const ExtractView e = vt[blockIdx.y];
-        job.out = e.out; job.qcount = e.qcount; job.k0 = e.k0; job.k1 = e.k1; job.stream = e.stream;
-    }
-    if (job.qcount[QCOUNT_HEADER + 2] == 0u) return;                 // no block of this view was refused anything (the resolver's word)
-    __shared__ unsigned int list[REFUSED_LIST];
-    __shared__ unsigned int count;
-    const int t = (int)threadIdx.x;
-    if (t == 0) count = 0u;
-    __syncthreads();
-    // refused voxels are a few per cent of a block's voxels, scattered: sampled where the walk finds them, one lane in twenty would work.
-    // So the walk only gathers positions, and the list is sampled whenever another trip (1024 candidates) might not fit: all lanes busy.
-    auto flush = [&]() {
-        __syncthreads();                                              // the list is complete
-        const unsigned int m = count;
-        for (unsigned int i = (unsigned int)t; i < m; i += 256u) {
-            const unsigned int o = list[i];
-            job.out[o] = resolve_in_place(-job.out[o], job, resolve_index_of(job, o));
-        }
-        __syncthreads();                                              // every lane has read `count` and its entries
-        if (t == 0) count = 0u;
-        __syncthreads();
-    };
-    unsigned int need = 0u;                                           // sixteenths of its voxels the fullest of this block's segments had pending
-    for (int seg = (int)blockIdx.x; seg < segments; seg += (int)gridDim.x) {
-        const unsigned int* qc = job.qcount + (size_t)QCOUNT_WORDS * seg;
-        if (qc[2] == 0u) continue;                                    // block-uniform
-        const unsigned int sixteenths = (unsigned int)((16ull * (qc[0] + qc[1] + qc[2]) + full_items - 1u) / full_items);
-        need = sixteenths > need ? sixteenths : need;
-        for (long long trip = 0;; ++trip) {
-            if (!refused_collect(job, seg, trip, t, segments, list, &count)) break;      // block-uniform
-            __syncthreads();
-            const unsigned int gathered = count;                      // the same for every lane: read between two barriers
-            __syncthreads();
-            if (gathered + 1024u > REFUSED_LIST) flush();             // the next trip adds up to 1024 positions
-        }
-    }
-    flush();
-    // what a context on the automatic share builds its next queue with (api.cpp: queue_mode_next reads the word without synchronising)
-    if (t == 0 && hint && need != 0u) __hip_atomic_fetch_max(hint, need > 16u ? 16u : need, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-int launch_poisson_resolve(hipStream_t s, float* out, void* queue_items, const unsigned int* qcount, int segments, unsigned int segcap,
-                           double mul, uint64_t seed, uint32_t stream, long long plane, int idx_inc, uint64_t index_offset)
-{
-    const ResolveJob job{out, reinterpret_cast<const PItem*>(queue_items), qcount, segcap, mul, (uint32_t)seed, (uint32_t)(seed >> 32), stream,
-                         (unsigned int)plane, (unsigned int)idx_inc, (unsigned long long)index_offset, 0, 0, 0};     // full segments: no refusals
-    hipLaunchKernelGGL(k_poisson_resolve, dim3(segments), dim3(256), 0, s, job, (const ExtractView*)nullptr);
-    MVSIM_HIP(hipGetLastError());
-    return MVSIM_OK;
-}
-
-// Work-queue geometry for n_out output voxels: `blocks` blocks of 256 lanes x 4 voxels walk the volume with a
-// grid stride; each owns a segment of `share` sixteenths of its voxels (16: every voxel, 16 B per output voxel of HBM
-// workspace and no refusals; less: what does not fit is sampled in place by phase 1, poisson_dev.h).
-constexpr size_t QCOUNT_BYTES = (size_t)QCOUNT_HEADER * sizeof(unsigned int) + 256;    // the [counts][header] in front of the segments
-static_assert(QCOUNT_BYTES % 256 == 0, "the segments start 16-byte aligned");
-
-// the share a queue of n_out voxels is built with.  Auto: what the context has learned its views need, from QUEUE_SHARE_START sixteenths up
-// (at 512^3 and the bench's SNR the sphere phantom's fullest block has 14 % of its voxels pending, that of a volume without an empty voxel
-// 68 %: profiles/r05_queue_share.txt), but small queues (<= 64 MiB at full size: up to 160^3 acquired
-// voxels) are not worth the extra launch that looks for refused voxels
-static int share_for(long long n_out, int share)
-{
-    if (share >= QUEUE_SHARE_AUTO) {
-        const int learned = share - QUEUE_SHARE_AUTO;
-        return n_out <= (4ll << 20) ? 16 : (learned >= 16 ? 16 : (learned > QUEUE_SHARE_START ? learned : QUEUE_SHARE_START));
-    }
-    return share >= 16 ? 16 : (share < 1 ? 1 : share);
-}
-
-static unsigned int segment_share(long long worst, int share)
-{
-    if (share >= 16) return (unsigned int)worst;
-    long long c = (worst * (share < 1 ? 1 : share) + 15) / 16;
-    c = (c + 63) & ~63ll;                                   // at least one wave of items, whole waves after that
-    return (unsigned int)(c < worst ? c : worst);
-}
-
-static void poisson_geometry(int64_t n_out, int share, int* blocks, unsigned int* segcap)
-{
-    long long want = (n_out / 4 + 255) / 256;
-    const int b = (int)(want < 1 ? 1 : (want > POISSON_MAX_BLOCKS ? POISSON_MAX_BLOCKS : want));
-    const long long iters = (n_out / 4 + (long long)b * 256 - 1) / ((long long)b * 256);
-    *blocks = b;
-    *segcap = segment_share(iters * 1024, share);   // worst case every voxel of the block: the squeeze accepts only ~35 % at lambda = 10
-}
-
-static size_t poisson_queue_bytes(int64_t n_out, int share)
-{
-    int blocks;
-    unsigned int segcap;
-    poisson_geometry(n_out, share, &blocks, &segcap);
-    return QCOUNT_BYTES + (size_t)blocks * segcap * sizeof(PItem);   // [counts][segments]
-}
-
-// The same for k_extract_noise2_any: a wave slot is 64 Philox groups of ONE plane (a plane of `plane` voxels that starts anywhere
-// inside a group touches up to plane / 4 + 1 of them, rounded up to whole slots), `blocks` blocks of four waves walk the slots with a
-// grid stride, and a block's segment holds `share` sixteenths of the voxels of its trips.
-static void poisson_geometry_any(long long plane, long long nzo, int share, int* blocks, unsigned int* segcap, long long* slots_per_plane)
-{
-    const long long spp = ((plane + 3) / 4 + 1 + 63) / 64;
-    const long long slots = spp * nzo;
-    long long want = (slots + 3) / 4;
-    const int b = (int)(want < 1 ? 1 : (want > POISSON_MAX_BLOCKS ? POISSON_MAX_BLOCKS : want));
-    const long long trips = (slots + (long long)b * 4 - 1) / ((long long)b * 4);
-    *blocks = b; *segcap = segment_share(trips * 1024, share); *slots_per_plane = spp;
-}
-
-// bytes of queue workspace for nzo acquired planes of `plane` voxels, whichever of the two kernels takes them
-size_t poisson_queue_bytes_planes(long long plane, long long nzo, int share)
-{
-    int blocks;
-    unsigned int segcap;
-    long long spp;
-    share = share_for(plane * nzo, share);
-    poisson_geometry_any(plane, nzo, share, &blocks, &segcap, &spp);
-    const size_t any = QCOUNT_BYTES + (size_t)blocks * segcap * sizeof(PItem);
-    const size_t vec = poisson_queue_bytes(plane * nzo, share);
-    return any > vec ? any : vec;
-}
-
-// What the last two-launch sampler that used this workspace queued (mvsim_get_queue_stats): {items a segment holds, bright items,
-// inversion items, voxels refused and sampled in place, pending voxels of the fullest block}.  The caller has synchronised the stream.
-int poisson_queue_read_stats(const void* queue_ws, size_t bytes, long long stats[5])
-{
-    stats[0] = stats[1] = stats[2] = stats[3] = stats[4] = 0;
-    if (!queue_ws || bytes < QCOUNT_BYTES) return MVSIM_OK;           // not a queue of the two-launch sampler
-    std::vector<unsigned int> h((size_t)QCOUNT_HEADER + 2);
-    MVSIM_HIP(hipMemcpy(h.data(), queue_ws, h.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
-    const unsigned int blocks = h[QCOUNT_HEADER] <= (unsigned int)POISSON_MAX_BLOCKS ? h[QCOUNT_HEADER] : 0u;
-    stats[0] = h[(size_t)QCOUNT_HEADER + 1];
-    stats[1] = stats[2] = stats[3] = stats[4] = 0;
-    for (unsigned int b = 0; b < blocks; ++b) {
-        const long long f = h[(size_t)QCOUNT_WORDS * b], k = h[(size_t)QCOUNT_WORDS * b + 1], r = h[(size_t)QCOUNT_WORDS * b + 2];
-        stats[1] += f;
-        stats[2] += k;
-        stats[3] += r;
-        if (f + k + r > stats[4]) stats[4] = f + k + r;     // what the fullest block had to settle: the segment size that refuses nothing
-    }
-    return MVSIM_OK;
-}
-
-// Which sampler form takes nzo = (dim[2] - 1) / inc + 1 acquired planes (mvsim_extract_path; launch_extract_impl decides through this
-// and nothing else).  index_inc: plane stride of the RNG counter (0 = inc); aligned16: both buffers allow 16-byte accesses; qshare: 0 =
-// no work queue, else the sixteenths share_for resolved.  path = {EXTRACT_K_*, segments can refuse, blocks, items per segment (0: no queue)}.
-void extract_path(const int64_t dim[3], int inc, int index_inc, uint64_t index_offset, bool aligned16, int qshare, int64_t path[4])
-{
-    if (index_inc <= 0) index_inc = inc;
-    const long long plane = (long long)dim[0] * dim[1];
-    const long long nzo = (dim[2] - 1) / inc + 1;
-    const long long total = plane * nzo;
-    // phase 1 hands a slot's RNG counters across lanes as 32-bit offsets from lane 0's (poisson_phase1): a vector slot is 256
-    // consecutive outputs, and planes smaller than that put several plane boundaries -- each a jump of (index_inc - 1) planes of
-    // counter -- into one slot; all of them together must stay below 2^31 (double: the product may exceed 64 bits)
-    const double crossings = (double)((255 + plane - 1) / plane);
-    // ... and a work item carries its output position (and the resolver the plane) in 32 bits
-    const bool use_queue = qshare != 0 && crossings * (double)(index_inc - 1) * (double)plane < 2147483648.0 && total < (1ll << 32) &&
-                           plane < (1ll << 32);
-    const bool vec = (plane % 4 == 0) && (index_offset % 4 == 0) && aligned16;
-    path[1] = use_queue && qshare < 16 ? 1 : 0;
-    path[3] = 0;
-    if (use_queue) {
-        int qblocks;
-        unsigned int segcap;
-        if (vec) {
-            poisson_geometry(total, qshare, &qblocks, &segcap);
-        } else {
-            long long spp;
-            poisson_geometry_any(plane, nzo, qshare, &qblocks, &segcap, &spp);
-        }
-        path[0] = vec ? EXTRACT_K_NOISE2 : EXTRACT_K_NOISE2_ANY;
-        path[2] = qblocks;
-        path[3] = segcap;
-    } else if (vec) {
-        const long long want = (total / 4 + 255) / 256;
-        path[0] = EXTRACT_K_VEC;
-        path[2] = want < 1 ? 1 : (want > 256 * 64 ? 256 * 64 : want);
-    } else {
-        const long long want = (total + 255) / 256;
-        path[0] = EXTRACT_K_SCALAR;
-        path[2] = want < 1 ? 1 : (want > 256 * 32 ? 256 * 32 : want);
-    }
-}
-
-// nviews > 0: the same launch for `nviews` views whose inputs, outputs, [sum, factor] slots, RNG keys and queue workspaces come from
-// the device table `vt` (blockIdx.y = view; `vec_all`: every view's buffers allow the 16-byte form; in / out / scal / seed / stream /
-// queue_ws arguments unused)
-static int launch_extract_impl(hipStream_t s, const float* in, float* out, const int64_t dim[3], int inc, bool adjust,
-                               const double* scal, float min_value, bool noise, double mul, uint64_t seed,
-                               uint32_t stream, uint64_t index_offset, void* queue_ws, QueueMode queue_mode, int index_inc,
-                               int nviews, const ExtractView* vt, bool vec_all, int64_t* path_out)
-{
-    // index_inc: plane stride of the RNG counter when it differs from the plane stride of the reads (a compact input
-    // that holds only the planes k * index_inc of the source volume); 0 = the same as inc
-    if (index_inc <= 0) index_inc = inc;
-    const unsigned gy = nviews > 0 ? (unsigned)nviews : 1u;
-    const long long plane = (long long)dim[0] * dim[1];
-    const long long nzo = (dim[2] - 1) / inc + 1;
-    const long long total = plane * nzo;
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    const int qshare = noise && (queue_ws || nviews > 0) && queue_mode.share != 0 ? share_for(total, queue_mode.share) : 0;
-    const bool aligned16 = nviews > 0 ? vec_all : ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) % 16 == 0);
-    int64_t path[4];
-    extract_path(dim, inc, index_inc, index_offset, aligned16, qshare, path);
-    if (path_out) {
-        for (int i = 0; i < 4; ++i) path_out[i] = path[i];
-        path_out[4] = gy;
-    }
-    const int qblocks = (int)path[2];
-    const unsigned int segcap = (unsigned int)path[3];
-    unsigned int* qcount = reinterpret_cast<unsigned int*>(queue_ws);
-    PItem* queue = queue_ws ? reinterpret_cast<PItem*>(reinterpret_cast<char*>(queue_ws) + QCOUNT_BYTES) : nullptr;
-    const bool checked = path[1] != 0;                    // segments that can fill up: the appends look before they write
-    if (path[0] == EXTRACT_K_NOISE2) {
-        int fb;
-        unsigned int full_items;
-        poisson_geometry(total, 16, &fb, &full_items);
-#define MVSIM_LAUNCH_N2(A, C)                                                                                                     \
-    hipLaunchKernelGGL((k_extract4_noise2<A, C>), dim3(qblocks, gy), dim3(256), 0, s, in, out, plane / 4, nzo, inc, index_inc, scal, \
-                       min_value, mul, k0, k1, stream, (unsigned long long)index_offset, queue, qcount, segcap, vt)
-        if (adjust && checked) MVSIM_LAUNCH_N2(true, true);
-        else if (adjust) MVSIM_LAUNCH_N2(true, false);
-        else if (checked) MVSIM_LAUNCH_N2(false, true);
-        else MVSIM_LAUNCH_N2(false, false);
-#undef MVSIM_LAUNCH_N2
-        const ResolveJob rjob{out, queue, qcount, segcap, mul, k0, k1, stream, (unsigned int)plane, (unsigned int)index_inc,
-                              (unsigned long long)index_offset, checked ? 1 : 0, total / 4, 0};
-        hipLaunchKernelGGL(k_poisson_resolve, dim3(qblocks, gy), dim3(256), 0, s, rjob, vt);
-        if (rjob.walk != 0)
-            hipLaunchKernelGGL(k_poisson_refused, dim3(qblocks < REFUSED_BLOCKS ? qblocks : REFUSED_BLOCKS, gy), dim3(256), 0, s, rjob, qblocks,
-                               full_items, queue_mode.hint, vt);
-    } else if (path[0] == EXTRACT_K_NOISE2_ANY) {
-        // planes that are no multiple of four voxels / unaligned buffers: the same two launches, group by group (k_extract_noise2_any)
-        int fb;
-        unsigned int full_items;
-        long long spp;
-        poisson_geometry_any(plane, nzo, 16, &fb, &full_items, &spp);
-#define MVSIM_LAUNCH_ANY(A, C)                                                                                                       \
-    hipLaunchKernelGGL((k_extract_noise2_any<A, C>), dim3(qblocks, gy), dim3(256), 0, s, in, out, plane, nzo, inc, index_inc, scal, min_value, \
-                       mul, k0, k1, stream, (unsigned long long)index_offset, queue, qcount, segcap, spp, vt)
-        if (adjust && checked) MVSIM_LAUNCH_ANY(true, true);
-        else if (adjust) MVSIM_LAUNCH_ANY(true, false);
-        else if (checked) MVSIM_LAUNCH_ANY(false, true);
-        else MVSIM_LAUNCH_ANY(false, false);
-#undef MVSIM_LAUNCH_ANY
-        const ResolveJob rjob{out, queue, qcount, segcap, mul, k0, k1, stream, (unsigned int)plane, (unsigned int)index_inc,
-                              (unsigned long long)index_offset, checked ? 2 : 0, spp * nzo, spp};
-        hipLaunchKernelGGL(k_poisson_resolve, dim3(qblocks, gy), dim3(256), 0, s, rjob, vt);
-        if (rjob.walk != 0)
-            hipLaunchKernelGGL(k_poisson_refused, dim3(qblocks < REFUSED_BLOCKS ? qblocks : REFUSED_BLOCKS, gy), dim3(256), 0, s, rjob, qblocks,
-                               full_items, queue_mode.hint, vt);
-    } else if (path[0] == EXTRACT_K_VEC) {
-        const int blocks = (int)path[2];
-#define MVSIM_LAUNCH_EX4(A, N)                                                                                          \
-    hipLaunchKernelGGL((k_extract4<A, N>), dim3(blocks, gy), dim3(256), 0, s, in, out, plane / 4, nzo, inc, index_inc, scal, \
-                       min_value, mul, k0, k1, stream, (unsigned long long)index_offset, vt)
-        if (adjust && noise) MVSIM_LAUNCH_EX4(true, true);
-        else if (adjust) MVSIM_LAUNCH_EX4(true, false);
-        else if (noise) MVSIM_LAUNCH_EX4(false, true);
-        else MVSIM_LAUNCH_EX4(false, false);
-#undef MVSIM_LAUNCH_EX4
-    } else {
-        const int blocks = (int)path[2];
-#define MVSIM_LAUNCH_EX(A, N)                                                                             \
-    hipLaunchKernelGGL((k_extract<A, N>), dim3(blocks, gy), dim3(256), 0, s, in, out, plane, nzo, inc, index_inc, scal, \
-                       min_value, mul, k0, k1, stream, (unsigned long long)index_offset, vt)
-        if (adjust && noise) MVSIM_LAUNCH_EX(true, true);
-        else if (adjust) MVSIM_LAUNCH_EX(true, false);
-        else if (noise) MVSIM_LAUNCH_EX(false, true);
-        else MVSIM_LAUNCH_EX(false, false);
-#undef MVSIM_LAUNCH_EX
-    }
-    MVSIM_HIP(hipGetLastError());
-    return MVSIM_OK;
-}
-
-int launch_extract(hipStream_t s, const float* in, float* out, const int64_t dim[3], int inc, bool adjust,
-                   const double* scal, float min_value, bool noise, double mul, uint64_t seed,
-                   uint32_t stream, uint64_t index_offset, void* queue_ws, QueueMode queue_mode, int index_inc, int64_t* path_out)
-{
-    return launch_extract_impl(s, in, out, dim, inc, adjust, scal, min_value, noise, mul, seed, stream, index_offset, queue_ws, queue_mode,
-                               index_inc, 0, nullptr, false, path_out);
-}
-
-// the queue region of one view inside a workspace of poisson_queue_bytes(n_out) bytes: [counts][segments]
-void poisson_queue_split(void* queue_ws, void** queue_items, unsigned int** qcount)
-{
-    *qcount = reinterpret_cast<unsigned int*>(queue_ws);
-    *queue_items = reinterpret_cast<char*>(queue_ws) + QCOUNT_BYTES;
-}
-
-int launch_extract_views(hipStream_t s, const int64_t dim[3], int inc, bool adjust, float min_value, bool noise, double mul,
-                         QueueMode queue_mode, int index_inc, int nviews, const ExtractView* vt_dev, bool vec_all, int64_t* path_out)
-{
-    return launch_extract_impl(s, nullptr, nullptr, dim, inc, adjust, nullptr, min_value, noise, mul, 0, 0, 0, nullptr, queue_mode, index_inc,
-                               nviews, vt_dev, vec_all, path_out);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "extract_plan.h"
+
 namespace mvsim {
 
 struct Philox4 {
@@ -435,6 +437,7 @@ struct __attribute__((aligned(16))) PItem {
     float v;                      // adjusted voxel value (lambda = v * mul)
     unsigned int w0, w1;          // random words of attempt 0 (inversion item: w0 = the voxel's word of its group block)
 };
+static_assert(sizeof(PItem) == PITEM_BYTES, "QueueLayout sizes the segments by PITEM_BYTES");
 
 // wave-private LDS scratch of phase 1 (1.1 KB: a block of four waves fits beside the two resident 75 KB blocks of the
 // convolution's y passes, which is what lets the hardware run the sampler on a second stream beside them -- DESIGN 4.5)
@@ -453,12 +456,7 @@ struct P1Args {                   // wave-uniform
     unsigned int* ovf;            // LDS: appends refused because the segment was full ([0] bright, [1] inversion)
 };
 
-// The count array in front of a queue's segments: per block three words -- items at the front, items at the back, voxels that found
-// the segment full -- for up to POISSON_MAX_BLOCKS blocks, then a header the first block of phase 1 writes: {blocks, items per segment}
-// (what mvsim_get_queue_stats reads) and the resolver completes: {.., .., 1 if any block refused a voxel} (what k_poisson_refused reads).
-constexpr int QCOUNT_WORDS = 3;
-constexpr int POISSON_MAX_BLOCKS = 256 * 64;
-constexpr int QCOUNT_HEADER = QCOUNT_WORDS * POISSON_MAX_BLOCKS;        // word index of the header
+// (the count array in front of a queue's segments -- QCOUNT_WORDS, POISSON_MAX_BLOCKS, QCOUNT_HEADER --: extract_plan.h)
 // What phase 1 leaves in the output of a voxel its full segment refused: the NEGATED voxel value (v > 0 for every voxel that has
 // anything to sample, counts are >= 0: a negative output cannot be a result).  k_poisson_refused walks the voxels of every block
 // whose third count word is non-zero once more and samples those voxels where they stand (resolve_refused).
@@ -752,7 +750,7 @@ __device__ __forceinline__ bool refused_collect(const ResolveJob& j, long long s
 
 constexpr int RESOLVE_TAB = 17 + 64;                         // doubles of LDS: log(k!) for k <= 16, then 1 / k for k < 64
 
-// One queue segment resolved by the 256 lanes of a block (k_poisson_resolve: kernels.hip).
+// One queue segment resolved by the 256 lanes of a block (k_poisson_resolve: extract.hip).
 __device__ __forceinline__ void resolve_segment_body(const ResolveJob& j, long long segment, int t, unsigned int* ticket, double* tab)
 {
     const unsigned int n = j.qcount[QCOUNT_WORDS * segment], ns = j.qcount[QCOUNT_WORDS * segment + 1];

@@ -1,8 +1,8 @@
 """Deterministic case list of the extract + Poisson sweep (tests/test_poisson_sweep.py): pure Python, no GPU, no library.
 
 Every case names an entry point, a geometry, a queue setting, an RNG key and counter range, and the sampler form it claims to
-land on; `launch_args` restates which arguments the entry point hands launch_extract (kernels.hip), and `expect_path` restates the
-decision that mvsim_extract_path makes on them.  The CPU tests hold both to the library; the GPU tests run the cases."""
+land on; `launch_args` restates the geometry the entry point hands the extract stage (extract_plan.h: ExtractGeom, as mvsim_extract_path's
+arguments), and `expect_path` restates the decision that extract_plan makes on it.  The CPU tests hold both to the library; the GPU tests run the cases."""
 import math
 from dataclasses import dataclass, field
 
@@ -61,7 +61,7 @@ def mul_of(case):
 
 
 def share_of(queue, total):
-    """What share_for (kernels.hip) resolves the option to: auto gives small queues (<= 4 Mi voxels) every voxel."""
+    """What share_for (extract_plan.h) resolves the option to: auto gives small queues (<= 4 Mi voxels) every voxel."""
     if queue == "off":
         return 0
     if queue == "auto":
@@ -75,7 +75,7 @@ def acquired(nz, inc):
 
 
 def slab_planes(case):
-    """(first acquired source plane, acquired planes, compact?) of a slab case (api_view.cpp: slab_finish_enqueue)."""
+    """(first acquired source plane, acquired planes, compact?) of a slab case (extract_plan.h: ExtractGeom::slab; api_view.cpp: slab_finish_enqueue)."""
     z0, z1 = case.slab
     k0, k1 = (z0 + case.inc - 1) // case.inc, (z1 + case.inc - 1) // case.inc
     return k0 * case.inc, k1 - k0, case.inc > 1 and z0 % case.inc == 0
@@ -111,7 +111,7 @@ def launch_args(case):
 
 
 def expect_path(dim, inc, index_inc, offset, aligned16, share):
-    """(kernel, segments can refuse) restated from extract_path (kernels.hip)."""
+    """(kernel, segments can refuse) restated from extract_plan (extract_plan.h)."""
     if index_inc <= 0:
         index_inc = inc
     plane = dim[0] * dim[1]

@@ -1,14 +1,18 @@
-"""Extract + Poisson swept over its sampler forms (tests/poisson_sweep_cases.py): the four kernels of launch_extract with and without
-the fused adjust, the queue kernels with full segments and with segments that refuse (refused walks 1 and 2), the fused tail, the
+"""Extract + Poisson swept over its sampler forms (tests/poisson_sweep_cases.py): the four kernels of launch_extract (extract.hip) with and
+without the fused adjust, the queue kernels with full segments and with segments that refuse (refused walks 1 and 2), the fused tail, the
 stacked-view table forms; queue shares 16, 1, auto and off; planes of 4 .. 4096 voxels, spacings 1, 2, 3, 7; counters that cross
 2^32, 2^33, 2^34 and 2^63 inside one wave; Philox keys with a non-zero high word and streams up to 2^32 - 1.
 
 Every GPU case first asserts, through mvsim_extract_path (or mvsim_fused_tail_geometry), that it lands on the form it claims, then
 that its counts EQUAL the oracle's counter sampler on the lambda the sampler read: the input itself for poisson_process and
 extractSlices, the noise-free twin of the same call (snr < 0) for views and slabs.  The CPU tests hold the case list to the library's
-path decision, check that it covers every form and counter range, and that its lambda mix would expose the classic counter mistakes."""
+path decision and the plan header (csrc/extract_plan.h, in a program of its own) to both, check that the list covers every form and
+counter range, and that its lambda mix would expose the classic counter mistakes."""
 import ctypes as C
 import importlib
+import os
+import shutil
+import subprocess
 import zlib
 
 import numpy as np
@@ -98,6 +102,99 @@ def test_path_query_at_the_size_guards(mvs):
     assert _path(mvs, (2048, 2048, 512), 3, 0, 0, 1, 16)[:2] == (S.K_NOISE2, 0)
     for args in (((2048, 2048, 2), 1, 516, 0, 1, 16), ((4, 1, 1000), 1, 2 ** 27, 0, 1, 16), ((2048, 2048, 1024), 1, 0, 0, 1, 16)):
         assert _path(mvs, *args)[0] == S.expect_path(*args)[0]
+
+
+def _geom_of(args):
+    """launch_args' (dim, inc, index_inc, offset, ..) as ExtractGeom states it: (plane, acquired planes, inc, index_inc, index_offset)."""
+    dim, inc, index_inc, offset = args[:4]
+    return dim[0] * dim[1], S.acquired(dim[2], inc), inc, index_inc or inc, offset
+
+
+def _plan_request(c):
+    """The ExtractGeom constructor the case's entry point calls (api.cpp, api_host.cpp, api_view.cpp), as a request of extract_plan_main."""
+    nz, ny, nx = c.shape
+    _, _, _, offset, aligned16, share = S.launch_args(c)
+    kind, a, b, k = "strided", 0, 0, 0
+    if c.entry == "poisson":
+        kind, (nx, ny, nz), b = "path", (c.shape[2], 1, 1), offset
+    elif c.entry in ("view", "views") and c.inc > 1 and c.queue != "off":
+        kind = "compact"
+    elif c.entry in ("slab3", "slab_dev"):
+        kind, (a, b), k = "slab", c.slab, int(S.slab_planes(c)[2])
+    return f"{kind} {nx} {ny} {nz} {c.inc} {a} {b} {k} {aligned16} 1 {share}"
+
+
+# test_path_query_at_the_size_guards' inputs and the kernels it expects of them
+_GUARD_INPUTS = (
+    (((2048, 2048, 1024), 1, 0, 0, 1, 16), S.K_VEC), (((2048, 2048, 1023), 1, 0, 0, 1, 16), S.K_NOISE2),
+    (((2048, 2048, 2047), 2, 0, 0, 1, 16), S.K_VEC), (((2048, 2048, 2), 1, 516, 0, 1, 16), S.K_VEC),
+    (((2048, 2048, 2), 1, 512, 0, 1, 16), S.K_NOISE2), (((2048, 2048, 520), 516, 0, 0, 0, 16), S.K_SCALAR),
+    (((4, 1, 1000), 1, 2 ** 27, 0, 1, 16), S.K_VEC), (((4, 1, 1000), 1, 2 ** 22, 0, 1, 16), S.K_NOISE2),
+    (((128, 1, 1000), 1, 2 ** 23 + 1, 0, 1, 16), S.K_VEC), (((256, 1, 1000), 1, 2 ** 22 + 1, 0, 1, 16), S.K_NOISE2),
+    (((512, 512, 512), 1, 0, 0, 1, 16), (S.K_NOISE2, 0)), (((512, 512, 512), 1, 0, 0, 1, 5), (S.K_NOISE2, 1)),
+    (((2048, 2048, 171), 1, 3, 0, 1, 5), (S.K_NOISE2, 1)), (((2048, 2048, 512), 3, 0, 0, 1, 16), (S.K_NOISE2, 0)),
+)
+
+
+def test_plan_header_agrees_with_the_case_list_and_the_library(mvs, tmp_path):
+    """tests/c_abi/extract_plan_main.cpp: csrc/extract_plan.h compiled by plain g++ under ASan + UBSan (no HIP, no libmvsim.so; a child
+    process, nothing preloaded).  (a) every non-fused case through the constructor its entry point calls: the geometry is launch_args',
+    the kernel and the refusing flag expect_path's, blocks and items per segment mvsim_extract_path's; (b) the size guards; (c)
+    ExtractGeom::slab over planes of 4, 60 and 257 voxels, nz 1..24, inc 1, 2, 3, 7, every 0 <= z0 < z1 <= nz, strided and -- where z0
+    is a multiple of inc -- compact: slab_planes' and launch_args' geometry, empty slabs included.  No mismatch, no sanitizer report."""
+    exe = str(tmp_path / "extract_plan_main")
+    cmd = [shutil.which("g++") or "g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall",
+           "-Wextra", "-Werror", "-I" + os.path.join(os.path.dirname(os.path.abspath(mvs.__file__)), "csrc"),
+           os.path.join(os.path.dirname(os.path.abspath(__file__)), "c_abi", "extract_plan_main.cpp"), "-o", exe]
+    b = subprocess.run(cmd, capture_output=True, text=True)
+    assert b.returncode == 0, b.stdout + b.stderr
+    cases = [c for c in S.CASES if c.claim != S.FUSED]
+    slabs = []
+    for ny, nx in ((1, 4), (6, 10), (1, 257)):
+        for nz in range(1, 25):
+            for inc in S.INCS:
+                for z0 in range(nz):
+                    for z1 in range(z0 + 1, nz + 1):
+                        for compact in (0, 1) if z0 % inc == 0 else (0,):
+                            slabs.append((S.Case("grid", "slab3", (nz, ny, nx), inc=inc, slab=(z0, z1)), compact))
+    requests = [_plan_request(c) for c in cases]
+    requests += [f"path {d[0]} {d[1]} {d[2]} {inc} {iinc} {off} 0 {al} 1 {share}" for (d, inc, iinc, off, al, share), _ in _GUARD_INPUTS]
+    requests += [f"slab {c.shape[2]} {c.shape[1]} {c.shape[0]} {c.inc} {c.slab[0]} {c.slab[1]} {k} 1 1 16" for c, k in slabs]
+    r = subprocess.run([exe], input="\n".join(requests) + "\n", capture_output=True, text=True)
+    assert r.returncode == 0 and f"extract plan run ok: {len(requests)} requests" in r.stderr, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr[-4000:]
+    rows = [tuple(int(t) for t in line.split()) for line in r.stdout.splitlines()]
+    assert len(rows) == len(requests)
+    mismatches = []
+    for c, row in zip(cases, rows):
+        args = S.launch_args(c)
+        ok = row[:5] == _geom_of(args) and (row[6], bool(row[7])) == S.expect_path(*args) == (c.claim, c.refuses)
+        ok = ok and row[8:10] == _path(mvs, *args)[2:4] and row[12] == args[5]
+        if c.entry in ("slab3", "slab_dev"):
+            first, _, compact = S.slab_planes(c)
+            ok = ok and row[5] == (0 if compact else c.plane * (first - c.slab[0])) and (row[5] % 4 == 0) == bool(args[4])
+        else:
+            ok = ok and row[5] == 0
+        if not ok:
+            mismatches.append((c.id, row))
+    rows = rows[len(cases):]
+    for (args, want), row in zip(_GUARD_INPUTS, rows):
+        got = (row[6], row[7], row[8], row[9])
+        if got != _path(mvs, *args) or (got[:2] != want if isinstance(want, tuple) else got[0] != want) or row[:5] != _geom_of(args):
+            mismatches.append((args, row))
+    rows = rows[len(_GUARD_INPUTS):]
+    n_empty = 0
+    for (c, k), row in zip(slabs, rows):
+        (z0, z1), plane = c.slab, c.plane
+        first, n_acq, compact = S.slab_planes(c)
+        ok = n_acq == sum(1 for j in range(c.shape[0] + 1) if z0 <= j * c.inc < z1) and first % c.inc == 0 and (n_acq == 0 or z0 <= first < z1)
+        ok = ok and row[:6] == (plane, n_acq, 1 if k else c.inc, c.inc, first * plane, 0 if k else plane * (first - z0))
+        if bool(k) == compact:
+            ok = ok and row[:5] == _geom_of(S.launch_args(c))
+        n_empty += n_acq == 0
+        if not ok:
+            mismatches.append((c.shape, c.inc, c.slab, k, row))
+    assert n_empty > 0 and not mismatches, (len(mismatches), mismatches[:5])
 
 
 def test_sweep_covers_every_form_and_counter_range():
