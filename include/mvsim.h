@@ -75,7 +75,8 @@ int  mvsim_join(mvsim_ctx* ctx);
  * columns up), "attenuate" = serial|scan (mvsim_attenuate3d
  * as a wavefront-level prefix scan along the illumination axis: parallel in y, not bit-identical to the serial walk), "beads_pair_cap" =
  * 1024..2^31 ((brick, bead) pairs the bead renderer bins at once; larger calls run in chunks with identical results; the refraction
- * simulator's injection bins its (brick, step) pairs under the same cap).
+ * simulator's injection bins its (brick, step) pairs under the same cap, and so does the sphere raster of the procedural phantom),
+ * "reject_batch" = 1..2^20|auto (trials per launch of mvsim_rejection_sample; the result does not depend on it).
  * MVSIM_OPTIONS="name=value;name=value" sets any of them process-wide.  Unknown names or values: MVSIM_EINVAL. */
 int  mvsim_set_option(mvsim_ctx* ctx, const char* name, const char* value);
 /* Release cached FFT plans / workspaces / PSF spectra held by the context. */
@@ -189,6 +190,65 @@ int mvsim_render_beads_dev(mvsim_ctx* ctx, const double* xyz, const int64_t* vie
  * float (a constant image gives NaN, as in the reference). */
 int mvsim_beads_normalize(mvsim_ctx* ctx, float* img, int64_t n);
 int mvsim_beads_normalize_dev(mvsim_ctx* ctx, float* img_dev, int64_t n);
+
+/* ---- the procedural phantom: HypersphereCollectionRealRandomAccessible.main (:199-286) ------------------------------------
+ *   PN = src/main/java/net/preibisch/simulation/PerlinNoiseRealRandomAccessible.java, HC = .../HypersphereCollectionRealRandomAccessible.java,
+ *   SC = .../SimpleCalculatedRealRandomAccessible.java, PRS = .../PointRejectionSampling.java
+ * Three dimensions only.  Positions are 3 doubles, x first; rasters are floats, x fastest, dim = {Nx, Ny, Nz}, the voxel l at the integer
+ * position origin + l.  The arithmetic is fp64, one rounding per operation, stated in DESIGN.md section 12: the results equal a literal
+ * restatement bit for bit.  The host forms take host buffers and are synchronous; the *_dev forms take DEVICE positions / rasters (the
+ * tables and sphere lists stay host arrays, copied before the call returns) and run asynchronously on the context's stream.
+ * MVSIM_EINVAL, without touching the GPU, for null pointers, n_vectors < 1 or > 1536 (the tables are staged in LDS), loop extents < 1 or
+ * with (1 + e0)(1 + e1) e2 >= 2^31 (PN's flatIndex would overflow), a scale that is 0 or NaN, non-finite positions or centres, a negative
+ * or NaN radius, non-positive dims, |origin| > 2^40. */
+/* PN:56-73, the constructor: per vector three nextGaussian() (JDK polar method over StrictMath.log = fdlibm, restated), each component
+ * divided by Math.sqrt(sSum); then Collections.shuffle of 0 .. n - 1.  rnd_state is the caller's java.util.Random (48 bits), advanced as
+ * the reference advances it; *pending_gaussian (may be NULL: none before, dropped after) is the generator's cached second Gaussian,
+ * NaN = none, in and out.  Pure host function. */
+int mvsim_perlin_init(uint64_t* rnd_state, int32_t n_vectors, double* gradients, int32_t* permutation, double* pending_gaussian);
+typedef struct mvsim_perlin {
+    double         scales[3];
+    int32_t        loop_extents[3];
+    int32_t        n_vectors;
+    const double*  gradients;       /* n_vectors x 3 */
+    const int32_t* permutation;     /* n_vectors, each 0 .. n_vectors - 1 */
+    double         threshold;       /* NaN: the raw value; else SC's lambda of HC:221-223 over PN's FloatType: (float)value > threshold ? 1 : 0 */
+} mvsim_perlin;
+/* PN:127-160 get() at n positions -> n doubles (the raw fp64 value, or 1 / 0 with a threshold). */
+int mvsim_perlin_at(mvsim_ctx* ctx, const mvsim_perlin* field, const double* xyz, int64_t n, double* out);
+int mvsim_perlin_at_dev(mvsim_ctx* ctx, const mvsim_perlin* field, const double* xyz_dev, int64_t n, double* out_dev);
+/* Views.raster of the field: out[l] = (float) of the value at origin + l. */
+int mvsim_perlin_raster(mvsim_ctx* ctx, const mvsim_perlin* field, const int64_t origin[3], const int64_t dim[3], float* out);
+int mvsim_perlin_raster_dev(mvsim_ctx* ctx, const mvsim_perlin* field, const int64_t origin[3], const int64_t dim[3], float* out_dev);
+/* HC:148-177: the value of the LOWEST-INDEX sphere with sqrt(dx dx + dy dy + dz dz) <= radius (ImgLib2's Util.distance: the squares
+ * summed x, y, z in fp64), else `background`.  The reference reaches this through a KD-tree search at the largest radius. */
+typedef struct mvsim_sphere_set {
+    int64_t       n;
+    const double* centres;          /* n x 3 */
+    const double* radii;            /* n, >= 0 */
+    const float*  values;           /* n */
+    float         background;
+} mvsim_sphere_set;
+int mvsim_spheres_at(mvsim_ctx* ctx, const mvsim_sphere_set* set, const double* xyz, int64_t n, float* out);
+int mvsim_spheres_at_dev(mvsim_ctx* ctx, const mvsim_sphere_set* set, const double* xyz_dev, int64_t n, float* out_dev);
+/* combine = 0: out = value; combine = 1: out = Math.max(out, value), the lambda of HC:265-270 without a temporary volume.  Calls that
+ * bin more (brick, sphere) pairs than the option "beads_pair_cap" run in sphere ranges with identical results. */
+int mvsim_spheres_raster(mvsim_ctx* ctx, const mvsim_sphere_set* set, const int64_t origin[3], const int64_t dim[3], int combine, float* out);
+int mvsim_spheres_raster_dev(mvsim_ctx* ctx, const mvsim_sphere_set* set, const int64_t origin[3], const int64_t dim[3], int combine,
+                             float* out_dev);
+/* PRS:37-55 sampleRealPoints: per trial pos[d] = rmin[d] + nextDouble() * (rmax[d] - rmin[d]), d = 0, 1, 2, then p = nextDouble(); the
+ * trial is accepted if p < density(pos), the density being the FloatType's value as a double ((double)(float) of a raw Perlin value).
+ * Every trial takes eight steps of the generator, so the trials are evaluated side by side on the GPU, "reject_batch" = 1..2^20|auto
+ * (option) at a time, and the accepted ones compacted in trial order; xyz_out receives the first n_samples, *n_trials_out (may be NULL)
+ * the number of trials the reference would have made, and *rnd_state advances by 8 steps per such trial.  More than max_trials trials:
+ * MVSIM_EINVAL with *rnd_state untouched (the reference would loop forever on a density that is 0 everywhere). */
+typedef struct mvsim_density {
+    int32_t                 kind;   /* 0: perlin, 1: spheres */
+    const mvsim_perlin*     perlin;
+    const mvsim_sphere_set* spheres;
+} mvsim_density;
+int mvsim_rejection_sample(mvsim_ctx* ctx, uint64_t* rnd_state, const double rmin[3], const double rmax[3], int64_t n_samples,
+                           const mvsim_density* density, int64_t max_trials, double* xyz_out, int64_t* n_trials_out);
 
 /* ---- the refraction simulator: net.preibisch.simulation.SimulateMultiViewAberrations --------------------------------------
  *   SMVA = src/main/java/net/preibisch/simulation/SimulateMultiViewAberrations.java, HES = .../Hessian.java,

@@ -18,6 +18,7 @@ There is no CPU fallback anywhere in this package.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -25,9 +26,11 @@ import numpy as np
 from . import _lib
 from ._lib import MvsimError, MvsimNoDeviceError, Sphere, Timings, ViewOutputs, ViewParams  # noqa: F401
 from .aberrations import ContextAberrations
+from .phantoms import ContextPhantoms
 
-__all__ = ["AffineTransform3D", "Context", "Group", "Hessian", "JavaRandom", "Lightsheet", "Raytrace", "SimulateBeads", "SimulateBeads2", "SimulateMultiViewAberrations",
-           "SimulateMultiViewDataset", "Tools", "VolumeInjection", "broadcast_plan", "default_context", "MvsimError", "MvsimNoDeviceError", "ViewParams", "shard_views",
+__all__ = ["AffineTransform3D", "Context", "Group", "Hessian", "HypersphereCollectionRealRandomAccessible", "JavaRandom", "Lightsheet",
+           "PerlinNoiseRealRandomAccessible", "PointRejectionSampling", "Raytrace", "SimpleCalculatedRealRandomAccessible", "SimulateBeads",
+           "SimulateBeads2", "SimulateMultiViewAberrations", "SimulateMultiViewDataset", "Tools", "VolumeInjection", "broadcast_plan", "default_context", "MvsimError", "MvsimNoDeviceError", "ViewParams", "shard_views",
            "version"]
 
 
@@ -60,6 +63,7 @@ class JavaRandom:
 
     def setSeed(self, seed: int) -> None:
         self._s = (seed ^ self._MULT) & self._MASK
+        self._pending = None              # nextGaussian()'s cached second value
 
     def next(self, bits: int) -> int:
         self._s = (self._s * self._MULT + 0xB) & self._MASK
@@ -91,6 +95,28 @@ class JavaRandom:
     def nextDouble(self) -> float:
         return ((self.next(26) << 27) + self.next(27)) * (1.0 / (1 << 53))
 
+    def nextGaussian(self) -> float:
+        """The polar method of the JDK specification over StrictMath.log (fdlibm, restated in phantoms.strict_log) and sqrt."""
+        from .phantoms import strict_log
+        if self._pending is not None:
+            g, self._pending = self._pending, None
+            return g
+        while True:
+            v1 = 2 * self.nextDouble() - 1
+            v2 = 2 * self.nextDouble() - 1
+            s = v1 * v1 + v2 * v2
+            if not (s >= 1 or s == 0):
+                break
+        multiplier = math.sqrt(-2 * strict_log(s) / s)
+        self._pending = v2 * multiplier
+        return v1 * multiplier
+
+    def shuffle(self, lst: list) -> None:
+        """Collections.shuffle(lst, this), in place."""
+        for i in range(len(lst), 1, -1):
+            j = self.nextInt(i)
+            lst[i - 1], lst[j] = lst[j], lst[i - 1]
+
 
 def _seed_from(rnd) -> int:
     if rnd is None:
@@ -121,9 +147,10 @@ def _ptr(a: np.ndarray) -> C.c_void_p:
     return C.c_void_p(a.ctypes.data)
 
 
-class Context(ContextAberrations):
+class Context(ContextAberrations, ContextPhantoms):
     """One ``mvsim_ctx``: bound to one GPU, not thread-safe.  (The refraction simulator's entry points -- refract3d,
-    project_to_camera, hessian_at, volume_inject, ... -- are in aberrations.ContextAberrations.)"""
+    project_to_camera, hessian_at, volume_inject, ... -- are in aberrations.ContextAberrations, the procedural phantom's --
+    perlin_at, spheres_raster, rejection_sample, ... -- in phantoms.ContextPhantoms.)"""
 
     def __init__(self, device: int | None = None):
         self._h = C.c_void_p()
@@ -1060,3 +1087,5 @@ class SimulateTileStitching:
 
 from .beads import AffineTransform3D, SimulateBeads, SimulateBeads2  # noqa: E402
 from .aberrations import Hessian, Lightsheet, Raytrace, SimulateMultiViewAberrations, VolumeInjection  # noqa: E402
+from .phantoms import (HypersphereCollectionRealRandomAccessible, PerlinNoiseRealRandomAccessible, PointRejectionSampling,  # noqa: E402
+                       SimpleCalculatedRealRandomAccessible)

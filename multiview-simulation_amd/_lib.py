@@ -54,6 +54,23 @@ class RaySteps(C.Structure):
                 ("moves", C.POINTER(C.c_int32))]
 
 
+class Perlin(C.Structure):
+    """mvsim_perlin: a Perlin field (host tables)."""
+    _fields_ = [("scales", C.c_double * 3), ("loop_extents", C.c_int32 * 3), ("n_vectors", C.c_int32), ("gradients", C.POINTER(C.c_double)),
+                ("permutation", C.POINTER(C.c_int32)), ("threshold", C.c_double)]
+
+
+class SphereSet(C.Structure):
+    """mvsim_sphere_set: spheres in list order (host arrays)."""
+    _fields_ = [("n", C.c_int64), ("centres", C.POINTER(C.c_double)), ("radii", C.POINTER(C.c_double)), ("values", C.POINTER(C.c_float)),
+                ("background", C.c_float)]
+
+
+class Density(C.Structure):
+    """mvsim_density: what mvsim_rejection_sample samples against."""
+    _fields_ = [("kind", C.c_int32), ("perlin", C.POINTER(Perlin)), ("spheres", C.POINTER(SphereSet))]
+
+
 class Timings(C.Structure):
     _fields_ = [(n, C.c_float) for n in
                 ("rotate_ms", "attenuate_ms", "psf_ms", "convolve_ms", "adjust_ms", "extract_ms", "total_ms",
@@ -179,6 +196,17 @@ SIGNATURES = {
                                          C.POINTER(C.c_double), C.POINTER(_vp), C.POINTER(_vp)]),
     "mvsim_beads_normalize": (C.c_int, [_vp, _vp, C.c_int64]),
     "mvsim_beads_normalize_dev": (C.c_int, [_vp, _vp, C.c_int64]),
+    "mvsim_perlin_init": (C.c_int, [C.POINTER(C.c_uint64), C.c_int32, _dp, C.POINTER(C.c_int32), _dp]),
+    "mvsim_perlin_at": (C.c_int, [_vp, C.POINTER(Perlin), _vp, C.c_int64, _vp]),
+    "mvsim_perlin_at_dev": (C.c_int, [_vp, C.POINTER(Perlin), _vp, C.c_int64, _vp]),
+    "mvsim_perlin_raster": (C.c_int, [_vp, C.POINTER(Perlin), _i64p, _i64p, _vp]),
+    "mvsim_perlin_raster_dev": (C.c_int, [_vp, C.POINTER(Perlin), _i64p, _i64p, _vp]),
+    "mvsim_spheres_at": (C.c_int, [_vp, C.POINTER(SphereSet), _vp, C.c_int64, _vp]),
+    "mvsim_spheres_at_dev": (C.c_int, [_vp, C.POINTER(SphereSet), _vp, C.c_int64, _vp]),
+    "mvsim_spheres_raster": (C.c_int, [_vp, C.POINTER(SphereSet), _i64p, _i64p, C.c_int, _vp]),
+    "mvsim_spheres_raster_dev": (C.c_int, [_vp, C.POINTER(SphereSet), _i64p, _i64p, C.c_int, _vp]),
+    "mvsim_rejection_sample": (C.c_int, [_vp, C.POINTER(C.c_uint64), _dp, _dp, C.c_int64, C.POINTER(Density), C.c_int64, _dp,
+                                         C.POINTER(C.c_int64)]),
     "mvsim_lightsheet_fit": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, _dp]),
     "mvsim_hessian_at": (C.c_int, [_vp, _vp, _i64p, _dp, C.c_int64, _dp, _dp, _dp]),
     "mvsim_hessian_at_dev": (C.c_int, [_vp, _vp, _i64p, _dp, C.c_int64, _dp, _dp, _dp]),

@@ -172,6 +172,202 @@ int mvsim_beads_normalize(mvsim_ctx* ctx, float* img, int64_t n)
     return down(ctx, img, ctx->vol_a.p, bytes);
 }
 
+// ---- the procedural phantom: Perlin field, sphere sets, rejection sampling (procedural.hip) ---------------------------------
+int mvsim_perlin_init(uint64_t* rnd_state, int32_t n_vectors, double* gradients, int32_t* permutation, double* pending_gaussian)
+{
+    MVSIM_CHECK_ARG(rnd_state && gradients && permutation, "null pointer");
+    MVSIM_CHECK_ARG(n_vectors >= 1, "n_vectors must be >= 1");
+    JRandom rnd{*rnd_state & JR_MASK};
+    double pending = pending_gaussian ? *pending_gaussian : std::nan("");
+    for (int32_t i = 0; i < n_vectors; ++i) {                          // PerlinNoiseRealRandomAccessible.java:67-71, :99-111
+        double* res = gradients + 3 * (size_t)i;
+        double s_sum = 0.0;
+        for (int d = 0; d < 3; ++d) {
+            res[d] = jr_next_gaussian(rnd, pending);
+            s_sum += res[d] * res[d];
+        }
+        for (int d = 0; d < 3; ++d) res[d] /= std::sqrt(s_sum);
+        permutation[i] = i;
+    }
+    jr_shuffle(rnd, permutation, n_vectors);                           // :72
+    *rnd_state = rnd.s;
+    if (pending_gaussian) *pending_gaussian = pending;
+    return MVSIM_OK;
+}
+
+static int perlin_check(const mvsim_perlin* f)
+{
+    MVSIM_CHECK_ARG(f && f->gradients && f->permutation, "null pointer");
+    MVSIM_CHECK_ARG(f->n_vectors >= 1, "n_vectors must be >= 1");
+    MVSIM_CHECK_ARG(f->n_vectors <= PERLIN_MAX_VECTORS, "n_vectors too large: the gradient table does not fit into LDS");
+    for (int d = 0; d < 3; ++d) {
+        MVSIM_CHECK_ARG(f->loop_extents[d] >= 1, "loop extents must be >= 1");
+        MVSIM_CHECK_ARG(f->scales[d] != 0.0 && f->scales[d] == f->scales[d], "scale must not be 0 or NaN");
+    }
+    MVSIM_CHECK_ARG((1 + (int64_t)f->loop_extents[0]) * (1 + (int64_t)f->loop_extents[1]) * (int64_t)f->loop_extents[2] < ((int64_t)1 << 31),
+                    "loop extents too large: flatIndex would overflow");
+    for (int32_t i = 0; i < f->n_vectors; ++i)
+        MVSIM_CHECK_ARG(f->permutation[i] >= 0 && f->permutation[i] < f->n_vectors, "permutation entry outside 0 .. n_vectors - 1");
+    return MVSIM_OK;
+}
+
+static int spheres_check(const mvsim_sphere_set* s)
+{
+    MVSIM_CHECK_ARG(s && s->n >= 0 && ((s->centres && s->radii && s->values) || s->n == 0), "null pointer or negative count");
+    MVSIM_CHECK_ARG(s->n < ((int64_t)1 << 31), "too many spheres");
+    for (int64_t i = 0; i < s->n; ++i) {
+        MVSIM_CHECK_ARG(s->radii[i] >= 0.0, "negative (or NaN) radius");
+        MVSIM_CHECK_ARG(std::isfinite(s->centres[3 * i]) && std::isfinite(s->centres[3 * i + 1]) && std::isfinite(s->centres[3 * i + 2]),
+                        "sphere centre not finite");
+    }
+    return MVSIM_OK;
+}
+
+static int raster_check(const int64_t origin[3], const int64_t dim[3], const float* out)
+{
+    MVSIM_CHECK_ARG(origin && dim && out, "null pointer");
+    MVSIM_CHECK_ARG(dim[0] >= 1 && dim[1] >= 1 && dim[2] >= 1, "dimensions must be >= 1");
+    MVSIM_CHECK_ARG(dim[0] <= (1 << 24) && dim[1] <= (1 << 24) && dim[2] <= (1 << 24) && nvox(dim) < ((int64_t)1 << 40), "raster too large");
+    for (int d = 0; d < 3; ++d) MVSIM_CHECK_ARG(origin[d] >= -((int64_t)1 << 40) && origin[d] <= ((int64_t)1 << 40), "origin outside +-2^40");
+    return MVSIM_OK;
+}
+
+static int positions_check(const double* xyz, int64_t n, const void* out, bool host)
+{
+    MVSIM_CHECK_ARG(n >= 0 && ((xyz && out) || n == 0), "null pointer or negative count");
+    if (host)
+        for (int64_t i = 0; i < 3 * n; ++i) MVSIM_CHECK_ARG(std::isfinite(xyz[i]), "position not finite");
+    return MVSIM_OK;
+}
+
+int mvsim_perlin_at_dev(mvsim_ctx* ctx, const mvsim_perlin* field, const double* xyz, int64_t n, double* out)
+{
+    MVSIM_TRY(perlin_check(field));
+    MVSIM_TRY(positions_check(xyz, n, out, false));
+    MVSIM_TRY(set_device(ctx));
+    PerlinDev pd;
+    MVSIM_TRY(perlin_upload(ctx, field, &pd));
+    return perlin_at_dev(ctx, pd, xyz, n, out);
+}
+
+int mvsim_perlin_at(mvsim_ctx* ctx, const mvsim_perlin* field, const double* xyz, int64_t n, double* out)
+{
+    MVSIM_TRY(perlin_check(field));
+    MVSIM_TRY(positions_check(xyz, n, out, true));
+    MVSIM_TRY(set_device(ctx));
+    if (n == 0) return MVSIM_OK;
+    PerlinDev pd;
+    MVSIM_TRY(perlin_upload(ctx, field, &pd));
+    MVSIM_TRY(up(ctx, ctx->vol_a, reinterpret_cast<const float*>(xyz), (size_t)n * 3 * sizeof(double)));
+    MVSIM_TRY(ctx->vol_b.reserve((size_t)n * sizeof(double)));
+    MVSIM_TRY(perlin_at_dev(ctx, pd, ctx->vol_a.as<double>(), n, ctx->vol_b.as<double>()));
+    return down(ctx, reinterpret_cast<float*>(out), ctx->vol_b.p, (size_t)n * sizeof(double));
+}
+
+int mvsim_perlin_raster_dev(mvsim_ctx* ctx, const mvsim_perlin* field, const int64_t origin[3], const int64_t dim[3], float* out)
+{
+    MVSIM_TRY(perlin_check(field));
+    MVSIM_TRY(raster_check(origin, dim, out));
+    MVSIM_TRY(set_device(ctx));
+    PerlinDev pd;
+    MVSIM_TRY(perlin_upload(ctx, field, &pd));
+    return perlin_raster_dev(ctx, pd, origin, dim, out);
+}
+
+int mvsim_perlin_raster(mvsim_ctx* ctx, const mvsim_perlin* field, const int64_t origin[3], const int64_t dim[3], float* out)
+{
+    MVSIM_TRY(perlin_check(field));
+    MVSIM_TRY(raster_check(origin, dim, out));
+    MVSIM_TRY(set_device(ctx));
+    const size_t bytes = (size_t)nvox(dim) * sizeof(float);
+    PerlinDev pd;
+    MVSIM_TRY(perlin_upload(ctx, field, &pd));
+    MVSIM_TRY(ctx->vol_a.reserve(bytes));
+    MVSIM_TRY(perlin_raster_dev(ctx, pd, origin, dim, ctx->vol_a.as<float>()));
+    return down(ctx, out, ctx->vol_a.p, bytes);
+}
+
+int mvsim_spheres_at_dev(mvsim_ctx* ctx, const mvsim_sphere_set* set, const double* xyz, int64_t n, float* out)
+{
+    MVSIM_TRY(spheres_check(set));
+    MVSIM_TRY(positions_check(xyz, n, out, false));
+    MVSIM_TRY(set_device(ctx));
+    SpheresDev sd;
+    MVSIM_TRY(spheres_upload(ctx, set, &sd));
+    return spheres_at_dev(ctx, sd, xyz, n, out);
+}
+
+int mvsim_spheres_at(mvsim_ctx* ctx, const mvsim_sphere_set* set, const double* xyz, int64_t n, float* out)
+{
+    MVSIM_TRY(spheres_check(set));
+    MVSIM_TRY(positions_check(xyz, n, out, true));
+    MVSIM_TRY(set_device(ctx));
+    if (n == 0) return MVSIM_OK;
+    SpheresDev sd;
+    MVSIM_TRY(spheres_upload(ctx, set, &sd));
+    MVSIM_TRY(up(ctx, ctx->vol_a, reinterpret_cast<const float*>(xyz), (size_t)n * 3 * sizeof(double)));
+    MVSIM_TRY(ctx->vol_b.reserve((size_t)n * sizeof(float)));
+    MVSIM_TRY(spheres_at_dev(ctx, sd, ctx->vol_a.as<double>(), n, ctx->vol_b.as<float>()));
+    return down(ctx, out, ctx->vol_b.p, (size_t)n * sizeof(float));
+}
+
+static int spheres_raster_args(const mvsim_sphere_set* set, const int64_t origin[3], const int64_t dim[3], int combine, const float* out)
+{
+    MVSIM_TRY(spheres_check(set));
+    MVSIM_TRY(raster_check(origin, dim, out));
+    MVSIM_CHECK_ARG(combine == 0 || combine == 1, "combine must be 0 or 1");
+    return MVSIM_OK;
+}
+
+int mvsim_spheres_raster_dev(mvsim_ctx* ctx, const mvsim_sphere_set* set, const int64_t origin[3], const int64_t dim[3], int combine,
+                             float* out)
+{
+    MVSIM_TRY(spheres_raster_args(set, origin, dim, combine, out));
+    MVSIM_TRY(set_device(ctx));
+    SpheresDev sd;
+    MVSIM_TRY(spheres_upload(ctx, set, &sd));
+    return spheres_raster_dev(ctx, set, sd, origin, dim, combine, out);
+}
+
+int mvsim_spheres_raster(mvsim_ctx* ctx, const mvsim_sphere_set* set, const int64_t origin[3], const int64_t dim[3], int combine, float* out)
+{
+    MVSIM_TRY(spheres_raster_args(set, origin, dim, combine, out));
+    MVSIM_TRY(set_device(ctx));
+    const size_t bytes = (size_t)nvox(dim) * sizeof(float);
+    SpheresDev sd;
+    MVSIM_TRY(spheres_upload(ctx, set, &sd));
+    if (combine) MVSIM_TRY(up(ctx, ctx->vol_a, out, bytes));
+    else MVSIM_TRY(ctx->vol_a.reserve(bytes));
+    MVSIM_TRY(spheres_raster_dev(ctx, set, sd, origin, dim, combine, ctx->vol_a.as<float>()));
+    return down(ctx, out, ctx->vol_a.p, bytes);
+}
+
+int mvsim_rejection_sample(mvsim_ctx* ctx, uint64_t* rnd_state, const double rmin[3], const double rmax[3], int64_t n_samples,
+                           const mvsim_density* density, int64_t max_trials, double* xyz_out, int64_t* n_trials_out)
+{
+    MVSIM_CHECK_ARG(rnd_state && rmin && rmax && density && (xyz_out || n_samples == 0), "null pointer");
+    MVSIM_CHECK_ARG(n_samples >= 0 && n_samples < ((int64_t)1 << 28), "n_samples must be 0 .. 2^28");
+    MVSIM_CHECK_ARG(max_trials >= 0 && max_trials < ((int64_t)1 << 44), "max_trials must be 0 .. 2^44");
+    for (int d = 0; d < 3; ++d) MVSIM_CHECK_ARG(std::isfinite(rmin[d]) && std::isfinite(rmax[d]), "interval not finite");
+    MVSIM_CHECK_ARG(density->kind == 0 || density->kind == 1, "density kind must be 0 (perlin) or 1 (spheres)");
+    if (density->kind == 0) MVSIM_TRY(perlin_check(density->perlin));
+    else MVSIM_TRY(spheres_check(density->spheres));
+    MVSIM_TRY(set_device(ctx));
+    PerlinDev pd;
+    SpheresDev sd;
+    if (n_samples > 0) {
+        if (density->kind == 0) MVSIM_TRY(perlin_upload(ctx, density->perlin, &pd));
+        else MVSIM_TRY(spheres_upload(ctx, density->spheres, &sd));
+    }
+    const uint64_t state = *rnd_state & JR_MASK;
+    int64_t trials = 0;
+    MVSIM_TRY(rejection_sample_dev(ctx, state, rmin, rmax, n_samples, density->kind == 0 ? &pd : nullptr, density->kind == 1 ? &sd : nullptr,
+                                   max_trials, xyz_out, &trials));
+    *rnd_state = jr_jump(state, 8 * (uint64_t)trials);
+    if (n_trials_out) *n_trials_out = trials;
+    return MVSIM_OK;
+}
+
 // ---- the refraction simulator: SimulateMultiViewAberrations (aberrations.hip) ---------------------------------------------
 int mvsim_lightsheet_fit(double center, double thickness_center, double length, double thickness_edges, double abc[3])
 {

@@ -193,6 +193,7 @@ struct Options {
     int64_t fft_pad[3] = {0, 0, 0};    // explicit padded sizes on the rocFFT path (0: choose)
     bool    skip_empty = true;         // convolution passes skip planes the fused rotate kernel found empty (exact; option for A/B runs)
     int64_t beads_pair_cap = (int64_t)1 << 28;   // bead renderer and volume injection: (brick, item) pairs one chunk may bin; larger calls run in chunks (beads.hip, aberrations.hip)
+    int64_t reject_batch = 0;          // rejection sampler: trials per launch (0 = auto: 4 per wanted sample, 4096 .. 2^20) (procedural.hip)
 };
 const Options& env_options();
 int parse_option(Options& o, const char* name, const char* value);   // MVSIM_OK / MVSIM_EINVAL
@@ -228,6 +229,8 @@ struct mvsim_ctx {
     mvsim::DevBuf pqueue;                   // Poisson work queue: [count][items]
     mvsim::DevBuf sphere_list;              // phantom generator: (centre, radius, value) items
     mvsim::DevBuf beads_buf[8];             // bead renderer (beads.hip): points, jobs, per-bead records, pair keys / values, sort temp, scratch
+    mvsim::DevBuf proc_buf[10];             // procedural phantom (procedural.hip): Perlin tables, sphere lists and records, counts, pair keys / values,
+                                            // scan / sort temp, ownership mask, sampler flags and positions
     mvsim::DevBuf plane_flags;              // per-plane non-zero flags of the current view (rotate_fft.hip -> the convolution passes)
     int*          empty_hint = nullptr;     // page-locked word the device writes: empty planes of the last view that carried flags (-1: none yet)
     unsigned int* queue_hint = nullptr;     // page-locked word the device raises: sixteenths of a block's voxels the fullest refused queue segment needed
@@ -325,7 +328,8 @@ struct mvsim_ctx {
 // are written against it.  Traits say where the three have always differed:
 //   WS_KEPT      partials, partials_e: mvsim_release_caches keeps them (the fixed-size scalar / partial-sum slots of PARTIALS_BYTES and
 //                SUM_BLOCKS doubles, no cache that grows with a volume); mvsim_destroy frees them like everything else.
-//   WS_NO_EPOCH  beads_buf: carries no allocation epoch -- no captured view graph holds an address inside the bead renderer's buffers.
+//   WS_NO_EPOCH  beads_buf, proc_buf: carry no allocation epoch -- no captured view graph holds an address inside the bead renderer's or the
+//                procedural phantom's buffers.
 enum { WS_KEPT = 1, WS_NO_EPOCH = 2 };
 template <class F> inline void mvsim_ctx::each_workspace(F&& f)
 {
@@ -337,6 +341,7 @@ template <class F> inline void mvsim_ctx::each_workspace(F&& f)
     f(partials, WS_KEPT);
     f(partials_e, WS_KEPT);
     for (mvsim::DevBuf& b : beads_buf) f(b, WS_NO_EPOCH);
+    for (mvsim::DevBuf& b : proc_buf) f(b, WS_NO_EPOCH);
 }
 
 inline mvsim_ctx::mvsim_ctx()
@@ -403,6 +408,36 @@ int render_beads_dev(mvsim_ctx* ctx, const double* xyz, const int64_t* view_offs
                      const int64_t dim[3], const int64_t imin[3], const double sigma[3], float* const* out_f32, uint16_t* const* out_u16);
 int beads_normalize_dev(mvsim_ctx* ctx, float* img, int64_t n);
 void beads_release(mvsim_ctx* ctx);
+// the procedural phantom (procedural.hip); arguments validated by the caller (api_sims.cpp).  *_upload puts the host tables of a field
+// on the device (synchronous); the launches that follow are asynchronous on the context's stream.
+struct PerlinParams {
+    double scale[3];
+    int    ext[3];
+    int    nvec;
+    double threshold;       // NaN: the raw value
+};
+struct PerlinDev {
+    PerlinParams   P;
+    const double*  grad;    // device: n x 3
+    const int32_t* perm;    // device: n
+};
+struct SpheresDev {
+    const double* centres;  // device: n x 3
+    const double* radii;    // device: n
+    const void*   recs;     // device: per-sphere records of procedural.hip
+    int64_t       n;
+    float         background;
+};
+constexpr int PERLIN_MAX_VECTORS = 1536;   // 28 bytes of LDS per vector: 42 KiB
+int perlin_upload(mvsim_ctx* ctx, const mvsim_perlin* p, PerlinDev* dev);
+int perlin_at_dev(mvsim_ctx* ctx, const PerlinDev& pd, const double* xyz, int64_t n, double* out);
+int perlin_raster_dev(mvsim_ctx* ctx, const PerlinDev& pd, const int64_t origin[3], const int64_t dim[3], float* out);
+int spheres_upload(mvsim_ctx* ctx, const mvsim_sphere_set* s, SpheresDev* dev);
+int spheres_at_dev(mvsim_ctx* ctx, const SpheresDev& sd, const double* xyz, int64_t n, float* out);
+int spheres_raster_dev(mvsim_ctx* ctx, const mvsim_sphere_set* s, const SpheresDev& sd, const int64_t origin[3], const int64_t dim[3],
+                       int combine, float* out);
+int rejection_sample_dev(mvsim_ctx* ctx, uint64_t state, const double rmin[3], const double rmax[3], int64_t n_samples, const PerlinDev* pd,
+                         const SpheresDev* sd, int64_t max_trials, double* xyz_out, int64_t* n_trials);
 // the refraction simulator (aberrations.hip); arguments validated by the caller (api_sims.cpp), volumes on the device
 void aberr_inject_geometry(const double sigma[3], int size[3], double tss[3]);
 int aberr_inject_dev(mvsim_ctx* ctx, float* image, float* weight, const int64_t dim[3], const double sigma[3], const double* xyz,
