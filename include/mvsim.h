@@ -70,9 +70,10 @@ int  mvsim_join(mvsim_ctx* ctx);
  * view concurrent with the next view's rotate+attenuate; 1 = only on the context's own stream, see mvsim_join; both
  * overlaps are on by default -- results are bit-identical to the serial order -- and are switched off for profiles whose
  * per-kernel durations must add up to the stage times), "fuse_tail" = 0|1 (adjust +
- * extract + Poisson phase 1 in the epilogue of the convolution's last pass), "fused_fftx" = auto|1|0 (per-view pipeline: rotate + attenuate + the x transform of
+ * extract + Poisson phase 1 in the epilogue of the convolution's last pass), "fused_fftx" = auto|1|0|roles (per-view pipeline: rotate + attenuate + the x transform of
  * the FFT convolution as one kernel, so that the attenuated volume crosses HBM only when requested; auto = from 131072
- * columns up), "attenuate" = serial|scan (mvsim_attenuate3d
+ * columns up, its waves split into walkers and transformers for rows of up to 512 voxels; roles = that kernel whenever
+ * the geometry allows; 1 = the kernel whose waves all walk and transform), "attenuate" = serial|scan (mvsim_attenuate3d
  * as a wavefront-level prefix scan along the illumination axis: parallel in y, not bit-identical to the serial walk), "beads_pair_cap" =
  * 1024..2^31 ((brick, bead) pairs the bead renderer bins at once; larger calls run in chunks with identical results; the refraction
  * simulator's injection bins its (brick, step) pairs under the same cap, and so does the sphere raster of the procedural phantom),

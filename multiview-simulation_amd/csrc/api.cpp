@@ -54,7 +54,7 @@ int parse_option(Options& o, const char* name, const char* value)
     if (n == "reject_batch") return number(7, 1, 1LL << 20, &o.reject_batch, 0);      // trials per launch of the rejection sampler
     if (n == "fuse_tail") return flag(&o.fuse_tail);
     if (n == "psf_overlap") return flag(&o.psf_overlap);
-    if (n == "fused_fftx") return word({{"auto", 2}, {"1", 1}, {"on", 1}, {"0", 0}, {"off", 0}}, &o.fused_fftx);
+    if (n == "fused_fftx") return word({{"auto", 2}, {"1", 1}, {"on", 1}, {"0", 0}, {"off", 0}, {"roles", 3}}, &o.fused_fftx);
     if (n == "tail_overlap") return word({{"0", 0}, {"off", 0}, {"1", 1}, {"on", 1}, {"own", 1}, {"2", 2}, {"any", 2}}, &o.tail_overlap);
     if (n == "acq_transfer") return word({{"auto", 1}, {"u16", 1}, {"f32", 0}}, &o.acq_u16);
     if (n == "host_threads") return number(3, 1, 256, &o.host_threads, 0);

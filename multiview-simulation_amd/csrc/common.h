@@ -146,7 +146,9 @@ struct Options {
                                        // against 20 us for the two kernels; break-even at 256^3)
     int     fused_fftx = 2;            // rotate + attenuate + the convolution's x transform as ONE kernel in the per-view pipeline
                                        // (rotate_fft.hip; `att` crosses HBM only when requested): 0 off, 1 whenever the geometry
-                                       // allows, 2 auto (production): from 131072 columns up, like fused_rotate
+                                       // allows (every wave walks and transforms), 2 auto (production): from 131072 columns up, like
+                                       // fused_rotate, with the block's waves split into walkers and transformers where rows have at most
+                                       // 512 voxels, 3 "roles": that kernel whenever the geometry allows
     bool    attenuate_scan = false;    // attenuate3d (stage operator) as a wavefront prefix scan along y: re-associates the
                                        // fp64 products (float outputs differ from the serial walk by one ulp on < 1e-6 of the voxels)
     int     poisson_queue = 1;         // 1: two-launch Poisson (streaming kernel with wave-level compaction + work-queue

@@ -427,7 +427,8 @@ struct RotFftArgs {
 // half lengths the fused kernel is instantiated for (rows of up to 1024 voxels with PSFs of up to 64 taps); the plans --
 // radices and with them the layout of the twiddle table -- are the size table's own
 constexpr bool rot_fftx_len_ok(int len) { return len >= 72 && len <= 576; }
-int  launch_rot_fftx(mvsim_ctx* ctx, int M, const RotFftArgs& a, bool write_out);
+// roles: the walker / transformer instance where it applies (rows of up to 512 voxels), else the kernel every wave walks and transforms in
+int  launch_rot_fftx(mvsim_ctx* ctx, int M, const RotFftArgs& a, bool write_out, bool roles);
 
 }  // namespace fft
 }  // namespace mvsim

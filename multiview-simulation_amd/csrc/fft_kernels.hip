@@ -1910,7 +1910,7 @@ int rotate_attenuate_fftx(mvsim_ctx* ctx, const float* gt, float* rot_or_null, f
         a.plane_nz = ctx->plane_flags.as<int>();
         *plane_nz = a.plane_nz;
     }
-    MVSIM_TRY(launch_rot_fftx(ctx, M, a, rot_or_null != nullptr || att_or_null != nullptr));
+    MVSIM_TRY(launch_rot_fftx(ctx, M, a, rot_or_null != nullptr || att_or_null != nullptr, ctx->opt.fused_fftx >= 2));
     *done = true;
     return MVSIM_OK;
 }
