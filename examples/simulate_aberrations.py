@@ -7,6 +7,10 @@ refr_img_<illum>_<ri>_<z>.tif, refr_weight_<...>.tif and proj_<...>.tif.  The re
 (z = 176 of 289 planes, lsMiddle = 1, lsEdge = 3, ri = 1.1, 200 000 rays, 500 rays per camera pixel).
 
     python examples/simulate_aberrations.py [--size 96] [--z 40 [41 ...]] [--illum] [--out DIR]
+
+--reference-phantom makes the pair the way the reference does, simulate(rnd, dir) (:408-440): noise on a canvas of refractive indices,
+multiSpheres, 2x down-sampling.  The canvas is --ri-tiff PATH (the reference's block4.tif, 580^3 there) or, without it,
+synthetic.index_block(2 * (size + 1)), a stand-in.  The canvas needs at least 190 voxels per dimension (size >= 94).
 """
 import argparse
 import importlib
@@ -28,13 +32,23 @@ def main():
     ap.add_argument("--rays", type=int, default=200000)
     ap.add_argument("--rays-per-pixel", type=int, default=500)
     ap.add_argument("--out", default=".")
+    ap.add_argument("--reference-phantom", action="store_true", help="image / index pair from simulate(rnd, dir) instead of smooth blobs")
+    ap.add_argument("--ri-tiff", default=None, help="the canvas of refractive indices (block4.tif) for --reference-phantom")
     args = ap.parse_args()
     mvs = importlib.import_module("multiview-simulation_amd")
     synth = importlib.import_module("multiview-simulation_amd.synthetic")
     n = args.size
+    if args.reference_phantom:
+        canvas = mvs.Tools.open(args.ri_tiff) if args.ri_tiff else synth.index_block(2 * (n + 1))
+        t0 = time.perf_counter()
+        img, ri_img = mvs.SimulateMultiViewAberrations.simulatePhantom(ri=canvas)
+        n = img.shape[0]
+        print(f"phantom: {' x '.join(str(d) for d in img.shape[::-1])} from a canvas of {' x '.join(str(d) for d in canvas.shape[::-1])}, "
+              f"image max {float(img.max()):.4g}, {time.perf_counter() - t0:.2f} s")
+    else:
+        img = synth.smooth_blobs(n, seed=3, count=8, sigma=(0.18, 0.3))
+        ri_img = synth.smooth_blobs(n, seed=4)
     planes = args.z if args.z is not None else [176 * n // 289]
-    img = synth.smooth_blobs(n, seed=3, count=8, sigma=(0.18, 0.3))
-    ri_img = synth.smooth_blobs(n, seed=4)
     os.makedirs(args.out, exist_ok=True)
     for z in planes:
         tag = f"{'true' if args.illum else 'false'}_{args.ri}_{z}"          # illum + "_" + ri + "_" + z (:628)

@@ -77,7 +77,8 @@ int  mvsim_join(mvsim_ctx* ctx);
  * as a wavefront-level prefix scan along the illumination axis: parallel in y, not bit-identical to the serial walk), "beads_pair_cap" =
  * 1024..2^31 ((brick, bead) pairs the bead renderer bins at once; larger calls run in chunks with identical results; the refraction
  * simulator's injection bins its (brick, step) pairs under the same cap, and so does the sphere raster of the procedural phantom),
- * "reject_batch" = 1..2^20|auto (trials per launch of mvsim_rejection_sample; the result does not depend on it).
+ * "reject_batch" = 1..2^20|auto (trials per launch of mvsim_rejection_sample; the result does not depend on it),
+ * "sphere_walk" = host|device|device_only|auto (mvsim_draw_spheres, mvsim_multi_spheres: see mvsim_multi_spheres; the result does not depend on it).
  * MVSIM_OPTIONS="name=value;name=value" sets any of them process-wide.  Unknown names or values: MVSIM_EINVAL. */
 int  mvsim_set_option(mvsim_ctx* ctx, const char* name, const char* value);
 /* Release cached FFT plans / workspaces / PSF spectra held by the context. */
@@ -342,6 +343,31 @@ int mvsim_project_to_camera(mvsim_ctx* ctx, const float* ri_img, const float* re
                             int rays_per_pixel, uint64_t* rnd_state, float* proj);
 int mvsim_project_to_camera_dev(mvsim_ctx* ctx, const float* ri_img_dev, const float* refr_dev, const int64_t dim[3], int current_z,
                                 int rays_per_pixel, uint64_t* rnd_state, float* proj_dev);
+/* The simulator's phantom, SMVA:408-440 simulate(rnd, dir): everything behind its Tools.open(dir + "block4.tif") -- a file the reference
+ * does not ship; the caller supplies that canvas of refractive indices.
+ * SMVA:425-426: voxel i of ri (x fastest, n voxels, n == 0 is legal) becomes (float)Math.max(0, ri[i] + (nextDouble() - 0.5) / 10), in
+ * place; voxel i takes draw i of the caller's java.util.Random (see mvsim_draw_spheres), every lane jumping the generator ahead on its
+ * own; rnd_state is advanced by the 2 n generator steps.  Bit-exact. */
+int mvsim_ri_noise(mvsim_ctx* ctx, float* ri, int64_t n, uint64_t* rnd_state);
+int mvsim_ri_noise_dev(mvsim_ctx* ctx, float* ri_dev, int64_t n, uint64_t* rnd_state);
+/* SMVA:474-586 multiSpheres(image, ri, scale, rnd), in place on two volumes of the same dimensions, with the ranges the reference
+ * hard-codes: {0.5, 1.0} for the image, {1.0, 1.1} for the index volume (its min == max branches never run and are not offered).  The walk
+ * is drawSpheres' with a large sphere of radius min(dim) / 2 - 47 scale - 1 about dim / 2, radius = Math.max(nextInt(10 scale) + 1,
+ * 10 scale - 1), and one voxel in 100 000 drawn (rv * 100000 < 1).  image: Math.max(value, existing).  ri: a covered voxel that holds
+ * exactly 5.0 takes the sphere's value, any other the maximum -- built as two passes in place: every covered voxel equal to 5.0 is set
+ * to -infinity, then all spheres are max-composited (the outcome does not depend on the order of the spheres: after the first
+ * replacement a voxel holds at most 1.1).  Caveat: a call that fails between the two passes (a HIP error) leaves -infinity in those
+ * voxels.  MVSIM_EINVAL, nothing written and rnd_state untouched: the large sphere's radius is negative, or a small sphere leaves the
+ * volume (the reference throws there).  n_spheres may be NULL.  Option "sphere_walk" = host|device|device_only|auto: who walks the sequential random
+ * stream over the voxels of the large sphere -- the host, one voxel after the other, or the GPU (csrc/sphere_walk.h: the stream cut in chunks, the
+ * orbit of voxel starts resolved per chunk and stitched by a scan; the host walk takes over in the cases the device walk does not vouch
+ * for; device_only: MVSIM_EINVAL in those cases, for tests).  Same bits either way.  auto (the default): mvsim_draw_spheres on the host, mvsim_multi_spheres on the device. */
+int mvsim_multi_spheres(mvsim_ctx* ctx, float* img, float* ri, const int64_t dim[3], int scale, uint64_t* rnd_state, int64_t* n_spheres);
+int mvsim_multi_spheres_dev(mvsim_ctx* ctx, float* img_dev, float* ri_dev, const int64_t dim[3], int scale, uint64_t* rnd_state,
+                            int64_t* n_spheres);
+/* Host only: stream positions per chunk of the device walk and the number of entry offsets resolved per chunk (tests aim at chunk
+ * boundaries with these). */
+int mvsim_sphere_walk_geometry(int64_t* chunk_positions, int* max_entry);
 
 /* ---- stage operators, device-resident buffers (asynchronous on the context stream) ------ */
 /* (mvsim_draw_spheres_dev returns after the host walk; the compositing kernels are asynchronous.) */

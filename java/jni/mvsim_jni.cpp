@@ -477,6 +477,50 @@ JNIEXPORT jlong JNICALL JNI_FN(drawSpheres)(JNIEnv* env, jclass, jlong h, jobjec
     return static_cast<jlong>(n);
 }
 
+// ---- the refraction simulator's phantom (mvsim_ri_noise, mvsim_multi_spheres): the generator state in and out through long[1] ----
+JNIEXPORT void JNICALL JNI_FN(riNoise)(JNIEnv* env, jclass, jlong h, jobject ri, jlong n, jlongArray rnd_state)
+{
+    if (n < 0) { throw_new(env, "java/lang/IllegalArgumentException", "riNoise: negative count"); return; }
+    float* p = fptr(env, ri, n, "riNoise: buffer smaller than the count", n == 0);
+    if (!p && n > 0) return;
+    uint64_t state = 0;
+    if (!state_in(env, rnd_state, "riNoise: long[1] state expected", &state)) return;
+    const int rc = mvsim_ri_noise(ctx_of(h), p, n, &state);
+    if (rc != MVSIM_OK) { throw_for(env, rc); return; }
+    const jlong st = static_cast<jlong>(state);
+    env->SetLongArrayRegion(rnd_state, 0, 1, &st);
+}
+
+JNIEXPORT jlong JNICALL JNI_FN(multiSpheres)(JNIEnv* env, jclass, jlong h, jobject img, jobject ri, jlongArray dim, jint scale,
+                                             jlongArray rnd_state)
+{
+    Dim d(env, dim);
+    if (!d.ok) return 0;
+    float* pi = fptr(env, img, d.n(), "multiSpheres: image buffer smaller than the dimensions");
+    float* pr = fptr(env, ri, d.n(), "multiSpheres: index buffer smaller than the dimensions");
+    if (!pi || !pr) return 0;
+    uint64_t state = 0;
+    if (!state_in(env, rnd_state, "multiSpheres: long[1] state expected", &state)) return 0;
+    int64_t n = 0;
+    const int rc = mvsim_multi_spheres(ctx_of(h), pi, pr, d.d, scale, &state, &n);
+    if (rc != MVSIM_OK) { throw_for(env, rc); return 0; }
+    const jlong st = static_cast<jlong>(state);
+    env->SetLongArrayRegion(rnd_state, 0, 1, &st);
+    return static_cast<jlong>(n);
+}
+
+// out[0] = stream positions per chunk of the device walk, out[1] = entry offsets resolved per chunk
+JNIEXPORT void JNICALL JNI_FN(sphereWalkGeometry)(JNIEnv* env, jclass, jlongArray out)
+{
+    if (!out || env->GetArrayLength(out) < 2) { throw_new(env, "java/lang/IllegalArgumentException", "sphereWalkGeometry: long[2] expected"); return; }
+    int64_t chunk = 0;
+    int entries = 0;
+    const int rc = mvsim_sphere_walk_geometry(&chunk, &entries);
+    if (rc != MVSIM_OK) { throw_for(env, rc); return; }
+    const jlong v[2] = {static_cast<jlong>(chunk), static_cast<jlong>(entries)};
+    env->SetLongArrayRegion(out, 0, 2, v);
+}
+
 JNIEXPORT void JNICALL JNI_FN(splatSpheres)(JNIEnv* env, jclass, jlong h, jobject img, jlongArray dim, jintArray geometry,
                                             jfloatArray values)
 {

@@ -66,7 +66,13 @@ final class MvsimNative
 	/** drawSpheres (:436-522), in place; rndState[0] is the 48-bit java.util.Random state, advanced on return; returns the sphere count. */
 	static native long drawSpheres( long ctx, FloatBuffer img, long[] dim, double minValue, double maxValue, int scale,
 			boolean halfPixelOffset, long[] rndState );
-	/** mvsim_splat_spheres: geometry = { cx, cy, cz, radius } per sphere, values = one float per sphere; in place. */
+	/** The noise on the refractive-index volume (SimulateMultiViewAberrations :425-426) over n floats, in place; rndState as for drawSpheres. */
+	static native void riNoise( long ctx, FloatBuffer ri, long n, long[] rndState );
+	/** multiSpheres (SimulateMultiViewAberrations :474-586), in place on image and index volume; returns the sphere count. */
+	static native long multiSpheres( long ctx, FloatBuffer img, FloatBuffer ri, long[] dim, int scale, long[] rndState );
+	/** out[0] = stream positions per chunk of the device walk, out[1] = entry offsets resolved per chunk (mvsim_sphere_walk_geometry). */
+	static native void sphereWalkGeometry( long[] out );
+	/** mvsim_splat_spheres: geometry ={ cx, cy, cz, radius } per sphere, values = one float per sphere; in place. */
 	static native void splatSpheres( long ctx, FloatBuffer img, long[] dim, int[] geometry, float[] values );
 	/** downSample2x (:394-424): out has dim/2 - 1 samples per dimension. */
 	static native void downSample2x( long ctx, FloatBuffer in, long[] dim, FloatBuffer out );

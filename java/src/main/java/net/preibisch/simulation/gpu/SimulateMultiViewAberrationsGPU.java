@@ -14,7 +14,8 @@ import net.imglib2.util.ValuePair;
 import net.imglib2.view.Views;
 
 /**
- * GPU form of {@code SimulateMultiViewAberrations.refract3d} and {@code projectToCamera}: the volumes cross to
+ * GPU form of {@code SimulateMultiViewAberrations.refract3d}, {@code projectToCamera}, {@code multiSpheres} and
+ * {@code simulate( rnd, dir )} (with the canvas of block4.tif passed in): the volumes cross to
  * {@code MvsimNative} as direct buffers, the rays are traced, injected and summed by the kernels of aberrations.hip.  The random
  * streams are the reference's -- {@code new Random(2423)} per refract3d call, one {@code Random(464232194)} shared by the
  * projectToCamera calls of this object -- kept as the 48-bit generator state the native side jumps ahead.
@@ -57,6 +58,52 @@ public class SimulateMultiViewAberrationsGPU
 		final FloatBuffer proj = direct( ( int ) ( dim[ 0 ] * dim[ 1 ] ) );
 		MvsimNative.projectToCamera( ctx, toBuffer( imgRi ), toBuffer( refr ), dim, currentzPlane, 500, cameraState, proj );
 		return toImg( proj, new long[] { dim[ 0 ], dim[ 1 ] } );
+	}
+
+	/**
+	 * multiSpheres (:474-586), in place on both images, with the reference's hard-coded ranges.  The generator is a {@link GpuRandom}:
+	 * its 48-bit state crosses the boundary, the native library walks the large sphere (on the GPU by default) and hands the state back
+	 * advanced exactly as the reference advances its java.util.Random.  Returns the number of small spheres drawn.
+	 */
+	public long multiSpheres( final Img< FloatType > image, final Img< FloatType > ri, final int scale, final GpuRandom rnd )
+	{
+		final long[] dim = dims( image );
+		final FloatBuffer bi = toBuffer( image ), br = toBuffer( ri );
+		final long[] state = { rnd.getState() };
+		final long n = MvsimNative.multiSpheres( ctx, bi, br, dim, scale, state );
+		rnd.setState( state[ 0 ] );
+		copyBack( bi, image );
+		copyBack( br, ri );
+		return n;
+	}
+
+	/**
+	 * simulate( rnd, dir ) (:408-440) behind its Tools.open: {@code ri} is the canvas of refractive indices the reference reads from
+	 * block4.tif (not shipped; 580^3 there).  Noise on the canvas, multiSpheres on a zero image and the canvas, both down-sampled 2x.
+	 */
+	public Pair< Img< FloatType >, Img< FloatType > > simulate( final GpuRandom rnd, final RandomAccessibleInterval< FloatType > ri )
+	{
+		final int scale = 2;
+		final long[] dim = dims( ri );
+		final int n = ( int ) ( dim[ 0 ] * dim[ 1 ] * dim[ 2 ] );
+		final FloatBuffer bi = direct( n ), br = toBuffer( ri );
+		final long[] state = { rnd.getState() };
+		MvsimNative.riNoise( ctx, br, n, state );
+		MvsimNative.multiSpheres( ctx, bi, br, dim, scale, state );
+		rnd.setState( state[ 0 ] );
+		final long[] o = { dim[ 0 ] / 2 - 1, dim[ 1 ] / 2 - 1, dim[ 2 ] / 2 - 1 };
+		final FloatBuffer oi = direct( ( int ) ( o[ 0 ] * o[ 1 ] * o[ 2 ] ) ), or = direct( ( int ) ( o[ 0 ] * o[ 1 ] * o[ 2 ] ) );
+		MvsimNative.downSample2x( ctx, bi, dim, oi );
+		MvsimNative.downSample2x( ctx, br, dim, or );
+		return new ValuePair<>( toImg( oi, o ), toImg( or, o ) );
+	}
+
+	static void copyBack( final FloatBuffer b, final Img< FloatType > img )
+	{
+		b.rewind();
+		final Cursor< FloatType > c = Views.flatIterable( img ).cursor();
+		while ( c.hasNext() )
+			c.next().set( b.get() );
 	}
 
 	static long[] dims( final RandomAccessibleInterval< FloatType > img )

@@ -184,7 +184,7 @@ class Context(ContextAberrations, ContextPhantoms):
     def set_option(self, name: str, value) -> None:
         """Run-time switch of this context (mvsim_set_option): fft_zpass, fft_backend, fft_pad, fused_rotate,
         poisson_queue, poisson_queue_share, early_sum, graph, fuse_tail, psf_overlap, tail_overlap, attenuate, broadcast, view_batch,
-        view_lanes, acq_transfer, host_threads (include/mvsim.h and DESIGN.md list them with their values)."""
+        view_lanes, acq_transfer, host_threads, sphere_walk (include/mvsim.h and DESIGN.md list them with their values)."""
         if isinstance(value, bool):
             value = "1" if value else "0"
         _lib.check(self._L.mvsim_set_option(self._h, name.encode(), str(value).encode()))
@@ -413,6 +413,74 @@ class Context(ContextAberrations, ContextPhantoms):
             self.dev_free(canvas)
             if out_d:
                 self.dev_free(out_d)
+
+    # -- the phantom of the refraction simulator (SimulateMultiViewAberrations.java:408-586)
+    def ri_noise(self, ri: np.ndarray, rnd: "JavaRandom") -> None:
+        """The noise on the refractive-index volume (:425-426), in place on a contiguous float32 array: voxel i, x fastest, becomes
+        (float)Math.max(0, t + (nextDouble() - 0.5) / 10); ``rnd`` advances by two steps per voxel."""
+        if ri.size:                                   # an empty volume is legal here: nothing is drawn
+            _check_inplace(ri)
+        st = C.c_uint64(rnd._s)
+        _lib.check(self._L.mvsim_ri_noise(self._h, _ptr(ri), ri.size, C.byref(st)))
+        rnd._s = int(st.value)
+
+    def multi_spheres(self, img: np.ndarray, ri: np.ndarray, scale: int, rnd: "JavaRandom") -> int:
+        """multiSpheres (:474-586), in place on two contiguous float32 (Nz,Ny,Nx) volumes of one shape, with the reference's hard-coded
+        ranges ({0.5, 1.0} image, {1.0, 1.1} index volume); ``rnd`` is advanced exactly as the reference advances its
+        java.util.Random.  Returns the number of small spheres drawn."""
+        _check_inplace(img)
+        _check_inplace(ri)
+        if img.shape != ri.shape:
+            raise ValueError("multiSpheres: image and index volume must have the same shape")
+        st = C.c_uint64(rnd._s)
+        n = C.c_int64(0)
+        _lib.check(self._L.mvsim_multi_spheres(self._h, _ptr(img), _ptr(ri), _dim(img), int(scale), C.byref(st), C.byref(n)))
+        rnd._s = int(st.value)
+        return int(n.value)
+
+    def simulate_aberration_phantom(self, ri_canvas, rnd: "JavaRandom", scale: int = 2):
+        """`simulate(rnd, dir)` (:408-440) behind its Tools.open: ``ri_canvas`` is the (Nz,Ny,Nx) canvas of refractive indices the
+        reference reads from block4.tif.  Noise on the canvas, multiSpheres on a zero image of the same shape and the canvas, 2x
+        down-sampling of both when scale == 2 -- both canvases resident in HBM, only the two results cross PCIe.  Returns (img, ri)."""
+        v = _as_volume(ri_canvas, "index canvas")
+        nz, ny, nx = v.shape
+        dim = (C.c_int64 * 3)(nx, ny, nz)
+        nbytes = v.size * 4
+        bufs = []
+        try:
+            img_d = self.dev_alloc(nbytes)
+            bufs.append(img_d)
+            ri_d = self.dev_alloc(nbytes)
+            bufs.append(ri_d)
+            _lib.check(self._L.mvsim_dev_memset(self._h, img_d, 0, nbytes))
+            self.upload(ri_d, v)
+            st = C.c_uint64(rnd._s)
+            _lib.check(self._L.mvsim_ri_noise_dev(self._h, ri_d, v.size, C.byref(st)))
+            _lib.check(self._L.mvsim_multi_spheres_dev(self._h, img_d, ri_d, dim, int(scale), C.byref(st), None))
+            if scale != 2:
+                rnd._s = int(st.value)
+                return self.download(img_d, v.shape), self.download(ri_d, v.shape)
+            if min(v.shape) < 4:
+                raise ValueError("downSample2x needs at least 4 samples per dimension")
+            oshape = (nz // 2 - 1, ny // 2 - 1, nx // 2 - 1)
+            outs = []
+            for src in (img_d, ri_d):
+                out_d = self.dev_alloc(int(np.prod(oshape)) * 4)
+                bufs.append(out_d)
+                _lib.check(self._L.mvsim_downsample2x_dev(self._h, src, dim, out_d))
+                outs.append(self.download(out_d, oshape))
+            rnd._s = int(st.value)
+            return outs[0], outs[1]
+        finally:
+            for b in bufs:
+                self.dev_free(b)
+
+    def sphere_walk_geometry(self):
+        """(stream positions per chunk of the device walk, entry offsets resolved per chunk): mvsim_sphere_walk_geometry."""
+        p = C.c_int64(0)
+        e = C.c_int(0)
+        _lib.check(self._L.mvsim_sphere_walk_geometry(C.byref(p), C.byref(e)))
+        return int(p.value), int(e.value)
 
     def compute_weight_image(self, shape_zyx) -> np.ndarray:
         nz, ny, nx = (int(s) for s in shape_zyx)

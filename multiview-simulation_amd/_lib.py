@@ -227,6 +227,11 @@ SIGNATURES = {
     "mvsim_volume_project_dev": (C.c_int, [_vp, _vp, _vp, _i64p, _vp]),
     "mvsim_project_to_camera": (C.c_int, [_vp, _vp, _vp, _i64p, C.c_int, C.c_int, C.POINTER(C.c_uint64), _vp]),
     "mvsim_project_to_camera_dev": (C.c_int, [_vp, _vp, _vp, _i64p, C.c_int, C.c_int, C.POINTER(C.c_uint64), _vp]),
+    "mvsim_ri_noise": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(C.c_uint64)]),
+    "mvsim_ri_noise_dev": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(C.c_uint64)]),
+    "mvsim_multi_spheres": (C.c_int, [_vp, _vp, _vp, _i64p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
+    "mvsim_multi_spheres_dev": (C.c_int, [_vp, _vp, _vp, _i64p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
+    "mvsim_sphere_walk_geometry": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
 }
 
 _lib = None

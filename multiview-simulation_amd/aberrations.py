@@ -6,8 +6,12 @@ single-vector helpers of ``Raytrace`` and the light-sheet fit are a handful of f
 Volumes are ``(Nz, Ny, Nx)`` float32 arrays, positions ``(n, 3)`` float64 with x first.  Random numbers come from a ``JavaRandom``
 that is advanced exactly as the reference advances its ``java.util.Random``.
 
-Out of scope, as in the C ABI: ``multiSpheres`` and ``simulate(rnd, dir)`` (they need ``block4.tif``, a file the reference does not
-ship), ``RayTracingTest``, ``ClearingMap``, ``RefractiveIndexMap`` and ``cluster/``."""
+The simulator's own phantom, ``simulate(rnd, dir)`` (:408-440), is ``simulatePhantom``: everything behind its ``Tools.open(dir +
+"block4.tif")``.  The reference does not ship that file, so the caller passes the canvas of refractive indices (or a directory that
+holds the file; ``synthetic.index_block`` is a stand-in).  ``multiSpheres`` uses the ranges the reference hard-codes; its
+``min == max`` branches never run and are not offered.
+
+Out of scope, as in the C ABI: ``RayTracingTest``, ``ClearingMap``, ``RefractiveIndexMap`` and ``cluster/``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -342,6 +346,23 @@ class SimulateMultiViewAberrations:
     def downSample2x(img) -> np.ndarray:
         """:442-472 -- the kernel of SimulateMultiViewDataset.downSample2x."""
         return _ctx().downsample2x(img)
+
+    @staticmethod
+    def multiSpheres(image, ri, scale, rnd, ctx=None) -> int:
+        """:474-586, in place on two float32 volumes of one shape; returns the number of small spheres drawn."""
+        return (ctx or _ctx()).multi_spheres(image, ri, scale, rnd)
+
+    @staticmethod
+    def simulatePhantom(rnd=None, ri=None, dir=None, scale=2, ctx=None):
+        """simulate(rnd, dir) (:408-440): noise on the index canvas, multiSpheres on a zero image and the canvas, both down-sampled
+        2x.  ``ri``: the (Nz, Ny, Nx) canvas the reference reads from block4.tif (580^3 there), or ``dir``: where that file is, opened
+        through Tools.open.  ``rnd``: the class's generator by default.  Returns (img, ri)."""
+        if ri is None:
+            if dir is None:
+                raise ValueError("simulatePhantom needs the index canvas (ri=) or the directory of block4.tif (dir=)")
+            from . import Tools
+            ri = Tools.open(str(dir) + "block4.tif")
+        return (ctx or _ctx()).simulate_aberration_phantom(ri, SimulateMultiViewAberrations._rnd() if rnd is None else rnd, scale)
 
     @staticmethod
     def simulate(imgIn, imgRi, illum, lsMiddle, lsEdge, ri, z, numRays=200000, raysPerPixel=500, ctx=None) -> dict:

@@ -80,6 +80,69 @@ int mvsim_splat_spheres(mvsim_ctx* ctx, float* img, const int64_t dim[3], const 
     return down(ctx, img, ctx->vol_a.p, bytes);
 }
 
+// ---- the phantom of the refraction simulator: noise on the index volume, multiSpheres (phantom.hip, sphere_walk.hip) ----------------
+int mvsim_sphere_walk_geometry(int64_t* chunk_positions, int* max_entry)
+{
+    MVSIM_CHECK_ARG(chunk_positions && max_entry, "null pointer");
+    *chunk_positions = SW_CHUNK;
+    *max_entry = SW_ENTRIES;
+    return MVSIM_OK;
+}
+
+static int ri_noise_args(mvsim_ctx* ctx, const float* ri, int64_t n, const uint64_t* rnd_state)
+{
+    MVSIM_CHECK_ARG(rnd_state != nullptr, "null rnd_state");
+    MVSIM_CHECK_ARG(n >= 0 && n < ((int64_t)1 << 40) && (ri || n == 0), "null volume or count outside 0 .. 2^40");
+    return set_device(ctx);
+}
+
+int mvsim_ri_noise_dev(mvsim_ctx* ctx, float* ri, int64_t n, uint64_t* rnd_state)
+{
+    MVSIM_TRY(ri_noise_args(ctx, ri, n, rnd_state));
+    MVSIM_TRY(ri_noise_dev(ctx, ri, n, *rnd_state & JR_MASK));
+    *rnd_state = jr_jump(*rnd_state & JR_MASK, 2 * (uint64_t)n);
+    return MVSIM_OK;
+}
+
+int mvsim_ri_noise(mvsim_ctx* ctx, float* ri, int64_t n, uint64_t* rnd_state)
+{
+    MVSIM_TRY(ri_noise_args(ctx, ri, n, rnd_state));
+    if (n > 0) {
+        const size_t bytes = (size_t)n * sizeof(float);
+        MVSIM_TRY(up(ctx, ctx->vol_a, ri, bytes));
+        MVSIM_TRY(ri_noise_dev(ctx, ctx->vol_a.as<float>(), n, *rnd_state & JR_MASK));
+        MVSIM_TRY(down(ctx, ri, ctx->vol_a.p, bytes));
+    }
+    *rnd_state = jr_jump(*rnd_state & JR_MASK, 2 * (uint64_t)n);
+    return MVSIM_OK;
+}
+
+static int multi_spheres_args(mvsim_ctx* ctx, const float* img, const float* ri, const int64_t dim[3], int scale, const uint64_t* rnd_state)
+{
+    MVSIM_TRY(set_device(ctx));
+    MVSIM_TRY(check_dim(dim));
+    MVSIM_CHECK_ARG(img && ri && img != ri && rnd_state, "null pointer or aliased volumes");
+    MVSIM_CHECK_ARG(scale >= 1 && scale <= 64, "scale must be in 1..64");
+    return MVSIM_OK;
+}
+
+int mvsim_multi_spheres_dev(mvsim_ctx* ctx, float* img, float* ri, const int64_t dim[3], int scale, uint64_t* rnd_state, int64_t* n_spheres)
+{
+    MVSIM_TRY(multi_spheres_args(ctx, img, ri, dim, scale, rnd_state));
+    return multi_spheres_dev(ctx, img, ri, dim, scale, rnd_state, n_spheres);
+}
+
+int mvsim_multi_spheres(mvsim_ctx* ctx, float* img, float* ri, const int64_t dim[3], int scale, uint64_t* rnd_state, int64_t* n_spheres)
+{
+    MVSIM_TRY(multi_spheres_args(ctx, img, ri, dim, scale, rnd_state));
+    const size_t bytes = (size_t)nvox(dim) * sizeof(float);
+    MVSIM_TRY(up(ctx, ctx->vol_a, img, bytes));
+    MVSIM_TRY(up(ctx, ctx->vol_b, ri, bytes));
+    MVSIM_TRY(multi_spheres_dev(ctx, ctx->vol_a.as<float>(), ctx->vol_b.as<float>(), dim, scale, rnd_state, n_spheres));
+    MVSIM_HIP(hipMemcpyAsync(img, ctx->vol_a.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return down(ctx, ri, ctx->vol_b.p, bytes);
+}
+
 // ---- bead images: SimulateBeads / SimulateBeads2 (beads.hip) ----------------------------------------------------------
 int mvsim_beads_random_points(uint64_t* rnd_state, int64_t n, const int64_t min[3], const int64_t max[3], double* xyz)
 {

@@ -18,6 +18,7 @@
 
 #include "../../include/mvsim.h"
 #include "extract_plan.h"
+#include "sphere_walk.h"
 
 // Attribution switches (tools/attribute_flags.sh, attribute_valu.sh, attribution_run.sh: builds that compile a part of a kernel's work
 // OUT -- and with it the correctness of the results -- to see what that part costs; the figures are in profiles/r04_attribution.txt).
@@ -196,6 +197,8 @@ struct Options {
     bool    skip_empty = true;         // convolution passes skip planes the fused rotate kernel found empty (exact; option for A/B runs)
     int64_t beads_pair_cap = (int64_t)1 << 28;   // bead renderer and volume injection: (brick, item) pairs one chunk may bin; larger calls run in chunks (beads.hip, aberrations.hip)
     int64_t reject_batch = 0;          // rejection sampler: trials per launch (0 = auto: 4 per wanted sample, 4096 .. 2^20) (procedural.hip)
+    int     sphere_walk = -1;          // the java.util.Random walk over the large sphere: 0 on the host, 1 on the device (sphere_walk.hip; the host
+                                       // walk where the device walk does not vouch for a case; 2: MVSIM_EINVAL there), -1 = each call's default: drawSpheres host, multiSpheres device
 };
 const Options& env_options();
 int parse_option(Options& o, const char* name, const char* value);   // MVSIM_OK / MVSIM_EINVAL
@@ -233,6 +236,7 @@ struct mvsim_ctx {
     mvsim::DevBuf beads_buf[8];             // bead renderer (beads.hip): points, jobs, per-bead records, pair keys / values, sort temp, scratch
     mvsim::DevBuf proc_buf[10];             // procedural phantom (procedural.hip): Perlin tables, sphere lists and records, counts, pair keys / values,
                                             // scan / sort temp, ownership mask, sampler flags and positions
+    mvsim::DevBuf walk_buf[4];              // device walk (sphere_walk.hip): event lists, chunk maps, scan results, accepted voxels
     mvsim::DevBuf plane_flags;              // per-plane non-zero flags of the current view (rotate_fft.hip -> the convolution passes)
     int*          empty_hint = nullptr;     // page-locked word the device writes: empty planes of the last view that carried flags (-1: none yet)
     unsigned int* queue_hint = nullptr;     // page-locked word the device raises: sixteenths of a block's voxels the fullest refused queue segment needed
@@ -330,8 +334,8 @@ struct mvsim_ctx {
 // are written against it.  Traits say where the three have always differed:
 //   WS_KEPT      partials, partials_e: mvsim_release_caches keeps them (the fixed-size scalar / partial-sum slots of PARTIALS_BYTES and
 //                SUM_BLOCKS doubles, no cache that grows with a volume); mvsim_destroy frees them like everything else.
-//   WS_NO_EPOCH  beads_buf, proc_buf: carry no allocation epoch -- no captured view graph holds an address inside the bead renderer's or the
-//                procedural phantom's buffers.
+//   WS_NO_EPOCH  beads_buf, proc_buf, walk_buf: carry no allocation epoch -- no captured view graph holds an address inside the bead
+//                renderer's, the procedural phantom's or the device walk's buffers.
 enum { WS_KEPT = 1, WS_NO_EPOCH = 2 };
 template <class F> inline void mvsim_ctx::each_workspace(F&& f)
 {
@@ -344,6 +348,7 @@ template <class F> inline void mvsim_ctx::each_workspace(F&& f)
     f(partials_e, WS_KEPT);
     for (mvsim::DevBuf& b : beads_buf) f(b, WS_NO_EPOCH);
     for (mvsim::DevBuf& b : proc_buf) f(b, WS_NO_EPOCH);
+    for (mvsim::DevBuf& b : walk_buf) f(b, WS_NO_EPOCH);
 }
 
 inline mvsim_ctx::mvsim_ctx()
@@ -405,6 +410,12 @@ int launch_downsample2x(hipStream_t s, const float* in, const int64_t dim[3], fl
 int draw_spheres_dev(mvsim_ctx* ctx, float* img, const int64_t dim[3], double min_value, double max_value, int scale,
                      int half_pixel_offset, uint64_t* rnd_state, int64_t* n_spheres);
 int splat_spheres_dev(mvsim_ctx* ctx, float* img, const int64_t dim[3], const mvsim_sphere* spheres, int64_t n);
+// the refraction simulator's phantom (phantom.hip): noise on the index volume, multiSpheres on image and index volume
+int ri_noise_dev(mvsim_ctx* ctx, float* ri, int64_t n, uint64_t state);
+int multi_spheres_dev(mvsim_ctx* ctx, float* img, float* ri, const int64_t dim[3], int scale, uint64_t* rnd_state, int64_t* n_spheres);
+// the walk over n voxels resolved on the device (sphere_walk.hip); *done = false: not vouched for, walk on the host
+int sphere_walk_dev(mvsim_ctx* ctx, uint64_t state, int64_t n, const WalkRule& rule, std::vector<WalkEntry>* entries, uint64_t* end_state,
+                    bool* done);
 // SimulateBeads.renderPoints on device outputs (beads.hip); arguments validated by the caller (api_sims.cpp)
 int render_beads_dev(mvsim_ctx* ctx, const double* xyz, const int64_t* view_offsets, int64_t n, const double* m12, int nviews,
                      const int64_t dim[3], const int64_t imin[3], const double sigma[3], float* const* out_f32, uint16_t* const* out_u16);

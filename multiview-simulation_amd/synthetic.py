@@ -107,6 +107,17 @@ def smooth_blobs(nx: int, ny: int | None = None, nz: int | None = None, seed: in
     return np.ascontiguousarray(lo + (hi - lo) * f, dtype=np.float32)
 
 
+def index_block(n: int = 580) -> np.ndarray:
+    """A stand-in for the canvas of refractive indices the refraction simulator reads from `block4.tif`, shape (n, n, n): background
+    1.0 and a marker region of exactly 5.0 -- the slab z in [n / 4, 3 n / 4), y in [n / 3, 2 n / 3), all x.  This is a GUESS at what
+    the unshipped file holds, made from what the reference does with it: noise of +-0.05 is added to every voxel, and `multiSpheres`
+    treats voxels equal to 5.0 as "take the sphere's index, not the maximum".  (After the noise step almost no voxel equals 5.0 any
+    more, so in `simulate` the marker mostly acts as a block of high index.)"""
+    ri = np.ones((n, n, n), dtype=np.float32)
+    ri[n // 4:(3 * n) // 4, n // 3:(2 * n) // 3, :] = np.float32(5.0)
+    return ri
+
+
 def view_angles(n_views: int, offset: int = 15) -> list[int]:
     """angleOffset + k * (360 / n_views) (SimulateMultiViewDataset.java:540-548,567-570)."""
     step = 360 // n_views
