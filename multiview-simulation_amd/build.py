@@ -9,8 +9,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmvsim.so")
-SOURCES = ["api.cpp", "api_view.cpp", "api_host.cpp", "api_sims.cpp", "comm.cpp", "kernels.hip", "extract.hip", "fftconv.hip", "fft_kernels.hip", "rotate_fft.hip", "stencil.hip", "phantom.hip", "beads.hip", "aberrations.hip", "procedural.hip", "sphere_walk.hip"]
-HEADERS = ["common.h", "api_internal.h", "host_pool.h", "jrandom.h", "extract_plan.h", "poisson_dev.h", "fft_dev.h", "rotate_rounds.h", "sphere_walk.h", "../../include/mvsim.h"]
+SOURCES = ["api.cpp", "api_view.cpp", "api_host.cpp", "api_sims.cpp", "comm.cpp", "kernels.hip", "extract.hip", "fftconv.hip", "fft_driver.hip", "fft_passes.hip", "zconv.hip", "rotate_fft.hip", "stencil.hip", "phantom.hip", "beads.hip", "aberrations.hip", "procedural.hip", "sphere_walk.hip"]
+HEADERS = ["common.h", "api_internal.h", "host_pool.h", "jrandom.h", "extract_plan.h", "poisson_dev.h", "fft_dev.h", "fft_host.h", "rotate_rounds.h", "sphere_walk.h", "../../include/mvsim.h"]
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 
@@ -72,7 +72,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(os.path.join(HERE, "build"), exist_ok=True)
     common = _common_flags()
     # per-object rebuild: an object is kept when it is newer than its source, every header and this recipe, and was built
-    # with the same flags (recorded beside it) -- fft_kernels.hip alone takes ~1.5 min
+    # with the same flags (recorded beside it) -- fft_passes.hip (every transform kernel for every length) alone takes ~4 min
+    # on one core and bounds a full build; fft_driver.hip and zconv.hip take seconds
     flags_id = " ".join(common)
     hdr_time = max(os.path.getmtime(os.path.normpath(os.path.join(CSRC, h))) for h in HEADERS)
     hdr_time = max(hdr_time, os.path.getmtime(os.path.abspath(__file__)))

@@ -252,9 +252,9 @@ struct mvsim_ctx {
     mvsim::DevBuf cfft_g1, cfft_g2;         // compact PSF intermediates [Kz][Ky][Hxp], [Kz][Py][Hxp]
     mvsim::Options opt;
     std::unordered_set<const void*> lds_attr_set;   // kernels whose dynamic-LDS limit has been raised on this device
-    std::map<std::string, void*> box_weights;   // early-sum weights (fft_kernels.hip: ensure_box_weights)
+    std::map<std::string, void*> box_weights;   // early-sum weights (fft_driver.hip: ensure_box_weights)
     mvsim::DevBuf partials_z;               // per-block sums of the z pass
-    std::map<int, void*> twiddles;          // 2*length + kind -> device twiddle table (fft_kernels.hip)
+    std::map<int, void*> twiddles;          // 2*length + kind -> device twiddle table (fft_driver.hip: ensure_twiddles)
     std::map<std::string, mvsim::FftPlan> plans;
     bool   fft_ready = false;
 
@@ -530,7 +530,7 @@ int fft_convolve(mvsim_ctx* ctx, const float* img_dev, const int64_t dim[3], con
                  const int64_t kdim[3], float* out_dev, ConvTail* tail);
 void fft_release(mvsim_ctx* ctx);
 void choose_padded(const int64_t dim[3], const int64_t kdim[3], int64_t P[3], const Options& opt);
-// hand-written LDS FFT path (fft_kernels.hip)
+// hand-written LDS FFT path (fft_driver.hip; its kernels: fft_passes.hip, zconv.hip)
 bool custom_fft_sizes(const int64_t dim[3], const int64_t kdim[3], int64_t P[3], const Options& opt);
 // orders a pending tail (extract + Poisson of the last view, on the tail stream) in front of whatever is enqueued on
 // ctx->stream next

@@ -1,4 +1,4 @@
-// Device-side building blocks of the hand-written FFT passes (fft_kernels.hip) shared with the fused
+// Device-side building blocks of the hand-written FFT passes (fft_passes.hip) shared with the fused
 // rotate + attenuate + x-transform kernel (rotate_fft.hip): complex helpers, small DFTs, the wave-private Stockham
 // passes in LDS, the plan / size table, and the index maps of the padded volume.
 #pragma once

@@ -2,7 +2,7 @@
 // round trip through HBM (SimulateMultiViewDataset.java:570-580 -- rotateAroundAxis, attenuate3d, and the first pass of
 // convolve's FFT).  The rotate+attenuate kernel (kernels.hip: k_rotate_attenuate_axis0_lds) already holds complete x rows
 // of the attenuated plane, one value per lane, while it walks y; pass A of the hand-written convolution
-// (fft_kernels.hip: k_fft_x_r2c) transforms exactly those rows.  Here a block -- all the x columns of one plane -- walks
+// (fft_passes.hip: k_fft_x_r2c) transforms exactly those rows.  Here a block -- all the x columns of one plane -- walks
 // y in batches of U = 8 rows: every lane blends, attenuates (same arithmetic, same order: `att`, and `rot`, stay
 // bit-identical and are still written when the caller asks for them) and drops its value into an LDS row with the
 // mirror halo of the padded row; after one barrier each wave owns a row end to end -- packed real FFT of M = Px/2

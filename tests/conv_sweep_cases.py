@@ -49,7 +49,7 @@ def lines_per_tile(L: int) -> int:
     return 16 if L <= 576 else 8
 
 
-NLZ = 16                                  # columns of a direct z pass tile (fft_kernels.hip)
+NLZ = 16                                  # columns of a direct z pass tile (fft_host.h)
 
 
 def hxp(px: int, py: int, pz: int, zdirect: bool) -> int:

@@ -513,6 +513,17 @@ def test_committed_pmc_traffic_belongs_to_this_build():
     assert rec["views_profiled"] >= 1 and rec["per_view_bytes"]["convolve"] > 0
 
 
+def test_build_recipe_lists_every_source_and_header():
+    """build.sources() drops a SOURCES entry that does not exist without a word, and a header missing from HEADERS leaves stale objects
+    behind and out of source_sha(): the recipe's two lists and the files of csrc/ have to agree."""
+    build = importlib.import_module("multiview-simulation_amd.build")
+    on_disk = os.listdir(build.CSRC)
+    assert sorted(f for f in on_disk if f.endswith((".hip", ".cpp"))) == sorted(set(build.SOURCES) & set(on_disk)), "a source of csrc/ is not in SOURCES"
+    assert sorted(f for f in on_disk if f.endswith(".h")) == sorted(set(build.HEADERS) & set(on_disk)), "a header of csrc/ is not in HEADERS"
+    missing = [f for f in build.SOURCES + build.HEADERS if not os.path.isfile(os.path.join(build.CSRC, f))]
+    assert not missing, f"listed in build.py but not there: {missing}"
+
+
 @pytest.mark.parametrize("nranks,root,count,pieces", [(2, 0, 1000, 8), (2, 1, 100003, 3), (3, 0, 100003, 8), (4, 2, 134217728, 8),
                                                         (8, 0, 134217728, 8), (8, 5, 1 << 20, 4), (8, 0, 100, 8), (5, 4, 17, 8), (8, 3, 4097, 1)])
 def test_pipelined_broadcast_plan_is_complete_and_matched(mvs, nranks, root, count, pieces):

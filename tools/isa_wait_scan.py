@@ -1,6 +1,6 @@
 """Which kernels wait for a global load the moment they have asked for it?
 
-    python tools/isa_wait_scan.py [source.hip ...]        (default: the three kernel files of the convolution / rotate / sampler path)
+    python tools/isa_wait_scan.py [source.hip ...]        (default: the kernel files of the convolution / rotate / sampler path)
 
 Compiles each file to gfx950 assembly with the product's flags (device only, nothing is linked or run: works without a GPU) and lists, per
 kernel, the `global_load` instructions that are followed at once by `s_waitcnt vmcnt(0)` -- a load whose data the wave sits and waits for
@@ -8,7 +8,7 @@ before it asks for anything else.  One such pair at the head of a tile's loads m
 loads are even under way.  Where it comes from in this code base: `v = 0; if (wanted) v = load(...)` becomes a branch
 whose merge of loaded and zero registers costs the compiler a register copy of the loaded value, hence the wait; a select instead of the
 branch is turned back into one (CodeGenPrepare sinks a load that only a select uses).  What holds: an unconditional load from a clamped
-address and an AND with a mask (fft_kernels.hip: zconv_keep4).  Dependent loads (an item fetched by a ticket, a table read behind a scalar
+address and an AND with a mask (zconv.hip: zconv_keep4).  Dependent loads (an item fetched by a ticket, a table read behind a scalar
 load) show up here as well and are what they are; the list is a place to look, not a verdict.
 """
 import os
@@ -52,7 +52,7 @@ def demangle(names):
 
 
 if __name__ == "__main__":
-    files = sys.argv[1:] or [os.path.join(CSRC, f) for f in ("fft_kernels.hip", "rotate_fft.hip", "kernels.hip", "extract.hip")]
+    files = sys.argv[1:] or [os.path.join(CSRC, f) for f in ("fft_passes.hip", "zconv.hip", "fft_driver.hip", "rotate_fft.hip", "kernels.hip", "extract.hip")]
     for f in files:
         loads, hits = scan(f)
         names = demangle(sorted(hits, key=lambda k: -hits[k]))

@@ -1,5 +1,5 @@
 """Where a block of the image's y passes (k_fft_lines FWD = pass B, INV = pass D) spends its time: shader-clock stamps written by an
-ATTRIBUTION build (python tools/build_variant.py stamps "-DMVSIM_DEV_ATTRIBUTION -DMVSIM_EXP_LINES_STAMPS" fft_kernels.hip), read back
+ATTRIBUTION build (python tools/build_variant.py stamps "-DMVSIM_DEV_ATTRIBUTION -DMVSIM_EXP_LINES_STAMPS" fft_passes.hip), read back
 after one view:
     cp multiview-simulation_amd/libmvsim_stamps.so multiview-simulation_amd/libmvsim.so   (on the GPU box: the copy there is scratch)
     python tools/lines_timeline.py 1024 1024 1024 31 31 31 1 [gt=phantom2x]

@@ -5,7 +5,7 @@
 //
 // Shapes:
 //   stream16       a wide coalesced stream, 16 B per lane, grid-stride (the shape MI355X_MICROARCH.md calibrated: counter = 1/2)
-//   tile<T>        pass B / D of csrc/fft_kernels.hip (k_fft_lines): grid (tiles, planes), a block of T threads loads the ROWS rows of
+//   tile<T>        pass B / D of csrc/fft_passes.hip (k_fft_lines): grid (tiles, planes), a block of T threads loads the ROWS rows of
 //                  one 16-column tile -- 8 lanes x 16 B = one 128-byte segment per row, rows `pitch` bytes apart, all loads requested
 //                  before the first wait --, drops them into LDS (dynamic LDS sized like the pass: it sets the blocks per CU) and leaves.
 //                  512^3: T = 512, rows 512, pitch 288 x 8 B, plane 560 rows, 18 tiles, 75 KB LDS (two blocks per CU)
