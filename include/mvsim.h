@@ -401,6 +401,36 @@ int mvsim_normalize_weights_dev(mvsim_ctx* ctx, float* const* weights, int n_vie
 /* Host buffers: weights[v] are host pointers of n floats each. */
 int mvsim_normalize_weights(mvsim_ctx* ctx, float* const* weights, int n_views, int64_t n, float osem);
 
+/* ---- extractSlices over Intervals of volumes that stay on the device (SimulateTileStitching.java:131-189) ---------------
+ * Views.zeroMin(Views.interval(con, min, max)) run through extractSlices: output voxel (x, y, k) of the contiguous tile
+ * tx x ty x mvsim_extract_nz(tz, inc), t_d = max_d - min_d + 1, is f(in[(min_x + x) + Nx ((min_y + y) + Ny (min_z + k inc))]).
+ * Its RNG counter is its index in the ZERO-MIN tile, x + tx (y + ty k inc), keyed by (seed, stream): bit for bit what
+ * mvsim_extract_slices returns for the cropped tile (the interval is treated as zero-min). */
+typedef struct mvsim_interval_job {
+    const float* in;          /* DEVICE: the volume the interval is cut from (several jobs may name the same one) */
+    int64_t  dim[3];          /* its size */
+    int64_t  min[3], max[3];  /* inclusive corners, as an ImgLib2 Interval */
+    int32_t  inc;  float snr; /* as mvsim_extract_slices: snr < 0 => copy */
+    uint64_t seed; uint32_t stream;
+} mvsim_interval_job;
+/* out_dim = {tx, ty, mvsim_extract_nz(tz, inc)}.  Host only, no context; MVSIM_EINVAL as the extract calls below. */
+int mvsim_interval_out_dim(const mvsim_interval_job* job, int64_t out_dim[3]);
+/* 1 <= n <= MVSIM_MAX_VIEWS jobs in one call; out_dev: HOST array of n DEVICE pointers.  Asynchronous on the context's stream.
+ * Jobs of equal tile size, inc and snr share their launches (one per sampler stage, blockIdx.y = job), the others follow one
+ * another; the results do not depend on it.  MVSIM_EINVAL: null pointer, inc < 1, min_d > max_d, an interval that leaves its
+ * volume, outputs that overlap each other or any job's volume, n out of range.  mvsim_get_extract_path reports kernel 5 for
+ * an interval launch (the last one of the call; the fifth field: its jobs). */
+int mvsim_extract_intervals_dev(mvsim_ctx* ctx, const mvsim_interval_job* jobs, int n, float* const* out_dev);
+/* The same with outputs on the HOST (the volumes stay DEVICE pointers); synchronous.  Sampled outputs cross PCIe as the
+ * acquisitions of the host-buffer views do: uint16 counts from 2^20 values up, automatic float32 fallback per output
+ * (option "acq_transfer", mvsim_get_transfer_stats). */
+int mvsim_extract_intervals(mvsim_ctx* ctx, const mvsim_interval_job* jobs, int n, float* const* out_host);
+/* The two tiles of SimulateTileStitching (:119-121, :214-234), quirks included: overlap_d = (int)Math.round(dim_d ratio_d / 2);
+ * tile 0 = [0, dim_d / 2 + overlap_d], tile 1 = [dim_0 / 2 - overlap_d, dim_d - 1] -- dimension 0 in every dimension, as the
+ * reference has it.  Host only; the interval is not validated (a ratio of 1 leaves the volume: the extract calls refuse it). */
+int mvsim_tile_interval(const int64_t dim[3], const double overlap_ratio[3], int tile,
+                        int64_t min[3], int64_t max[3], int64_t overlap[3]);
+
 /* ---- fused per-view pipeline: loop body SMVD:570-585 -------------------------------------- */
 typedef struct mvsim_view_params {
     int32_t  axis;            /* 0 (SMVD:570)                                  */
@@ -547,7 +577,8 @@ int mvsim_stencil_geometry(const int64_t kdim[3], int64_t geometry[5]);
  * group-by-group form; 1 if queue segments can refuse voxels; blocks; items per segment (0: no queue)}.  Host only, no context. */
 int mvsim_extract_path(const int64_t dim[3], int inc, int index_inc, uint64_t index_offset, int aligned16, int queue_share, int64_t path[4]);
 /* The sampler form of the last extract + Poisson this context enqueued: {kernel as mvsim_extract_path, or 4 for the fused tail of the
- * convolution; 1 if queue segments can refuse voxels; blocks; items per segment; views in the launch (> 1: the stacked-view tables)}.
+ * convolution, or 5 for an interval launch (mvsim_extract_intervals*: items per segment 0 = one voxel per lane, else the two-launch
+ * form); 1 if queue segments can refuse voxels; blocks; items per segment; views or jobs in the launch (> 1: the per-view tables)}.
  * Recorded on the host when the work is enqueued; kernel -1 before the first. */
 int mvsim_get_extract_path(mvsim_ctx* ctx, int64_t path[5]);
 /* {blocks, items per segment} of the fused tail (the convolution's last pass adjusts, extracts and samples) for a noisy view of this

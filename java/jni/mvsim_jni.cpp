@@ -555,6 +555,72 @@ JNIEXPORT void JNICALL JNI_FN(downSample2x)(JNIEnv* env, jclass, jlong h, jobjec
     throw_for(env, mvsim_downsample2x(ctx_of(h), pi, d.d, po));
 }
 
+// ---- volumes that stay on the device, and extractSlices over their intervals (mvsim_dev_alloc / _free / mvsim_upload / mvsim_extract_intervals)
+JNIEXPORT jlong JNICALL JNI_FN(devAlloc)(JNIEnv* env, jclass, jlong h, jlong bytes)
+{
+    if (bytes < 1) { throw_new(env, "java/lang/IllegalArgumentException", "devAlloc: bytes >= 1 expected"); return 0; }
+    void* p = nullptr;
+    throw_for(env, mvsim_dev_alloc(ctx_of(h), static_cast<size_t>(bytes), &p));
+    return static_cast<jlong>(reinterpret_cast<intptr_t>(p));
+}
+
+JNIEXPORT void JNICALL JNI_FN(devFree)(JNIEnv* env, jclass, jlong h, jlong dptr)
+{
+    if (dptr != 0) throw_for(env, mvsim_dev_free(ctx_of(h), reinterpret_cast<void*>(static_cast<intptr_t>(dptr))));
+}
+
+JNIEXPORT void JNICALL JNI_FN(uploadFloats)(JNIEnv* env, jclass, jlong h, jlong dptr, jobject src, jlong n)
+{
+    if (dptr == 0 || n < 1) { throw_new(env, "java/lang/IllegalArgumentException", "uploadFloats: a device pointer and n >= 1 expected"); return; }
+    float* p = fptr(env, src, n, "uploadFloats: source buffer smaller than n");
+    if (!p) return;
+    throw_for(env, mvsim_upload(ctx_of(h), reinterpret_cast<void*>(static_cast<intptr_t>(dptr)), p, static_cast<size_t>(n) * sizeof(float)));
+}
+
+// geometry: 10 longs per job {volume (device pointer), Nx, Ny, Nz, min x, y, z, max x, y, z}; inc, snr, seed, stream: one entry per job;
+// out: one direct FloatBuffer per job holding the tile, tx * ty * mvsim_extract_nz(tz, inc) floats
+JNIEXPORT void JNICALL JNI_FN(extractIntervals)(JNIEnv* env, jclass, jlong h, jlongArray geometry, jintArray inc, jfloatArray snr, jlongArray seed,
+                                                jintArray stream, jobjectArray out)
+{
+    if (!geometry || !inc || !snr || !seed || !stream || !out) { throw_new(env, "java/lang/IllegalArgumentException", "extractIntervals: null array"); return; }
+    const jsize n = env->GetArrayLength(out);
+    if (n < 1 || n > MVSIM_MAX_VIEWS) { throw_new(env, "java/lang/IllegalArgumentException", "extractIntervals: 1..32 jobs"); return; }
+    if (env->GetArrayLength(geometry) != 10 * n || env->GetArrayLength(inc) != n || env->GetArrayLength(snr) != n || env->GetArrayLength(seed) != n ||
+        env->GetArrayLength(stream) != n) {
+        throw_new(env, "java/lang/IllegalArgumentException", "extractIntervals: 10 geometry entries and one inc, snr, seed and stream per output expected");
+        return;
+    }
+    jlong g[10 * MVSIM_MAX_VIEWS], sd[MVSIM_MAX_VIEWS];
+    jint ic[MVSIM_MAX_VIEWS], st[MVSIM_MAX_VIEWS];
+    jfloat sn[MVSIM_MAX_VIEWS];
+    env->GetLongArrayRegion(geometry, 0, 10 * n, g);
+    if (env->ExceptionCheck()) return;
+    env->GetIntArrayRegion(inc, 0, n, ic);
+    if (env->ExceptionCheck()) return;
+    env->GetFloatArrayRegion(snr, 0, n, sn);
+    if (env->ExceptionCheck()) return;
+    env->GetLongArrayRegion(seed, 0, n, sd);
+    if (env->ExceptionCheck()) return;
+    env->GetIntArrayRegion(stream, 0, n, st);
+    if (env->ExceptionCheck()) return;
+    mvsim_interval_job jobs[MVSIM_MAX_VIEWS];
+    float* ptr[MVSIM_MAX_VIEWS];
+    for (jsize j = 0; j < n; ++j) {
+        mvsim_interval_job& job = jobs[j];
+        const jlong* q = g + 10 * j;
+        job.in = reinterpret_cast<const float*>(static_cast<intptr_t>(q[0]));
+        for (int d = 0; d < 3; ++d) { job.dim[d] = q[1 + d]; job.min[d] = q[4 + d]; job.max[d] = q[7 + d]; }
+        job.inc = ic[j]; job.snr = sn[j]; job.seed = static_cast<uint64_t>(sd[j]); job.stream = static_cast<uint32_t>(st[j]);
+        int64_t od[3];
+        if (mvsim_interval_out_dim(&job, od) != MVSIM_OK) { throw_for(env, MVSIM_EINVAL); return; }      // host only: no pointer is touched
+        jobject b = env->GetObjectArrayElement(out, j);
+        if (env->ExceptionCheck()) return;
+        ptr[j] = fptr(env, b, od[0] * od[1] * od[2], "extractIntervals: output buffer smaller than the tile");
+        if (!ptr[j]) return;
+    }
+    throw_for(env, mvsim_extract_intervals(ctx_of(h), jobs, (int)n, ptr));
+}
+
 JNIEXPORT void JNICALL JNI_FN(normalizeWeights)(JNIEnv* env, jclass, jlong h, jobjectArray weights, jlong n, jfloat osem)
 {
     if (!weights) { throw_new(env, "java/lang/IllegalArgumentException", "normalizeWeights: null list"); return; }

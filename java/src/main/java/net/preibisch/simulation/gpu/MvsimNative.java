@@ -77,6 +77,19 @@ final class MvsimNative
 	/** downSample2x (:394-424): out has dim/2 - 1 samples per dimension. */
 	static native void downSample2x( long ctx, FloatBuffer in, long[] dim, FloatBuffer out );
 
+	// ---- volumes that stay on the device (SimulateTileStitchingGPU) ----
+	/** mvsim_dev_alloc: a device pointer as a long; devFree (mvsim_dev_free) releases it, 0 is ignored. */
+	static native long devAlloc( long ctx, long bytes );
+	static native void devFree( long ctx, long dptr );
+	/** mvsim_upload: n floats of a direct buffer to the device pointer; returns when src may be reused. */
+	static native void uploadFloats( long ctx, long dptr, FloatBuffer src, long n );
+	/**
+	 * mvsim_extract_intervals: extractSlices over intervals of DEVICE volumes, all jobs in one call.  geometry holds 10 longs per job
+	 * {volume (device pointer), Nx, Ny, Nz, min x, y, z, max x, y, z} (inclusive corners); inc, snr, seed and stream one entry per job;
+	 * out[j] receives the zero-min tile, tx * ty * ((tz - 1) / inc + 1) floats.  The shim checks every array length and buffer capacity first.
+	 */
+	static native void extractIntervals( long ctx, long[] geometry, int[] inc, float[] snr, long[] seed, int[] stream, FloatBuffer[] out );
+
 	/** Cross-view weight normalisation (:615-640), in place on every buffer. */
 	static native void normalizeWeights( long ctx, FloatBuffer[] weights, long n, float osem );
 

@@ -24,7 +24,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import MvsimError, MvsimNoDeviceError, Sphere, Timings, ViewOutputs, ViewParams  # noqa: F401
+from ._lib import IntervalJob, MvsimError, MvsimNoDeviceError, Sphere, Timings, ViewOutputs, ViewParams  # noqa: F401
 from .aberrations import ContextAberrations
 from .phantoms import ContextPhantoms
 
@@ -414,6 +414,35 @@ class Context(ContextAberrations, ContextPhantoms):
             if out_d:
                 self.dev_free(out_d)
 
+    def simulate_phantom_dev(self, size: int = 289, scale: int = 2, half_pixel_offset: bool = False, rnd: "JavaRandom | None" = None):
+        """:meth:`simulate_phantom` with the result left on the device: (device pointer, (Nx, Ny, Nz)); the caller frees it."""
+        if rnd is None:
+            rnd = SimulateMultiViewDataset.rnd
+        if scale == 2:
+            size += 1
+        n = size * scale
+        dim = (C.c_int64 * 3)(n, n, n)
+        canvas = self.dev_alloc(n ** 3 * 4)
+        try:
+            _lib.check(self._L.mvsim_dev_memset(self._h, canvas, 0, n ** 3 * 4))
+            st = C.c_uint64(rnd._s)
+            _lib.check(self._L.mvsim_draw_spheres_dev(self._h, canvas, dim, 0.0, 1.0, int(scale), int(bool(half_pixel_offset)), C.byref(st), None))
+            rnd._s = int(st.value)
+            if scale != 2:
+                done, canvas = canvas, 0
+                return done, (n, n, n)
+            o = n // 2 - 1
+            out_d = self.dev_alloc(o ** 3 * 4)
+            try:
+                _lib.check(self._L.mvsim_downsample2x_dev(self._h, canvas, dim, out_d))
+            except Exception:
+                self.dev_free(out_d)
+                raise
+            return out_d, (o, o, o)
+        finally:
+            if canvas:
+                self.dev_free(canvas)
+
     # -- the phantom of the refraction simulator (SimulateMultiViewAberrations.java:408-586)
     def ri_noise(self, ri: np.ndarray, rnd: "JavaRandom") -> None:
         """The noise on the refractive-index volume (:425-426), in place on a contiguous float32 array: voxel i, x fastest, becomes
@@ -780,6 +809,47 @@ class Context(ContextAberrations, ContextPhantoms):
         _lib.check(self._L.mvsim_extract_slices_dev(self._h, C.c_void_p(in_dptr), (C.c_int64 * 3)(*dim_xyz), inc, snr,
                                                     seed & 0xFFFFFFFFFFFFFFFF, stream, C.c_void_p(out_dptr)))
 
+    # -- extractSlices over intervals of device volumes (Views.zeroMin(Views.interval(...)), SimulateTileStitching.java:131-189)
+    @staticmethod
+    def _interval_jobs(jobs):
+        arr = (IntervalJob * max(1, len(jobs)))(*jobs)
+        shapes = []
+        od = (C.c_int64 * 3)()
+        for j in jobs:
+            _lib.check(_lib.load().mvsim_interval_out_dim(C.byref(j), od))
+            shapes.append((int(od[2]), int(od[1]), int(od[0])))
+        return arr, shapes
+
+    def extract_intervals_dev(self, jobs, out_dptrs) -> None:
+        """mvsim_extract_intervals_dev: ``jobs`` from :func:`interval_job`, one device pointer per job; asynchronous on the stream."""
+        if len(out_dptrs) != len(jobs):
+            raise ValueError("extract_intervals_dev: one output pointer per job")
+        arr = (IntervalJob * max(1, len(jobs)))(*jobs)
+        outs = (C.c_void_p * max(1, len(jobs)))(*[int(p) for p in out_dptrs])
+        _lib.check(self._L.mvsim_extract_intervals_dev(self._h, arr, len(jobs), outs))
+
+    def extract_intervals(self, jobs, out=None) -> list:
+        """mvsim_extract_intervals: the tiles as (Nz', Ny', Nx') float32 arrays -- volumes on the device, tiles on the host.  ``out``: the
+        arrays of an earlier call of the same shapes, written in place and returned (a caller that asks for tile after tile: fresh
+        arrays cost a page fault per 4 KiB, several times the call itself for 32 tiles of 174^3)."""
+        arr, shapes = self._interval_jobs(jobs)
+        if out is None:
+            out = [np.empty(s, dtype=np.float32) for s in shapes]
+        else:
+            out = list(out)
+            if len(out) != len(shapes) or any(not isinstance(a, np.ndarray) or a.shape != s or a.dtype != np.float32 or not a.flags.c_contiguous
+                                              or not a.flags.writeable for a, s in zip(out, shapes)):
+                raise ValueError("extract_intervals: out must hold one writable C-contiguous float32 array of the tile's shape per job")
+        outs = (C.c_void_p * max(1, len(jobs)))(*[a.ctypes.data for a in out])
+        _lib.check(self._L.mvsim_extract_intervals(self._h, arr, len(jobs), outs))
+        return out
+
+    def extract_path(self):
+        """mvsim_get_extract_path: {kernel (5: an interval launch), segments can refuse, blocks, items per segment, views / jobs}."""
+        p = (C.c_int64 * 5)()
+        _lib.check(self._L.mvsim_get_extract_path(self._h, p))
+        return [int(v) for v in p]
+
     # -- timings
     def enable_timing(self, enable: bool = True) -> None:
         _lib.check(self._L.mvsim_enable_timing(self._h, 1 if enable else 0))
@@ -938,6 +1008,21 @@ def walk_large_sphere(shape_zyx, minValue: float, maxValue: float, scale: int, h
     return out
 
 
+def interval_job(in_dptr: int, dim_xyz, min_xyz, max_xyz, inc: int, snr: float, seed: int = 0, stream: int = 0) -> IntervalJob:
+    """One mvsim_interval_job: extractSlices (every ``inc``-th plane, Poisson noise iff ``snr`` >= 0) over the inclusive interval
+    [min, max] of the DEVICE volume at ``in_dptr``; all triples x first."""
+    return IntervalJob(C.c_void_p(int(in_dptr)), (C.c_int64 * 3)(*[int(v) for v in dim_xyz]), (C.c_int64 * 3)(*[int(v) for v in min_xyz]),
+                       (C.c_int64 * 3)(*[int(v) for v in max_xyz]), int(inc), float(snr), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream))
+
+
+def tile_interval(dim_xyz, overlap_ratio, tile: int):
+    """mvsim_tile_interval: (min, max, overlap) of tile 0 / 1 of SimulateTileStitching (:119-121, :214-234), x first, quirks included."""
+    mn, mx, ov = (C.c_int64 * 3)(), (C.c_int64 * 3)(), (C.c_int64 * 3)()
+    _lib.check(_lib.load().mvsim_tile_interval((C.c_int64 * 3)(*[int(v) for v in dim_xyz]), (C.c_double * 3)(*[float(v) for v in overlap_ratio]),
+                                               int(tile), mn, mx, ov))
+    return list(mn), list(mx), list(ov)
+
+
 _default_ctx: Context | None = None
 
 
@@ -1086,12 +1171,19 @@ class SimulateTileStitching:
     dir = "src/main/resources/"
 
     def __init__(self, rnd=None, halfPixelOffset: bool = False, overlapRatio=(0.2, 0.2, 0.2), service=None,
-                 psf: np.ndarray | None = None):
+                 psf: np.ndarray | None = None, resident: bool = False):
+        """``resident``: both convolved phantoms are built and kept in HBM (no intermediate crosses PCIe) and every pair is ONE
+        mvsim_extract_intervals call with two jobs -- the same tiles, bit for bit; ``con`` / ``conHalfPixel`` are downloaded when first
+        read.  Such an object owns device memory: ``close()`` it, or use it as a context manager."""
         self.rnd = rnd if rnd is not None else JavaRandom(464232194)          # :66-69
         self.service = service
         self.lightsheetSpacing = 3                                              # :48
         self.attenuation = float(np.float32(0.01))                              # :49, a Java float widened to double
         self.psf = psf if psf is not None else Tools.open(self.dir + "Angle0.tif", True)
+        self.resident = bool(resident)
+        self._closed = False
+        self._host = {}                                                         # "con" / "conHalfPixel" -> the host array
+        self._dev = {}                                                          # ... -> the device pointer (resident)
         self.init(overlapRatio, halfPixelOffset)
 
     def init(self, overlapRatio, halfPixelOffset: bool) -> None:
@@ -1107,19 +1199,82 @@ class SimulateTileStitching:
             Tools.adjustImage(con, S.minValue, S.avgIntensity)
             return con
 
-        self.con = rendered(False)
-        self.conHalfPixel = rendered(True)
-        nz, ny, nx = self.con.shape
-        dims = (nx, ny, nz)
+        def rendered_dev(half: bool) -> int:
+            # the same operators in the same order on device buffers: only the PSF crosses PCIe
+            ctx = default_context()
+            gt, dim = ctx.simulate_phantom_dev(289, 2, half, JavaRandom(seed))
+            n = dim[0] * dim[1] * dim[2]
+            att = con = 0
+            try:
+                att = ctx.dev_alloc(4 * n)
+                ctx.attenuate3d_dev(gt, dim, self.attenuation, att)
+                con = ctx.dev_alloc(4 * n)
+                ctx.convolve_dev(att, dim, self.psf, con)
+                ctx.adjust_image_dev(con, n, S.minValue, S.avgIntensity)
+                self._dims = dim
+                done, con = con, 0
+                return done
+            finally:
+                for p in (gt, att, con):
+                    if p:
+                        ctx.dev_free(p)
+
+        self._host = {}
+        if self.resident:
+            self._release()
+            self._dev["con"] = rendered_dev(False)
+            self._dev["conHalfPixel"] = rendered_dev(True)
+        else:
+            self.con = rendered(False)
+            self.conHalfPixel = rendered(True)
+            nz, ny, nx = self.con.shape
+            self._dims = (nx, ny, nz)
+        dims = self._dims
         self.overlap = [int(np.floor(dims[d] * overlapRatio[d] / 2 + 0.5)) for d in range(3)]     # Math.round
         self.min = [0, 0, 0]
         self.max = [0, 0, 0]
 
+    def _volume(self, name: str) -> np.ndarray:
+        if name not in self._host:
+            self._check_open()
+            nx, ny, nz = self._dims
+            self._host[name] = default_context().download(self._dev[name], (nz, ny, nx))
+        return self._host[name]
+
+    con = property(lambda self: self._volume("con"), lambda self, v: self._host.__setitem__("con", v))
+    conHalfPixel = property(lambda self: self._volume("conHalfPixel"), lambda self, v: self._host.__setitem__("conHalfPixel", v))
+
+    def _check_open(self) -> None:
+        if self._closed:
+            raise RuntimeError("SimulateTileStitching: closed")
+
+    def _release(self) -> None:
+        for p in self._dev.values():
+            default_context().dev_free(p)
+        self._dev = {}
+
+    def close(self) -> None:
+        """Frees the resident volumes; the object serves no further pair."""
+        if not self._closed:
+            self._closed = True
+            self._release()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
     def getInterval(self, tile: int):
         """:226-246 -- inclusive (min, max) per dimension, x first.  Tile 1 starts at dimension(0)/2 - overlap in
         every dimension, as in the reference."""
-        nz, ny, nx = self.con.shape
-        dims = (nx, ny, nz)
+        dims = self._dims
         lo, hi = [0, 0, 0], [d - 1 for d in dims]
         if tile == 0:
             hi = [dims[d] // 2 + self.overlap[d] for d in range(3)]
@@ -1133,6 +1288,9 @@ class SimulateTileStitching:
 
     def getNextPair(self, snr: float):
         """:133-198 -- (left, right) tiles; each draws its extractSlices seed from ``new Random(seedN)``."""
+        self._check_open()
+        if self.resident:
+            return self.getNextPairs([snr])[0]
         S = SimulateMultiViewDataset
         seed0 = self.rnd.nextInt()
         seed1 = self.rnd.nextInt()
@@ -1140,6 +1298,29 @@ class SimulateTileStitching:
         src1 = self.conHalfPixel if self.halfPixelOffset else self.con
         split1 = S.extractSlices(self._tile(src1, 1), self.lightsheetSpacing, snr, JavaRandom(seed1))
         return split0, split1
+
+    def getNextPairs(self, snrs, out=None) -> list:
+        """The pairs consecutive ``getNextPair(snr)`` calls would return, seeds drawn in the same order; resident: every tile of up to 16
+        pairs in ONE mvsim_extract_intervals call (MVSIM_MAX_VIEWS jobs).  ``out`` (resident): the list an earlier call returned for as
+        many pairs -- its arrays are overwritten and returned instead of fresh ones."""
+        self._check_open()
+        if not self.resident:
+            return [self.getNextPair(snr) for snr in snrs]
+        if out is not None and len(out) != len(snrs):
+            raise ValueError("getNextPairs: out must hold one (left, right) pair per snr")
+        flat = None if out is None else [a for pair in out for a in pair]
+        jobs = []
+        for snr in snrs:
+            seeds = [self.rnd.nextInt(), self.rnd.nextInt()]
+            for tile in (0, 1):
+                lo, hi = self.getInterval(tile)
+                src = self._dev["conHalfPixel" if tile == 1 and self.halfPixelOffset else "con"]
+                seed = _seed_from(JavaRandom(seeds[tile])) if snr >= 0.0 else 0        # as extractSlices draws it
+                jobs.append(interval_job(src, self._dims, lo, hi, self.lightsheetSpacing, snr, seed))
+        tiles = []
+        for first in range(0, len(jobs), 32):
+            tiles += default_context().extract_intervals(jobs[first:first + 32], None if flat is None else flat[first:first + 32])
+        return [(tiles[2 * i], tiles[2 * i + 1]) for i in range(len(snrs))]
 
     def getCorrectTranslation(self):
         """:200-224 -- shift of the right tile relative to the left one, (x, y, z) with z in acquired planes."""

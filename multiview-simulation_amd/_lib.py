@@ -71,6 +71,12 @@ class Density(C.Structure):
     _fields_ = [("kind", C.c_int32), ("perlin", C.POINTER(Perlin)), ("spheres", C.POINTER(SphereSet))]
 
 
+class IntervalJob(C.Structure):
+    """mvsim_interval_job: extractSlices over the interval [min, max] (inclusive, x first) of a DEVICE volume."""
+    _fields_ = [("in_", C.c_void_p), ("dim", C.c_int64 * 3), ("min", C.c_int64 * 3), ("max", C.c_int64 * 3), ("inc", C.c_int32),
+                ("snr", C.c_float), ("seed", C.c_uint64), ("stream", C.c_uint32)]
+
+
 class Timings(C.Structure):
     _fields_ = [(n, C.c_float) for n in
                 ("rotate_ms", "attenuate_ms", "psf_ms", "convolve_ms", "adjust_ms", "extract_ms", "total_ms",
@@ -122,6 +128,10 @@ SIGNATURES = {
     "mvsim_adjust_image_dev": (C.c_int, [_vp, _vp, C.c_int64, C.c_float, C.c_float, C.POINTER(C.c_double)]),
     "mvsim_extract_slices_dev": (C.c_int, [_vp, _vp, _i64p, C.c_int, C.c_float, C.c_uint64, C.c_uint32, _vp]),
     "mvsim_make_isotropic_dev": (C.c_int, [_vp, _vp, _i64p, C.c_int, _vp]),
+    "mvsim_interval_out_dim": (C.c_int, [C.POINTER(IntervalJob), _i64p]),
+    "mvsim_extract_intervals_dev": (C.c_int, [_vp, C.POINTER(IntervalJob), C.c_int, C.POINTER(_vp)]),
+    "mvsim_extract_intervals": (C.c_int, [_vp, C.POINTER(IntervalJob), C.c_int, C.POINTER(_vp)]),
+    "mvsim_tile_interval": (C.c_int, [_i64p, _dp, C.c_int, _i64p, _i64p, _i64p]),
     "mvsim_draw_spheres": (C.c_int, [_vp, _vp, _i64p, C.c_double, C.c_double, C.c_int, C.c_int,
                                      C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
     "mvsim_draw_spheres_dev": (C.c_int, [_vp, _vp, _i64p, C.c_double, C.c_double, C.c_int, C.c_int,

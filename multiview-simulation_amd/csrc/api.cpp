@@ -287,6 +287,88 @@ int extract_stage(mvsim_ctx* ctx, const ExtractGeom& g, ExtractOps& ops)
     return extract_stage_run(ctx, pl, ops);
 }
 
+// ---- extractSlices over intervals of device volumes (interval_plan.h, extract_interval.hip) ----------------------------------------
+int interval_jobs_check(const mvsim_interval_job* jobs, int n, std::vector<IntervalGeom>* geoms)
+{
+    MVSIM_CHECK_ARG(jobs != nullptr, "interval jobs: null pointer");
+    MVSIM_CHECK_ARG(n >= 1 && n <= MVSIM_MAX_VIEWS, "interval jobs: n must be in [1, MVSIM_MAX_VIEWS]");
+    geoms->resize((size_t)n);
+    for (int j = 0; j < n; ++j) {
+        if (!jobs[j].in) { set_error("invalid argument: interval job %d: null volume", j); return MVSIM_EINVAL; }
+        if (const char* why = interval_geom(jobs[j].dim, jobs[j].min, jobs[j].max, jobs[j].inc, &(*geoms)[(size_t)j])) {
+            set_error("invalid argument: interval job %d: %s", j, why);
+            return MVSIM_EINVAL;
+        }
+    }
+    return MVSIM_OK;
+}
+
+static IntervalKey interval_key(const mvsim_interval_job& job, const IntervalGeom& g)
+{
+    IntervalKey k{{g.tile[0], g.tile[1], g.tile[2]}, g.inc, job.snr >= 0.0f, 0u};
+    std::memcpy(&k.snr_bits, &job.snr, sizeof(k.snr_bits));
+    return k;
+}
+
+// Jobs of one IntervalKey share their launches, the groups follow one another on the stream in the order of their first jobs.  One table
+// upload and one queue workspace for the call: a group's queue regions are free again when the next group's phase 1 starts (stream order).
+int extract_intervals_enqueue(mvsim_ctx* ctx, const mvsim_interval_job* jobs, const std::vector<IntervalGeom>& geoms, float* const* out_dev)
+{
+    const int n = (int)geoms.size();
+    QueueMode qm;
+    MVSIM_TRY(queue_mode_next(ctx, &qm));
+    struct Group { IntervalPlan pl; std::vector<int> members; bool noise; double mul; };
+    std::vector<Group> groups;
+    std::vector<IntervalKey> keys;
+    size_t queue_bytes = 0;
+    for (int j = 0; j < n; ++j) {
+        const IntervalKey key = interval_key(jobs[j], geoms[(size_t)j]);
+        size_t gi = 0;
+        while (gi < keys.size() && !(keys[gi] == key)) ++gi;
+        if (gi == keys.size()) {
+            keys.push_back(key);
+            groups.push_back(Group{interval_plan(geoms[(size_t)j], key.noise, qm), {}, key.noise, mvsim_poisson_mul((double)jobs[j].snr)});
+        }
+        groups[gi].members.push_back(j);
+    }
+    for (const Group& g : groups)
+        if (g.noise) queue_bytes = std::max(queue_bytes, g.pl.xp.layout.view_stride() * g.members.size());
+    if (queue_bytes) MVSIM_TRY(ctx->pqueue.reserve(queue_bytes));
+    const size_t off_r = ((size_t)n * sizeof(IntervalView) + 255) & ~(size_t)255, up_bytes = off_r + (size_t)n * sizeof(ExtractView);
+    MVSIM_TRY(ctx->interval_tab.reserve(up_bytes));
+    int slot = 0;
+    MVSIM_TRY(ctx->pinned.acquire(up_bytes, &slot));
+    char* hp = reinterpret_cast<char*>(ctx->pinned.p[slot]);
+    char* dp = ctx->interval_tab.as<char>();
+    IntervalView* vtab = reinterpret_cast<IntervalView*>(hp);
+    ExtractView* rtab = reinterpret_cast<ExtractView*>(hp + off_r);
+    int row = 0;
+    for (const Group& g : groups)
+        for (size_t m = 0; m < g.members.size(); ++m, ++row) {
+            const int j = g.members[m];
+            const IntervalGeom& ig = geoms[(size_t)j];
+            const QueueLayout::Region q = g.pl.xp.layout.region(g.noise ? ctx->pqueue.p : nullptr, (int)m);
+            vtab[row] = IntervalView{jobs[j].in + ig.in_offset, out_dev[j], q.items, q.counts, (uint32_t)jobs[j].seed, (uint32_t)(jobs[j].seed >> 32),
+                                     jobs[j].stream, 0u, ig.row_pitch, ig.plane_pitch};
+            rtab[row] = ExtractView{nullptr, out_dev[j], nullptr, q.items, q.counts, (uint32_t)jobs[j].seed, (uint32_t)(jobs[j].seed >> 32), jobs[j].stream, 0u};
+        }
+    MVSIM_HIP(hipMemcpyAsync(dp, hp, up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    MVSIM_HIP(hipEventRecord(ctx->pinned.ev[slot], ctx->stream));
+    ctx->pinned.busy[slot] = true;
+    ev_begin(ctx, ST_EXTRACT);
+    row = 0;
+    for (const Group& g : groups) {
+        const int m = (int)g.members.size();
+        MVSIM_TRY(launch_extract_interval(ctx->stream, g.pl, reinterpret_cast<const IntervalView*>(dp) + row, reinterpret_cast<const ExtractView*>(dp + off_r) + row,
+                                          m, g.noise, g.mul));
+        const int64_t path[5] = {EXTRACT_K_INTERVAL, g.pl.xp.checked ? 1 : 0, g.pl.xp.blocks, g.pl.xp.segcap, m};
+        std::memcpy(ctx->extract_path, path, sizeof(path));
+        row += m;
+    }
+    ev_end(ctx, ST_EXTRACT);
+    return MVSIM_OK;
+}
+
 // Tools.normImage on the host (Tools.java:112-132), in place (Q5): double sum, (float)(v / sum).
 void psf_normalise_host(float* psf_host, int64_t n)
 {
@@ -680,6 +762,44 @@ int mvsim_extract_slices_dev(mvsim_ctx* ctx, const float* in, const int64_t dim[
     ops.noise = snr >= 0.0f;   // SMVD:211
     ops.mul = mvsim_poisson_mul((double)snr); ops.seed = seed; ops.stream = stream;
     return extract_stage(ctx, ExtractGeom::strided(dim, inc), ops);
+}
+
+int mvsim_interval_out_dim(const mvsim_interval_job* job, int64_t out_dim[3])
+{
+    if (!job || !out_dim) { set_error("invalid argument: null pointer"); return MVSIM_EINVAL; }
+    IntervalGeom g;
+    if (const char* why = interval_geom(job->dim, job->min, job->max, job->inc, &g)) { set_error("invalid argument: %s", why); return MVSIM_EINVAL; }
+    out_dim[0] = g.tile[0]; out_dim[1] = g.tile[1]; out_dim[2] = g.nzo();
+    return MVSIM_OK;
+}
+
+int mvsim_tile_interval(const int64_t dim[3], const double overlap_ratio[3], int tile, int64_t min[3], int64_t max[3], int64_t overlap[3])
+{
+    if (!dim || !overlap_ratio || !min || !max || !overlap) { set_error("invalid argument: null pointer"); return MVSIM_EINVAL; }
+    MVSIM_TRY(check_dim(dim));
+    MVSIM_CHECK_ARG(tile == 0 || tile == 1, "tile must be 0 or 1");
+    tile_interval(dim, overlap_ratio, tile, min, max, overlap);
+    return MVSIM_OK;
+}
+
+int mvsim_extract_intervals_dev(mvsim_ctx* ctx, const mvsim_interval_job* jobs, int n, float* const* out_dev)
+{
+    MVSIM_TRY(set_device(ctx));
+    MVSIM_CHECK_ARG(out_dev != nullptr, "interval jobs: null pointer");
+    std::vector<IntervalGeom> geoms;
+    MVSIM_TRY(interval_jobs_check(jobs, n, &geoms));
+    // an output must not meet another output or any job's volume: the jobs of a launch run side by side
+    for (int j = 0; j < n; ++j) {
+        MVSIM_CHECK_ARG(out_dev[j] != nullptr, "interval jobs: null output");
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(out_dev[j]), o1 = o0 + (uintptr_t)geoms[(size_t)j].n_out() * sizeof(float);
+        for (int w = 0; w < n; ++w) {
+            const uintptr_t v0 = reinterpret_cast<uintptr_t>(jobs[w].in), v1 = v0 + (uintptr_t)nvox(jobs[w].dim) * sizeof(float);
+            const uintptr_t p0 = reinterpret_cast<uintptr_t>(out_dev[w]), p1 = p0 + (uintptr_t)geoms[(size_t)w].n_out() * sizeof(float);
+            MVSIM_CHECK_ARG(!(o0 < v1 && v0 < o1), "interval jobs: an output overlaps a job's volume");
+            MVSIM_CHECK_ARG(w <= j || !out_dev[w] || !(o0 < p1 && p0 < o1), "interval jobs: outputs overlap each other");
+        }
+    }
+    return extract_intervals_enqueue(ctx, jobs, geoms, out_dev);
 }
 
 int mvsim_make_isotropic_dev(mvsim_ctx* ctx, const float* in, const int64_t dim[3], int inc, float* out)

@@ -214,6 +214,49 @@ int mvsim_extract_slices(mvsim_ctx* ctx, const float* in, const int64_t dim[3], 
     return down_counts(ctx, out, ctx->out_buf.as<float>(), (int64_t)(obytes / sizeof(float)), snr >= 0.0f);
 }
 
+// Volumes on the DEVICE, tiles on the HOST: the tiles are staged side by side in the context's output workspace; the sampled ones of 2^20
+// values and more cross PCIe as 16-bit counts in ONE transfer (down_counts' staging and its float32 fallback), the others as they are.
+int mvsim_extract_intervals(mvsim_ctx* ctx, const mvsim_interval_job* jobs, int n, float* const* out_host)
+{
+    MVSIM_TRY(set_device(ctx));
+    MVSIM_CHECK_ARG(out_host != nullptr, "interval jobs: null pointer");
+    std::vector<IntervalGeom> geoms;
+    MVSIM_TRY(interval_jobs_check(jobs, n, &geoms));
+    std::vector<size_t> off((size_t)n + 1, 0);
+    for (int j = 0; j < n; ++j) {
+        MVSIM_CHECK_ARG(out_host[j] != nullptr, "interval jobs: null output");
+        off[(size_t)j + 1] = off[(size_t)j] + (((size_t)geoms[(size_t)j].n_out() * sizeof(float) + 255) & ~(size_t)255);
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(out_host[j]), o1 = o0 + (uintptr_t)geoms[(size_t)j].n_out() * sizeof(float);
+        for (int w = 0; w < j; ++w) {
+            const uintptr_t p0 = reinterpret_cast<uintptr_t>(out_host[w]), p1 = p0 + (uintptr_t)geoms[(size_t)w].n_out() * sizeof(float);
+            MVSIM_CHECK_ARG(!(o0 < p1 && p0 < o1), "interval jobs: outputs overlap each other");
+        }
+    }
+    MVSIM_TRY(ctx->out_buf.reserve(off[(size_t)n]));
+    std::vector<float*> dev((size_t)n);
+    for (int j = 0; j < n; ++j) dev[(size_t)j] = reinterpret_cast<float*>(ctx->out_buf.as<char>() + off[(size_t)j]);
+    MVSIM_TRY(extract_intervals_enqueue(ctx, jobs, geoms, dev.data()));
+    std::vector<long long> counts;                    // the outputs that cross as 16-bit counts, and where they come from / go to
+    std::vector<const float*> src16;
+    std::vector<float*> dst16;
+    for (int j = 0; j < n; ++j) {
+        const long long c = geoms[(size_t)j].n_out();
+        if (jobs[j].snr >= 0.0f && ctx->opt.acq_u16 != 0 && c >= (1ll << 20)) {
+            counts.push_back(c); src16.push_back(dev[(size_t)j]); dst16.push_back(out_host[j]);
+        } else {
+            MVSIM_HIP(hipMemcpyAsync(out_host[j], dev[(size_t)j], (size_t)c * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        }
+    }
+    SyncOnExit sync{ctx};                             // the host outputs are the caller's again on every path
+    if (counts.empty()) { MVSIM_HIP(hipStreamSynchronize(ctx->stream)); return MVSIM_OK; }
+    CountsStaging& st = ctx->sync_counts;
+    MVSIM_TRY(st.reserve(counts.data(), (int)counts.size()));
+    for (size_t v = 0; v < counts.size(); ++v) MVSIM_TRY(st.pack(ctx->stream, (int)v, src16[v]));
+    MVSIM_TRY(st.fetch(ctx->stream));
+    MVSIM_HIP(hipStreamSynchronize(ctx->stream));
+    return st.land(ctx, src16.data(), dst16.data());
+}
+
 int mvsim_poisson_process(mvsim_ctx* ctx, float* img, int64_t n, double snr, uint64_t seed, uint32_t stream,
                           uint64_t index_offset)
 {

@@ -20,6 +20,10 @@ int set_device(mvsim_ctx* ctx, bool keep_tail = false);
 int extract_stage_plan(mvsim_ctx* ctx, const ExtractGeom& g, const ExtractOps& ops, ExtractPlan* pl, bool views_aligned16 = false);
 int extract_stage_run(mvsim_ctx* ctx, const ExtractPlan& pl, ExtractOps& ops);
 int extract_stage(mvsim_ctx* ctx, const ExtractGeom& g, ExtractOps& ops);
+// extractSlices over intervals of device volumes (api.cpp): the jobs checked against everything mvsim_extract_intervals* refuses but the
+// outputs (geoms: one per job), and the launches of checked jobs into DEVICE outputs, asynchronous on ctx->stream
+int interval_jobs_check(const mvsim_interval_job* jobs, int n, std::vector<IntervalGeom>* geoms);
+int extract_intervals_enqueue(mvsim_ctx* ctx, const mvsim_interval_job* jobs, const std::vector<IntervalGeom>& geoms, float* const* out_dev);
 int host_threads_of(const mvsim_ctx* ctx);
 void psf_normalise_host(float* psf_host, int64_t n);
 int psf_prepare(mvsim_ctx* ctx, float* psf_host, const int64_t kdim[3], const int64_t dim[3]);

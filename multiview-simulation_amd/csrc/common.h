@@ -18,6 +18,7 @@
 
 #include "../../include/mvsim.h"
 #include "extract_plan.h"
+#include "interval_plan.h"
 #include "sphere_walk.h"
 
 // Attribution switches (tools/attribute_flags.sh, attribute_valu.sh, attribution_run.sh: builds that compile a part of a kernel's work
@@ -226,6 +227,7 @@ struct mvsim_ctx {
     mvsim::DevBuf out_buf;                  // extract output staging
     mvsim::DevBuf psf_dev;                  // K^3 floats
     mvsim::DevBuf view_tab;                 // stacked views: [inverse models][extract tables][PSFs] of the current batch
+    mvsim::DevBuf interval_tab;             // interval jobs of the current call: [IntervalView table][ExtractView table] (extract_interval.hip)
     mvsim::DevBuf stencil_psf;              // direct stencil: PSF reversed along x, rows zero-padded to 4 taps
     mvsim::PinnedRing pinned;
     mvsim::DevBuf fft_real;                 // P^3 floats
@@ -340,7 +342,7 @@ enum { WS_KEPT = 1, WS_NO_EPOCH = 2 };
 template <class F> inline void mvsim_ctx::each_workspace(F&& f)
 {
     for (mvsim::DevBuf* b : {&vol_a, &vol_b, &vol_c, &out_buf, &psf_dev, &stencil_psf, &fft_real, &fft_spec_img, &fft_spec_psf, &fft_work,
-                             &pqueue, &view_tab, &sphere_list, &weight_img, &plane_flags, &host_gt, &host_rot, &host_att, &host_con, &cfft_f, &cfft_g,
+                             &pqueue, &view_tab, &interval_tab, &sphere_list, &weight_img, &plane_flags, &host_gt, &host_rot, &host_att, &host_con, &cfft_f, &cfft_g,
                              &cfft_g1, &cfft_g2, &partials_z, &async_gt[0], &async_gt[1], &async_acq[0], &async_acq[1], &async_counts[0].dev,
                              &async_counts[1].dev, &sync_counts.dev})
         f(*b, 0);
@@ -401,6 +403,18 @@ int launch_resolve(hipStream_t s, const ExtractPlan& pl, const ExtractOps& o);  
 // per segment}.  index_inc: 0 = inc; qshare: 0 = no work queue, else 1..16 sixteenths.
 void extract_path(const int64_t dim[3], int inc, int index_inc, uint64_t index_offset, bool aligned16, int qshare, int64_t path[4]);
 int poisson_queue_read_stats(const void* queue_ws, size_t bytes, long long stats[5]);
+// ---- extractSlices over intervals of device volumes (extract_interval.hip runs what interval_plan.h plans)
+struct IntervalView {             // per-job operands of the interval kernels (device table, blockIdx.y = job): ExtractView's idea, plus the
+    const float*  in;             // pitches of the volume the tile is cut from.  in: the interval's MIN corner
+    float*        out;            // the contiguous zero-min tile
+    void*         queue;          // the job's Poisson work-queue segments (PItem) ...
+    unsigned int* qcount;         // ... and their counters
+    uint32_t      k0, k1, stream, pad;
+    long long     row_pitch, plane_pitch;   // voxels from one row / plane of the volume to the next
+};
+// One launch per sampler stage for `njobs` jobs of one IntervalPlan.  vt: their IntervalView table; rvt: the same jobs as the resolver's
+// table (out, queue, qcount, keys; sampled launches with a queue only) -- both on the device.
+int launch_extract_interval(hipStream_t s, const IntervalPlan& pl, const IntervalView* vt, const ExtractView* rvt, int njobs, bool noise, double mul);
 // ---- stacked views (mvsim_simulate_views_dev): one launch per stage for V views of one ground truth; blockIdx.y / .z = view
 int launch_rotate_attenuate_views(hipStream_t s, const float* in, float* att, const int64_t dim[3], const Affine* atab_dev, int nviews, double delta);
 int launch_pack_u16(hipStream_t s, const float* in, unsigned short* out16, int64_t n, unsigned int* flag);

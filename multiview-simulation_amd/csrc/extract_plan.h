@@ -18,7 +18,8 @@ constexpr int QCOUNT_HEADER = QCOUNT_WORDS * POISSON_MAX_BLOCKS;        // word 
 constexpr size_t PITEM_BYTES = 16;                                      // one work item (poisson_dev.h: PItem)
 
 // The sampler form: path = {EXTRACT_K_*, segments can refuse, blocks, items per segment} (mvsim_extract_path, mvsim_get_extract_path)
-enum { EXTRACT_K_SCALAR = 0, EXTRACT_K_VEC = 1, EXTRACT_K_NOISE2 = 2, EXTRACT_K_NOISE2_ANY = 3, EXTRACT_FUSED_TAIL = 4 };
+enum { EXTRACT_K_SCALAR = 0, EXTRACT_K_VEC = 1, EXTRACT_K_NOISE2 = 2, EXTRACT_K_NOISE2_ANY = 3, EXTRACT_FUSED_TAIL = 4,
+       EXTRACT_K_INTERVAL = 5 };   // 5: an interval launch (interval_plan.h), reported by mvsim_get_extract_path only
 
 // How the stage samples.  share 0: one launch, no work queue.  1..16: work queue whose per-block segments hold that many sixteenths
 // of the block's voxels.  QUEUE_SHARE_AUTO + L (L = 0..16): the library's choice -- every voxel for queues of up to 64 MiB, else
