@@ -343,6 +343,65 @@ int mvsim_project_to_camera(mvsim_ctx* ctx, const float* ri_img, const float* re
                             int rays_per_pixel, uint64_t* rnd_state, float* proj);
 int mvsim_project_to_camera_dev(mvsim_ctx* ctx, const float* ri_img_dev, const float* refr_dev, const int64_t dim[3], int current_z,
                                 int rays_per_pixel, uint64_t* rnd_state, float* proj_dev);
+/* ---- the ray sandbox: net.preibisch.simulation.raytracing.RayTracingTest, and the general tracer under it -------------------
+ *   RTT = .../raytracing/RayTracingTest.java; RAY, HES, VI, SMVA as above.
+ * refract3d and projectToCamera launch the two ray families the reference hard-codes; mvsim_trace_rays launches the CALLER's rays
+ * through the same move.  What is exact and what is not is as above: starts, the wedge, the Hessian plane and the injection of a
+ * given step list are bit-exact; a ray's path is exact until its first refraction and within the libm's ulp afterwards.  On one
+ * device, mvsim_trace_rays given refract3d's starts, the map (1, ri), max_moves = Nz and the image as value source returns
+ * refract3d's step list, image and weight bit for bit. */
+#define MVSIM_TRACE_KEEP    0   /* total reflection: the ray keeps its direction (every loop of the reference) */
+#define MVSIM_TRACE_REFLECT 1   /* ... or takes RAY:32-40 reflect (the line RTT:164 has commented out), then norm */
+typedef struct mvsim_trace_params {
+    double  n_a, n_b;          /* the linear index map n = (n_b - n_a) * sample + n_a: (1, ri) is refract3d, (0, 1) a raw index image */
+    double  ev_threshold;      /* a move refracts where |largest eigenvalue| > ev_threshold (0.01 in every reference loop); >= 0 */
+    int64_t max_moves;         /* 1 .. 2^20 moves per ray: always finite, so no ray can spin */
+    int32_t total_reflection;  /* MVSIM_TRACE_KEEP / MVSIM_TRACE_REFLECT */
+    int32_t normalize_dirs;    /* != 0: RAY:66-73 norm applied once to every direction (a zero direction: MVSIM_EINVAL); 0: as given */
+    double  constant_value;    /* the value a ray carries when there is neither an image volume nor an intensity list, as a float */
+    double  sigma[3];          /* the injected Gaussians (VI): > 0 */
+    int32_t normalized;        /* != 0: addNormalizedGaussian (value / sumWeights), 0: addGaussian */
+} mvsim_trace_params;
+/* The sandbox's settings: (0, 1), 0.01, max_moves = 4 * (Nx + Ny + Nz) (the reference's loops have no cap), keep, directions as
+ * given, constant 1.0, sigma 0.5, normalized. */
+int mvsim_trace_params_default(const int64_t dim[3], mvsim_trace_params* params);
+/* n rays, ray r from pos3[r] along dir3[r] (host lists; |coordinate| < 2^30).  A ray moves while it is inside (0 <= p <= N - 1) and
+ * has made fewer than max_moves moves.  Per move: the value it carries is the interpolated sample of img (may be NULL), else
+ * intensity[r] (floats, may be NULL), else constant_value -- a float, like the step list's values; Hessian of ri_img and its largest
+ * eigenpair; where |eigenvalue| > ev_threshold the refraction of refract3d with the map above and the total-reflection policy; the
+ * step record; position += direction.  Outputs, each may be NULL (image and weight go together): image and weight, OVERWRITTEN with
+ * the injection of the step list in list order (sigma, normalized); steps (moves: n counts); end_pos3 and end_dir3 (n * 3: where
+ * each ray stood when it stopped, outside or at its last allowed move, and the direction it had); n_capped: the rays still inside
+ * after max_moves moves.  Rays run in ranges of at most 2^25 step records (option "beads_pair_cap" / 8 lowers it): same bits.
+ * MVSIM_EINVAL: non-finite scalars, positions, directions or intensities, max_moves outside 1 .. 2^20, ev_threshold < 0, sigma <= 0,
+ * a dimension below 2, a null index volume, a step list that needs more than its capacity. */
+int mvsim_trace_rays(mvsim_ctx* ctx, const float* ri_img, const float* img, const int64_t dim[3], const double* pos3, const double* dir3,
+                     const float* intensity, int64_t n, const mvsim_trace_params* params, float* image, float* weight,
+                     mvsim_ray_steps* steps, double* end_pos3, double* end_dir3, int64_t* n_capped);
+/* Device volumes; image_dev and weight_dev are ADDED to (zero them for the sandbox's result).  Synchronises. */
+int mvsim_trace_rays_dev(mvsim_ctx* ctx, const float* ri_img_dev, const float* img_dev, const int64_t dim[3], const double* pos3,
+                         const double* dir3, const float* intensity, int64_t n, const mvsim_trace_params* params, float* image_dev,
+                         float* weight_dev, mvsim_ray_steps* steps, double* end_pos3, double* end_dir3, int64_t* n_capped);
+/* RTT:110-123 drawMultipleRays' bundle, computed on the GPU: ray i consumes draws 2i, 2i + 1 of nextDouble() of the caller's
+ * java.util.Random (the reference: new Random(234345)): (x + u - 0.5, Ny - 1, z + u - 0.5), direction (0, -1, 0).  rnd_state is
+ * advanced by the 4 n generator steps.  Bit-exact. */
+int mvsim_sandbox_ray_starts(mvsim_ctx* ctx, uint64_t* rnd_state, const int64_t dim[3], int x, int z, int64_t n, double* pos3,
+                             double* dir3);
+/* RTT:334-344 drawRays' grid: x = spacing, 2 spacing, .. <= Nx from (x, Ny - 25, z), direction (0, -1, 0).  Returns the number of
+ * rays, Nx / spacing, in *n_out; pos3 and dir3 hold `capacity` rays (MVSIM_EINVAL when that is too few; both may be NULL with
+ * capacity 0 to ask for the count).  Quirks kept: x = Nx is a ray that is not inside and makes no move; Ny < 25 gives rays that
+ * make no move (Ny = 25 starts at y = 0: one move).  spacing >= 1. */
+int mvsim_grid_ray_starts(mvsim_ctx* ctx, const int64_t dim[3], int z, int spacing, int64_t capacity, double* pos3, double* dir3,
+                          int64_t* n_out);
+/* RAY:96-128 drawSimpleImage, the wedge: out = high where (x < Nx / 2 ? x > y : Nx - x > y) (integer division), low elsewhere,
+ * for every z.  Bit-exact. */
+int mvsim_draw_simple_image(mvsim_ctx* ctx, float* out, const int64_t dim[3], float low, float high);
+int mvsim_draw_simple_image_dev(mvsim_ctx* ctx, float* out_dev, const int64_t dim[3], float low, float high);
+/* RTT:55-84 hessian(img, z): plane z (0 <= z < Nz) of mvsim_hessian_images alone -- eigval[Ny][Nx], eigvec[3][Ny][Nx] (may be
+ * NULL) -- at the cost of one plane.  (The reference returns a copy of img with that plane replaced by eigval.) */
+int mvsim_hessian_plane(mvsim_ctx* ctx, const float* img, const int64_t dim[3], int z, float* eigval, float* eigvec);
+int mvsim_hessian_plane_dev(mvsim_ctx* ctx, const float* img_dev, const int64_t dim[3], int z, float* eigval_dev, float* eigvec_dev);
+
 /* The simulator's phantom, SMVA:408-440 simulate(rnd, dir): everything behind its Tools.open(dir + "block4.tif") -- a file the reference
  * does not ship; the caller supplies that canvas of refractive indices.
  * SMVA:425-426: voxel i of ri (x fastest, n voxels, n == 0 is legal) becomes (float)Math.max(0, ri[i] + (nextDouble() - 0.5) / 10), in

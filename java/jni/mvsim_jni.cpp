@@ -328,6 +328,70 @@ JNIEXPORT void JNICALL JNI_FN(projectToCamera)(JNIEnv* env, jclass, jlong h, job
     env->SetLongArrayRegion(rnd_state, 0, 1, &st);
 }
 
+// ---- the ray sandbox (mvsim_trace_rays, mvsim_draw_simple_image, mvsim_sandbox_ray_starts) ------------------------------------------
+// pos3 / dir3: direct DoubleBuffers of 3 n doubles; img_in and intensity may be null; image and weight are given together or both
+// null.  The injection is the sandbox's (sigma 0.5, normalized).  Returns the number of rays still inside after max_moves moves.
+JNIEXPORT jlong JNICALL JNI_FN(traceRays)(JNIEnv* env, jclass, jlong h, jobject ri_img, jobject img_in, jlongArray dim, jobject pos3,
+                                          jobject dir3, jobject intensity, jlong n, jdouble n_a, jdouble n_b, jdouble ev_threshold,
+                                          jlong max_moves, jint total_reflection, jboolean normalize_dirs, jdouble constant_value,
+                                          jobject image, jobject weight)
+{
+    Dim d(env, dim);
+    if (!d.ok) return 0;
+    if (n < 0) { throw_new(env, "java/lang/IllegalArgumentException", "traceRays: negative number of rays"); return 0; }
+    float* pr = fptr(env, ri_img, d.n(), "traceRays: refractive-index buffer smaller than the dimensions");
+    if (!pr) return 0;
+    float* pi = fptr(env, img_in, d.n(), "traceRays: image buffer smaller than the dimensions", true);
+    float* pv = fptr(env, intensity, n, "traceRays: intensity buffer smaller than n floats", true);
+    float* po = fptr(env, image, d.n(), "traceRays: output image buffer smaller than the dimensions", true);
+    float* pw = fptr(env, weight, d.n(), "traceRays: output weight buffer smaller than the dimensions", true);
+    if (env->ExceptionCheck()) return 0;
+    const double* pp = nullptr;
+    const double* pd = nullptr;
+    if (n > 0) {
+        pp = static_cast<const double*>(any_ptr(env, pos3, 3 * n, "traceRays: position buffer smaller than 3 n doubles"));
+        if (!pp) return 0;
+        pd = static_cast<const double*>(any_ptr(env, dir3, 3 * n, "traceRays: direction buffer smaller than 3 n doubles"));
+        if (!pd) return 0;
+    }
+    mvsim_trace_params tp;
+    int rc = mvsim_trace_params_default(d.d, &tp);
+    if (rc != MVSIM_OK) { throw_for(env, rc); return 0; }
+    tp.n_a = n_a; tp.n_b = n_b; tp.ev_threshold = ev_threshold; tp.max_moves = max_moves; tp.total_reflection = total_reflection;
+    tp.normalize_dirs = normalize_dirs ? 1 : 0; tp.constant_value = constant_value;
+    int64_t capped = 0;
+    rc = mvsim_trace_rays(ctx_of(h), pr, pi, d.d, pp, pd, pv, n, &tp, po, pw, nullptr, nullptr, nullptr, &capped);
+    if (rc != MVSIM_OK) { throw_for(env, rc); return 0; }
+    return static_cast<jlong>(capped);
+}
+
+JNIEXPORT void JNICALL JNI_FN(drawSimpleImage)(JNIEnv* env, jclass, jlong h, jobject out, jlongArray dim, jfloat low, jfloat high)
+{
+    Dim d(env, dim);
+    if (!d.ok) return;
+    float* po = fptr(env, out, d.n(), "drawSimpleImage: buffer smaller than the dimensions");
+    if (!po) return;
+    throw_for(env, mvsim_draw_simple_image(ctx_of(h), po, d.d, low, high));
+}
+
+JNIEXPORT void JNICALL JNI_FN(sandboxRayStarts)(JNIEnv* env, jclass, jlong h, jlongArray rnd_state, jlongArray dim, jint x, jint z, jlong n,
+                                                jobject pos3, jobject dir3)
+{
+    Dim d(env, dim);
+    if (!d.ok) return;
+    if (n < 0) { throw_new(env, "java/lang/IllegalArgumentException", "sandboxRayStarts: negative number of rays"); return; }
+    double* pp = static_cast<double*>(any_ptr(env, pos3, 3 * n, "sandboxRayStarts: position buffer smaller than 3 n doubles"));
+    if (!pp) return;
+    double* pd = static_cast<double*>(any_ptr(env, dir3, 3 * n, "sandboxRayStarts: direction buffer smaller than 3 n doubles"));
+    if (!pd) return;
+    uint64_t state = 0;
+    if (!state_in(env, rnd_state, "sandboxRayStarts: long[1] state expected", &state)) return;
+    const int rc = mvsim_sandbox_ray_starts(ctx_of(h), &state, d.d, x, z, n, pp, pd);
+    if (rc != MVSIM_OK) { throw_for(env, rc); return; }
+    const jlong st = static_cast<jlong>(state);
+    env->SetLongArrayRegion(rnd_state, 0, 1, &st);
+}
+
 // ---- per-stage operators with z-slab lists (mvsim_*_zslabs) ----------------------------------------------------------
 namespace {
 // the host pointers and plane counts of a FloatBuffer[] / long[] pair; every buffer is checked against plane * nz[i] floats

@@ -45,6 +45,19 @@ final class MvsimNative
 	static native void projectToCamera( long ctx, FloatBuffer imgRi, FloatBuffer refr, long[] dim, int currentZ, int raysPerPixel,
 			long[] rndState, FloatBuffer proj );
 
+	// the general tracer under RayTracingTest (mvsim_trace_rays): n rays from pos3 along dir3 (3 n doubles each) through imgRi mapped by
+	// (nB - nA) * sample + nA; the value carried is imgIn's sample, else intensity (n floats), else constantValue (either may be null);
+	// totalReflection 0 keeps the direction, 1 reflects; image and weight (both or neither) receive the sandbox's injection (sigma 0.5,
+	// normalized).  Returns the number of rays still inside after maxMoves moves
+	static native long traceRays( long ctx, FloatBuffer imgRi, FloatBuffer imgIn, long[] dim, java.nio.DoubleBuffer pos3, java.nio.DoubleBuffer dir3,
+			FloatBuffer intensity, long n, double nA, double nB, double evThreshold, long maxMoves, int totalReflection, boolean normalizeDirs,
+			double constantValue, FloatBuffer image, FloatBuffer weight );
+	// Raytrace.drawSimpleImage (mvsim_draw_simple_image): the wedge
+	static native void drawSimpleImage( long ctx, FloatBuffer out, long[] dim, float low, float high );
+	// RayTracingTest.drawMultipleRays' bundle (mvsim_sandbox_ray_starts): n starts around (x, Ny - 1, z) drawn from rndState[0], advanced on return
+	static native void sandboxRayStarts( long ctx, long[] rndState, long[] dim, int x, int z, long n, java.nio.DoubleBuffer pos3,
+			java.nio.DoubleBuffer dir3 );
+
 	// the per-stage operators with volumes as z-slab lists (mvsim_*_zslabs): in[i] holds inNz[i] planes, out[j] receives outNz[j];
 	// this is how images beyond one 2 GiB direct buffer (2^29 voxels) cross the boundary -- a 512^3 image is a list of one
 	static native void rotateAroundAxisSlabs( long ctx, FloatBuffer[] in, long[] inNz, long[] dim, int axis, int degrees, FloatBuffer[] out, long[] outNz );

@@ -29,7 +29,7 @@ from .aberrations import ContextAberrations
 from .phantoms import ContextPhantoms
 
 __all__ = ["AffineTransform3D", "Context", "Group", "Hessian", "HypersphereCollectionRealRandomAccessible", "JavaRandom", "Lightsheet",
-           "PerlinNoiseRealRandomAccessible", "PointRejectionSampling", "Raytrace", "SimpleCalculatedRealRandomAccessible", "SimulateBeads",
+           "PerlinNoiseRealRandomAccessible", "PointRejectionSampling", "RayTracingTest", "Raytrace", "RefractiveIndexMap", "ClearingMap", "SimpleCalculatedRealRandomAccessible", "SimulateBeads",
            "SimulateBeads2", "SimulateMultiViewAberrations", "SimulateMultiViewDataset", "Tools", "VolumeInjection", "broadcast_plan", "default_context", "MvsimError", "MvsimNoDeviceError", "ViewParams", "shard_views",
            "version"]
 
@@ -1335,6 +1335,6 @@ class SimulateTileStitching:
 
 
 from .beads import AffineTransform3D, SimulateBeads, SimulateBeads2  # noqa: E402
-from .aberrations import Hessian, Lightsheet, Raytrace, SimulateMultiViewAberrations, VolumeInjection  # noqa: E402
+from .aberrations import ClearingMap, Hessian, Lightsheet, RayTracingTest, Raytrace, RefractiveIndexMap, SimulateMultiViewAberrations, VolumeInjection  # noqa: E402
 from .phantoms import (HypersphereCollectionRealRandomAccessible, PerlinNoiseRealRandomAccessible, PointRejectionSampling,  # noqa: E402
                        SimpleCalculatedRealRandomAccessible)

@@ -54,6 +54,16 @@ class RaySteps(C.Structure):
                 ("moves", C.POINTER(C.c_int32))]
 
 
+class TraceParams(C.Structure):
+    """mvsim_trace_params: the settings of mvsim_trace_rays."""
+    _fields_ = [("n_a", C.c_double), ("n_b", C.c_double), ("ev_threshold", C.c_double), ("max_moves", C.c_int64),
+                ("total_reflection", C.c_int32), ("normalize_dirs", C.c_int32), ("constant_value", C.c_double), ("sigma", C.c_double * 3),
+                ("normalized", C.c_int32)]
+
+
+MVSIM_TRACE_KEEP, MVSIM_TRACE_REFLECT = 0, 1
+
+
 class Perlin(C.Structure):
     """mvsim_perlin: a Perlin field (host tables)."""
     _fields_ = [("scales", C.c_double * 3), ("loop_extents", C.c_int32 * 3), ("n_vectors", C.c_int32), ("gradients", C.POINTER(C.c_double)),
@@ -228,6 +238,17 @@ SIGNATURES = {
                                   C.POINTER(C.c_uint64), _vp, _vp, C.POINTER(RaySteps)]),
     "mvsim_refract3d_dev": (C.c_int, [_vp, _vp, _vp, _i64p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64,
                                       C.POINTER(C.c_uint64), _vp, _vp, C.POINTER(RaySteps)]),
+    "mvsim_trace_params_default": (C.c_int, [_i64p, C.POINTER(TraceParams)]),
+    "mvsim_trace_rays": (C.c_int, [_vp, _vp, _vp, _i64p, _dp, _dp, C.POINTER(C.c_float), C.c_int64, C.POINTER(TraceParams), _vp, _vp,
+                                   C.POINTER(RaySteps), _dp, _dp, C.POINTER(C.c_int64)]),
+    "mvsim_trace_rays_dev": (C.c_int, [_vp, _vp, _vp, _i64p, _dp, _dp, C.POINTER(C.c_float), C.c_int64, C.POINTER(TraceParams), _vp, _vp,
+                                       C.POINTER(RaySteps), _dp, _dp, C.POINTER(C.c_int64)]),
+    "mvsim_sandbox_ray_starts": (C.c_int, [_vp, C.POINTER(C.c_uint64), _i64p, C.c_int, C.c_int, C.c_int64, _dp, _dp]),
+    "mvsim_grid_ray_starts": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int64, _dp, _dp, C.POINTER(C.c_int64)]),
+    "mvsim_draw_simple_image": (C.c_int, [_vp, _vp, _i64p, C.c_float, C.c_float]),
+    "mvsim_draw_simple_image_dev": (C.c_int, [_vp, _vp, _i64p, C.c_float, C.c_float]),
+    "mvsim_hessian_plane": (C.c_int, [_vp, _vp, _i64p, C.c_int, _vp, _vp]),
+    "mvsim_hessian_plane_dev": (C.c_int, [_vp, _vp, _i64p, C.c_int, _vp, _vp]),
     "mvsim_volume_inject": (C.c_int, [_vp, _vp, _vp, _i64p, _dp, _dp, _dp, C.c_int64, C.c_int]),
     "mvsim_volume_inject_dev": (C.c_int, [_vp, _vp, _vp, _i64p, _dp, _dp, _dp, C.c_int64, C.c_int]),
     "mvsim_volume_inject_info": (C.c_int, [_dp, C.POINTER(C.c_int32), _dp, C.POINTER(C.c_int32)]),

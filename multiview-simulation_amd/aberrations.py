@@ -11,7 +11,9 @@ The simulator's own phantom, ``simulate(rnd, dir)`` (:408-440), is ``simulatePha
 holds the file; ``synthetic.index_block`` is a stand-in).  ``multiSpheres`` uses the ranges the reference hard-codes; its
 ``min == max`` branches never run and are not offered.
 
-Out of scope, as in the C ABI: ``RayTracingTest``, ``ClearingMap``, ``RefractiveIndexMap`` and ``cluster/``."""
+The ray sandbox, ``raytracing.RayTracingTest``, sits on the general tracer of raytrace.hip (``Context.trace_rays``: the caller's
+rays through the same move); ``RefractiveIndexMap`` is the linear map that tracer takes, ``ClearingMap`` the reference's stub.
+``cluster/`` stays out of scope, as in the C ABI."""
 from __future__ import annotations
 
 import ctypes as C
@@ -170,6 +172,114 @@ class ContextAberrations:
         return out
 
 
+    # ---- the general tracer and the ray sandbox (raytrace.hip) ----
+    def _trace_params(self, dim, n_a, n_b, ev_threshold, max_moves, total_reflection, normalize_dirs, constant_value, sigma, normalized):
+        tp = _lib.TraceParams()
+        _lib.check(self._L.mvsim_trace_params_default(dim, C.byref(tp)))
+        tp.n_a, tp.n_b, tp.ev_threshold = float(n_a), float(n_b), float(ev_threshold)
+        if max_moves is not None:
+            tp.max_moves = int(max_moves)
+        policies = {"keep": _lib.MVSIM_TRACE_KEEP, "reflect": _lib.MVSIM_TRACE_REFLECT}
+        if total_reflection not in policies:
+            raise ValueError("total_reflection must be 'keep' or 'reflect'")
+        tp.total_reflection = policies[total_reflection]
+        tp.normalize_dirs, tp.constant_value, tp.normalized = int(bool(normalize_dirs)), float(constant_value), int(bool(normalized))
+        tp.sigma[0], tp.sigma[1], tp.sigma[2] = (float(x) for x in sigma)
+        return tp
+
+    def _trace_call(self, fn, ri_p, img_p, dim, pos3, dir3, intensity, tp, image_p, weight_p, steps, ends):
+        pos, vec = _points(pos3), _points(dir3)
+        n = len(pos)
+        if len(vec) != n:
+            raise ValueError("one direction per ray")
+        inten = None
+        if intensity is not None:
+            inten = np.ascontiguousarray(intensity, dtype=np.float32).reshape(-1)
+            if len(inten) != n:
+                raise ValueError("one intensity per ray")
+        out, rs = {}, None
+        if steps:
+            cap = max(1, n) * int(tp.max_moves)
+            xyz, val, mv = np.empty((cap, 3)), np.empty(cap, np.float32), np.empty(max(1, n), np.int32)
+            rs = _lib.RaySteps(cap, 0, _d(xyz), val.ctypes.data_as(C.POINTER(C.c_float)), mv.ctypes.data_as(C.POINTER(C.c_int32)))
+        if ends:
+            out["end_pos"], out["end_dir"] = np.empty((n, 3)), np.empty((n, 3))
+        capped = C.c_int64(0)
+        _lib.check(fn(self._h, ri_p, img_p, dim, _d(pos), _d(vec), None if inten is None else inten.ctypes.data_as(C.POINTER(C.c_float)), n,
+                      C.byref(tp), image_p, weight_p, None if rs is None else C.byref(rs), _d(out.get("end_pos")), _d(out.get("end_dir")),
+                      C.byref(capped)))
+        if steps:
+            out["xyz"], out["value"], out["moves"] = xyz[:rs.n].copy(), val[:rs.n].copy(), mv[:n]
+        out["n_capped"] = int(capped.value)
+        return out
+
+    def trace_rays(self, ri_img, pos3, dir3, img=None, intensity=None, n_a=0.0, n_b=1.0, ev_threshold=0.01, max_moves=None,
+                   total_reflection="keep", normalize_dirs=False, constant_value=1.0, sigma=(0.5, 0.5, 0.5), normalized=True, steps=False,
+                   inject=True, ends=True) -> dict:
+        """Caller-supplied rays through the move of refract3d (mvsim_trace_rays).  ri_img: the index volume, mapped by
+        n = (n_b - n_a) * sample + n_a; the value a ray carries: the sample of ``img``, else ``intensity`` per ray, else
+        ``constant_value``.  max_moves: 4 * (Nx + Ny + Nz) by default.  Returns {"image", "weight"} (inject), {"xyz", "value", "moves"}
+        (steps=True), {"end_pos", "end_dir"} (ends) and "n_capped": the rays still inside after max_moves moves."""
+        b = _vol(ri_img, "imgRi")
+        a = None if img is None else _vol(img, "imgIn")
+        if a is not None and a.shape != b.shape:
+            raise ValueError("imgIn and imgRi must have the same dimensions")
+        dim = _dim(b)
+        tp = self._trace_params(dim, n_a, n_b, ev_threshold, max_moves, total_reflection, normalize_dirs, constant_value, sigma, normalized)
+        image = np.empty(b.shape, np.float32) if inject else None
+        weight = np.empty(b.shape, np.float32) if inject else None
+        out = self._trace_call(self._L.mvsim_trace_rays, _p(b), _p(a), dim, pos3, dir3, intensity, tp, _p(image), _p(weight), steps, ends)
+        if inject:
+            out["image"], out["weight"] = image, weight
+        return out
+
+    def trace_rays_dev(self, ri_dev, shape, pos3, dir3, img_dev=None, intensity=None, image_dev=None, weight_dev=None, n_a=0.0, n_b=1.0,
+                       ev_threshold=0.01, max_moves=None, total_reflection="keep", normalize_dirs=False, constant_value=1.0,
+                       sigma=(0.5, 0.5, 0.5), normalized=True, steps=False, ends=True) -> dict:
+        """trace_rays on DEVICE volumes of (Nz, Ny, Nx) floats (addresses as dev_alloc returns them); image_dev and weight_dev, given
+        together or not at all, are ADDED to.  Ray lists and every returned list are host arrays."""
+        dim = (C.c_int64 * 3)(shape[2], shape[1], shape[0])
+        tp = self._trace_params(dim, n_a, n_b, ev_threshold, max_moves, total_reflection, normalize_dirs, constant_value, sigma, normalized)
+        vp = lambda q: None if q is None else C.c_void_p(int(q))
+        return self._trace_call(self._L.mvsim_trace_rays_dev, vp(ri_dev), vp(img_dev), dim, pos3, dir3, intensity, tp, vp(image_dev),
+                                vp(weight_dev), steps, ends)
+
+    def sandbox_ray_starts(self, shape, x, z, n, rnd=None):
+        """RayTracingTest.drawMultipleRays' bundle (:110-123) for a (Nz, Ny, Nx) volume: (positions (n, 3), directions (n, 3)); rnd
+        (new Random(234345) by default) advances."""
+        st = _State(rnd, 234345)
+        dim = (C.c_int64 * 3)(shape[2], shape[1], shape[0])
+        pos, vec = np.empty((n, 3)), np.empty((n, 3))
+        _lib.check(self._L.mvsim_sandbox_ray_starts(self._h, C.byref(st.c), dim, int(x), int(z), n, _d(pos), _d(vec)))
+        st.commit()
+        return pos, vec
+
+    def grid_ray_starts(self, shape, z, spacing):
+        """RayTracingTest.drawRays' grid (:334-344): (positions (Nx // spacing, 3), directions)."""
+        dim = (C.c_int64 * 3)(shape[2], shape[1], shape[0])
+        n = C.c_int64(0)
+        _lib.check(self._L.mvsim_grid_ray_starts(self._h, dim, int(z), int(spacing), 0, None, None, C.byref(n)))
+        pos, vec = np.empty((n.value, 3)), np.empty((n.value, 3))
+        if n.value:
+            _lib.check(self._L.mvsim_grid_ray_starts(self._h, dim, int(z), int(spacing), n.value, _d(pos), _d(vec), C.byref(n)))
+        return pos, vec
+
+    def draw_simple_image(self, shape, low, high) -> np.ndarray:
+        """Raytrace.drawSimpleImage (:96-128): the wedge as a (Nz, Ny, Nx) volume."""
+        out = np.empty(tuple(int(k) for k in shape), np.float32)
+        _lib.check(self._L.mvsim_draw_simple_image(self._h, _p(out), _dim(out), float(low), float(high)))
+        return out
+
+    def hessian_plane(self, img, z, vectors=False):
+        """Plane z of hessian_images at the cost of one plane: the eigenvalue plane (Ny, Nx), with vectors=True
+        (eigenvalue plane, eigenvector planes (3, Ny, Nx))."""
+        v = _vol(img)
+        val = np.empty(v.shape[1:], np.float32)
+        vec = np.empty((3,) + v.shape[1:], np.float32) if vectors else None
+        _lib.check(self._L.mvsim_hessian_plane(self._h, _p(v), _dim(v), int(z), _p(val), _p(vec)))
+        return (val, vec) if vectors else val
+
+
 def _ctx():
     from . import default_context
     return default_context()
@@ -232,6 +342,14 @@ class Raytrace:
             v[d] /= l
 
     @staticmethod
+    def drawSimpleImage(randomAccessible, low, high, ctx=None) -> None:
+        """:96-128 -- the wedge, in place on a writable C-contiguous (Nz, Ny, Nx) float32 array."""
+        a = randomAccessible
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim != 3 or not a.flags.c_contiguous or not a.flags.writeable:
+            raise ValueError("drawSimpleImage needs a writable C-contiguous 3-D float32 numpy array")
+        a[...] = (ctx or _ctx()).draw_simple_image(a.shape, low, high)
+
+    @staticmethod
     def incidentAngle(i, n) -> float:
         """:75-93 -- flips n in place and SUBTRACTS pi / 2 when the angle is >= pi / 2 (the reference's quirk, kept)."""
         c = (n[0] * i[0] + n[1] * i[1] + n[2] * i[2]) / (math.sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]) *
@@ -242,6 +360,27 @@ class Raytrace:
                 n[d] *= -1
             thetaI -= math.pi / 2
         return thetaI
+
+
+class RefractiveIndexMap:
+    """raytracing/RefractiveIndexMap.java, as the linear map the tracers apply: getRI(i) = (n_b - n_a) * i + n_a.  (1, ri) is
+    refract3d's map, (0, 1) the sandbox's raw index image."""
+
+    def __init__(self, n_a=0.0, n_b=1.0):
+        self.n_a, self.n_b = float(n_a), float(n_b)
+
+    def getRI(self, intensity: float) -> float:
+        return (self.n_b - self.n_a) * intensity + self.n_a
+
+
+class ClearingMap(RefractiveIndexMap):
+    """raytracing/ClearingMap.java: the reference's stub, getRI returns 0."""
+
+    def __init__(self):
+        super().__init__(0.0, 0.0)
+
+    def getRI(self, intensity: float) -> float:
+        return 0
 
 
 class Hessian:
@@ -372,3 +511,77 @@ class SimulateMultiViewAberrations:
         out = c.refract3d(imgIn, imgRi, illum, z, lsMiddle, lsEdge, ri, num_rays=numRays)
         proj = c.project_to_camera(imgRi, out["image"], z, raysPerPixel, SimulateMultiViewAberrations._rnd())
         return {"refr_img": out["image"], "refr_weight": out["weight"], "proj": proj}
+
+
+class RayTracingTest:
+    """net.preibisch.simulation.raytracing.RayTracingTest: the ray sandbox, on Context.trace_rays.  The reference's loops have no
+    move cap; the mirror passes max_moves = 4 * (Nx + Ny + Nz) and raises if a ray is still inside after that many moves, because the
+    result would not be the reference's.  An index map other than the sandbox's raw image is a ``RefractiveIndexMap``."""
+
+    @staticmethod
+    def _trace(imgIn, pos, vec, ctx, riMap, steps=False, inject=True):
+        c = ctx or _ctx()
+        m = riMap or RefractiveIndexMap(0.0, 1.0)
+        v = _vol(imgIn, "imgIn")
+        out = c.trace_rays(v, pos, vec, n_a=m.n_a, n_b=m.n_b, max_moves=4 * sum(v.shape), steps=steps, inject=inject, ends=False)
+        if out["n_capped"] > 0:
+            raise RuntimeError(f"{out['n_capped']} rays were still inside the image after {4 * sum(v.shape)} moves: the reference would "
+                               "go on tracing them")
+        return out
+
+    @staticmethod
+    def hessian(img, z, ctx=None) -> np.ndarray:
+        """:55-84 -- a copy of img with plane z replaced by the largest eigenvalue of the Hessian."""
+        out = np.array(_vol(img), dtype=np.float32, copy=True)
+        out[int(z)] = (ctx or _ctx()).hessian_plane(img, z)
+        return out
+
+    @staticmethod
+    def drawMultipleRays(imgIn, z, x, numRays, ctx=None, riMap=None) -> VolumeInjection:
+        """:86-194 -- numRays rays from new Random(234345) around (x, Ny - 1, z), going down y."""
+        c = ctx or _ctx()
+        pos, vec = c.sandbox_ray_starts(np.shape(imgIn), x, z, int(numRays))
+        out = RayTracingTest._trace(imgIn, pos, vec, c, riMap)
+        return VolumeInjection(out["image"], out["weight"], [0.5, 0.5, 0.5], ctx=ctx)
+
+    @staticmethod
+    def drawRays(imgIn, z, spacing, ctx=None, riMap=None) -> VolumeInjection:
+        """:308-415 -- one ray every ``spacing`` voxels of x from (x, Ny - 25, z), going down y."""
+        c = ctx or _ctx()
+        pos, vec = c.grid_ray_starts(np.shape(imgIn), z, spacing)
+        out = RayTracingTest._trace(imgIn, pos, vec, c, riMap)
+        return VolumeInjection(out["image"], out["weight"], [0.5, 0.5, 0.5], ctx=ctx)
+
+    @staticmethod
+    def drawSingleRay(imgIn, z, x, ctx=None, riMap=None) -> np.ndarray:
+        """:196-306 -- the ray from (x, Ny - 25, z): the stack (moves, Ny, Nx) of the weight's plane z after each move, built from
+        the step list by injecting step after step.  The text overlay is not restated."""
+        c = ctx or _ctx()
+        v = _vol(imgIn, "imgIn")
+        out = RayTracingTest._trace(v, [[float(x), float(v.shape[1] - 25), float(z)]], [[0.0, -1.0, 0.0]], c, riMap, steps=True, inject=False)
+        image, weight = np.zeros(v.shape, np.float32), np.zeros(v.shape, np.float32)
+        frames = np.empty((len(out["xyz"]),) + v.shape[1:], np.float32)
+        for k in range(len(out["xyz"])):
+            c.volume_inject(image, weight, (0.5, 0.5, 0.5), out["xyz"][k:k + 1], out["value"][k:k + 1].astype(np.float64), True)
+            frames[k] = RayTracingTest.getProcessor(weight, z)
+        return frames
+
+    @staticmethod
+    def getProcessor(img, z) -> np.ndarray:
+        """:417-437 -- a copy of plane z."""
+        return np.array(np.asarray(img)[int(z)], dtype=np.float32, copy=True)
+
+    @staticmethod
+    def renderDifferentNAs(size=(300, 300, 10), naFrom=1.0, naTo=2.0, naStep=0.01, z=5, spacing=8, ctx=None) -> np.ndarray:
+        """:439-463 -- for na = naFrom; na <= naTo; na += naStep: the wedge (1.0, (float)na) of ``size`` = (Nx, Ny, Nz),
+        drawRays(wedge, z, spacing), plane z of its weight.  Returns the stack.  na is accumulated in fp64 as the reference's loop
+        does: its defaults give 100 scenes, 1.0 .. 1.99, because the sum passes 2 before the 101st."""
+        c = ctx or _ctx()
+        shape = (int(size[2]), int(size[1]), int(size[0]))
+        frames = []
+        na = float(naFrom)
+        while na <= naTo:
+            wedge = c.draw_simple_image(shape, 1.0, np.float32(na))
+            frames.append(RayTracingTest.getProcessor(RayTracingTest.drawRays(wedge, z, spacing, ctx=c).getWeight(), z))
+            na += naStep
+        return np.stack(frames) if frames else np.empty((0, shape[1], shape[2]), np.float32)

@@ -508,7 +508,7 @@ static int hessian_images_args(mvsim_ctx* ctx, const float* img, const int64_t d
 int mvsim_hessian_images_dev(mvsim_ctx* ctx, const float* img, const int64_t dim[3], float* eigval, float* eigvec)
 {
     MVSIM_TRY(hessian_images_args(ctx, img, dim, eigval, eigvec));
-    return aberr_hessian_images_dev(ctx, img, dim, eigval, eigvec);
+    return aberr_hessian_images_dev(ctx, img, dim, 0, (int)dim[2], eigval, eigvec);
 }
 
 int mvsim_hessian_images(mvsim_ctx* ctx, const float* img, const int64_t dim[3], float* eigval, float* eigvec)
@@ -518,7 +518,7 @@ int mvsim_hessian_images(mvsim_ctx* ctx, const float* img, const int64_t dim[3],
     MVSIM_TRY(up(ctx, ctx->vol_a, img, bytes));
     MVSIM_TRY(ctx->vol_b.reserve(4 * bytes));
     float* out = ctx->vol_b.as<float>();
-    MVSIM_TRY(aberr_hessian_images_dev(ctx, ctx->vol_a.as<float>(), dim, out, out + bytes / sizeof(float)));
+    MVSIM_TRY(aberr_hessian_images_dev(ctx, ctx->vol_a.as<float>(), dim, 0, (int)dim[2], out, out + bytes / sizeof(float)));
     MVSIM_HIP(hipMemcpyAsync(eigval, out, bytes, hipMemcpyDeviceToHost, ctx->stream));
     return down(ctx, eigvec, out + bytes / sizeof(float), 3 * bytes);
 }
@@ -773,6 +773,156 @@ int mvsim_project_to_camera(mvsim_ctx* ctx, const float* ri_img, const float* re
                                           ctx->vol_c.as<float>()));
     advance_camera_rays(rnd_state, dim, rays_per_pixel);
     return down(ctx, proj, ctx->vol_c.p, pbytes);
+}
+
+// ---- the ray sandbox (raytracing/RayTracingTest.java) and the general tracer (raytrace.hip) ------------------------------------
+int mvsim_trace_params_default(const int64_t dim[3], mvsim_trace_params* params)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(params != nullptr, "null params");
+    *params = mvsim_trace_params{};
+    params->n_a = 0.0;
+    params->n_b = 1.0;
+    params->ev_threshold = 0.01;
+    params->max_moves = std::min<int64_t>(4 * (dim[0] + dim[1] + dim[2]), (int64_t)1 << 20);
+    params->total_reflection = MVSIM_TRACE_KEEP;
+    params->normalize_dirs = 0;
+    params->constant_value = 1.0;
+    params->sigma[0] = params->sigma[1] = params->sigma[2] = 0.5;
+    params->normalized = 1;
+    return MVSIM_OK;
+}
+
+// everything trace_rays checks, and the weight sum of the injected Gaussians (0 when they are not normalized)
+static int trace_rays_args(mvsim_ctx* ctx, const float* ri_img, const int64_t dim[3], const double* pos3, const double* dir3,
+                           const float* intensity, int64_t n, const mvsim_trace_params* tp, const float* image, const float* weight,
+                           const mvsim_ray_steps* steps, double* sumw)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(tp != nullptr, "null params");
+    MVSIM_CHECK_ARG(std::isfinite(tp->n_a) && std::isfinite(tp->n_b) && std::isfinite(tp->ev_threshold) && std::isfinite(tp->constant_value),
+                    "trace_rays: non-finite parameter");
+    MVSIM_CHECK_ARG(std::isfinite((float)tp->constant_value), "trace_rays: constant_value is not a finite float");
+    MVSIM_CHECK_ARG(tp->ev_threshold >= 0.0, "trace_rays: ev_threshold must be >= 0");
+    MVSIM_CHECK_ARG(tp->max_moves >= 1 && tp->max_moves <= ((int64_t)1 << 20), "trace_rays: max_moves must be 1 .. 2^20");
+    MVSIM_CHECK_ARG(tp->total_reflection == MVSIM_TRACE_KEEP || tp->total_reflection == MVSIM_TRACE_REFLECT,
+                    "trace_rays: unknown total_reflection policy");
+    MVSIM_TRY(aberr_sigma_check(tp->sigma));
+    MVSIM_CHECK_ARG(n >= 0 && n < ((int64_t)1 << 31), "trace_rays: 0 .. 2^31 - 1 rays");
+    MVSIM_CHECK_ARG((pos3 && dir3) || n == 0, "null ray list");
+    MVSIM_TRY(aberr_points_check(pos3, n, 0x1.0p30));
+    for (int64_t i = 0; i < 3 * n; ++i) MVSIM_CHECK_ARG(std::fabs(dir3[i]) < 0x1.0p30, "direction not finite or too long");
+    if (tp->normalize_dirs)
+        for (int64_t i = 0; i < n; ++i)
+            MVSIM_CHECK_ARG(dir3[3 * i] != 0.0 || dir3[3 * i + 1] != 0.0 || dir3[3 * i + 2] != 0.0, "a zero direction cannot be normalised");
+    if (intensity)
+        for (int64_t i = 0; i < n; ++i) MVSIM_CHECK_ARG(std::isfinite(intensity[i]), "intensity not finite");
+    MVSIM_CHECK_ARG(!steps || steps->capacity >= 0, "negative step capacity");
+    MVSIM_CHECK_ARG(ri_img && ((image != nullptr) == (weight != nullptr)), "null volume (image and weight go together)");
+    MVSIM_TRY(set_device(ctx));
+    int size[3];
+    *sumw = tp->normalized ? aberr_sum_weights(tp->sigma, size, nullptr) : 0.0;
+    return MVSIM_OK;
+}
+
+int mvsim_trace_rays_dev(mvsim_ctx* ctx, const float* ri_img, const float* img, const int64_t dim[3], const double* pos3, const double* dir3,
+                         const float* intensity, int64_t n, const mvsim_trace_params* params, float* image, float* weight,
+                         mvsim_ray_steps* steps, double* end_pos3, double* end_dir3, int64_t* n_capped)
+{
+    double sumw;
+    MVSIM_TRY(trace_rays_args(ctx, ri_img, dim, pos3, dir3, intensity, n, params, image, weight, steps, &sumw));
+    return trace_rays_dev(ctx, ri_img, img, dim, pos3, dir3, intensity, n, params, sumw, image, weight, steps, end_pos3, end_dir3, n_capped);
+}
+
+int mvsim_trace_rays(mvsim_ctx* ctx, const float* ri_img, const float* img, const int64_t dim[3], const double* pos3, const double* dir3,
+                     const float* intensity, int64_t n, const mvsim_trace_params* params, float* image, float* weight, mvsim_ray_steps* steps,
+                     double* end_pos3, double* end_dir3, int64_t* n_capped)
+{
+    double sumw;
+    MVSIM_TRY(trace_rays_args(ctx, ri_img, dim, pos3, dir3, intensity, n, params, image, weight, steps, &sumw));
+    const size_t bytes = aberr_bytes(dim);
+    MVSIM_TRY(up(ctx, ctx->vol_b, ri_img, bytes));
+    if (img) MVSIM_TRY(up(ctx, ctx->vol_a, img, bytes));
+    float* out = nullptr;
+    if (image) {
+        MVSIM_TRY(ctx->vol_c.reserve(2 * bytes));
+        out = ctx->vol_c.as<float>();
+        MVSIM_HIP(hipMemsetAsync(out, 0, 2 * bytes, ctx->stream));
+    }
+    MVSIM_TRY(trace_rays_dev(ctx, ctx->vol_b.as<float>(), img ? ctx->vol_a.as<float>() : nullptr, dim, pos3, dir3, intensity, n, params, sumw,
+                             out, out ? out + bytes / sizeof(float) : nullptr, steps, end_pos3, end_dir3, n_capped));
+    if (!image) return MVSIM_OK;
+    MVSIM_HIP(hipMemcpyAsync(image, out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return down(ctx, weight, out + bytes / sizeof(float), bytes);
+}
+
+int mvsim_sandbox_ray_starts(mvsim_ctx* ctx, uint64_t* rnd_state, const int64_t dim[3], int x, int z, int64_t n, double* pos3, double* dir3)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(rnd_state && n >= 0 && ((pos3 && dir3) || n == 0), "null pointer or negative count");
+    MVSIM_TRY(set_device(ctx));
+    MVSIM_TRY(trace_ray_starts(ctx, 1, *rnd_state, dim, x, z, n, pos3, dir3));
+    *rnd_state = jr_jump(*rnd_state & JR_MASK, 4 * (uint64_t)n);        // two nextDouble() per ray, two generator steps each
+    return MVSIM_OK;
+}
+
+int mvsim_grid_ray_starts(mvsim_ctx* ctx, const int64_t dim[3], int z, int spacing, int64_t capacity, double* pos3, double* dir3, int64_t* n_out)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(spacing >= 1, "grid: spacing must be >= 1");
+    MVSIM_CHECK_ARG(n_out != nullptr && capacity >= 0, "null count or negative capacity");
+    const int64_t n = dim[0] / spacing;                                  // x = spacing, 2 spacing, .. <= Nx (RTT:334)
+    *n_out = n;
+    if (capacity == 0 && !pos3 && !dir3) return MVSIM_OK;
+    MVSIM_CHECK_ARG(pos3 && dir3 && capacity >= n, "grid: the ray lists are null or hold fewer rays than the grid has");
+    MVSIM_TRY(set_device(ctx));
+    return trace_ray_starts(ctx, 0, 0, dim, spacing, z, n, pos3, dir3);
+}
+
+int mvsim_draw_simple_image_dev(mvsim_ctx* ctx, float* out, const int64_t dim[3], float low, float high)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(out != nullptr, "null volume");
+    MVSIM_CHECK_ARG(std::isfinite(low) && std::isfinite(high), "drawSimpleImage: non-finite value");
+    MVSIM_TRY(set_device(ctx));
+    return draw_simple_image_dev(ctx, out, dim, low, high);
+}
+
+int mvsim_draw_simple_image(mvsim_ctx* ctx, float* out, const int64_t dim[3], float low, float high)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(out != nullptr, "null volume");
+    MVSIM_CHECK_ARG(std::isfinite(low) && std::isfinite(high), "drawSimpleImage: non-finite value");
+    MVSIM_TRY(set_device(ctx));
+    MVSIM_TRY(ctx->vol_a.reserve(aberr_bytes(dim)));
+    MVSIM_TRY(draw_simple_image_dev(ctx, ctx->vol_a.as<float>(), dim, low, high));
+    return down(ctx, out, ctx->vol_a.p, aberr_bytes(dim));
+}
+
+static int hessian_plane_args(mvsim_ctx* ctx, const float* img, const int64_t dim[3], int z, const float* eigval)
+{
+    MVSIM_TRY(aberr_dim_check(dim));
+    MVSIM_CHECK_ARG(img && eigval, "null pointer");
+    MVSIM_CHECK_ARG(z >= 0 && z < dim[2], "hessian_plane: z outside the volume");
+    return set_device(ctx);
+}
+
+int mvsim_hessian_plane_dev(mvsim_ctx* ctx, const float* img, const int64_t dim[3], int z, float* eigval, float* eigvec)
+{
+    MVSIM_TRY(hessian_plane_args(ctx, img, dim, z, eigval));
+    return aberr_hessian_images_dev(ctx, img, dim, z, 1, eigval, eigvec);
+}
+
+int mvsim_hessian_plane(mvsim_ctx* ctx, const float* img, const int64_t dim[3], int z, float* eigval, float* eigvec)
+{
+    MVSIM_TRY(hessian_plane_args(ctx, img, dim, z, eigval));
+    const size_t pbytes = (size_t)(dim[0] * dim[1]) * sizeof(float);
+    MVSIM_TRY(up(ctx, ctx->vol_a, img, aberr_bytes(dim)));
+    MVSIM_TRY(ctx->vol_b.reserve(4 * pbytes));
+    float* out = ctx->vol_b.as<float>();
+    MVSIM_TRY(aberr_hessian_images_dev(ctx, ctx->vol_a.as<float>(), dim, z, 1, out, eigvec ? out + pbytes / sizeof(float) : nullptr));
+    if (eigvec) MVSIM_HIP(hipMemcpyAsync(eigvec, out + pbytes / sizeof(float), 3 * pbytes, hipMemcpyDeviceToHost, ctx->stream));
+    return down(ctx, eigval, out, pbytes);
 }
 
 }  // extern "C"

@@ -477,7 +477,14 @@ int aberr_ray_starts(mvsim_ctx* ctx, uint64_t state, const int64_t dim[3], int c
                      int rays_per_pixel, int64_t n, double* pos3, double* dir3);
 int aberr_hessian_at_dev(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const double* xyz, int64_t n, double* matrix9,
                          double* eigvec3, double* eigval);
-int aberr_hessian_images_dev(mvsim_ctx* ctx, const float* img, const int64_t dim[3], float* eigval, float* eigvec);
+int aberr_hessian_images_dev(mvsim_ctx* ctx, const float* img, const int64_t dim[3], int z0, int planes, float* eigval, float* eigvec);
+// raytrace.hip
+int64_t trace_rays_per_range(int64_t pair_cap, int64_t max_moves);
+int trace_rays_dev(mvsim_ctx* ctx, const float* ri_img, const float* img, const int64_t dim[3], const double* pos3, const double* dir3,
+                   const float* intensity, int64_t n, const mvsim_trace_params* tp, double sumw, float* image, float* weight,
+                   mvsim_ray_steps* steps, double* end_pos3, double* end_dir3, int64_t* n_capped);
+int trace_ray_starts(mvsim_ctx* ctx, int bundle, uint64_t state, const int64_t dim[3], int x, int z, int64_t n, double* pos3, double* dir3);
+int draw_simple_image_dev(mvsim_ctx* ctx, float* out, const int64_t dim[3], float low, float high);
 int aberr_normalize_dev(mvsim_ctx* ctx, const float* image, const float* weight, int64_t n, float* out);
 int aberr_project_dev(mvsim_ctx* ctx, const float* image, const float* weight, const int64_t dim[3], float* proj);
 int launch_weight_image(hipStream_t s, float* out, const int64_t dim[3]);
