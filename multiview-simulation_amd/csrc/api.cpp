@@ -1,7 +1,7 @@
 // C ABI of libmvsim (include/mvsim.h), part 1: errors, options, context lifetime, memory, the stage operators on device buffers
 // and the statistics / geometry / timing queries.  The per-view pipeline is api_view.cpp, the host-buffer entry points are
 // api_host.cpp, the phantom / bead / refraction-simulator wrappers api_sims.cpp.  Host orchestration only -- every voxel of
-// arithmetic happens in the HIP kernels (kernels.hip, extract.hip, fftconv.hip, stencil.hip).
+// arithmetic happens in the HIP kernels (rotate.hip, kernels.hip, extract.hip, fftconv.hip, stencil.hip).
 #include "api_internal.h"
 
 #include <cstdlib>

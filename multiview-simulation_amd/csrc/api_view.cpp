@@ -307,7 +307,7 @@ static bool views_batchable(const mvsim_ctx* ctx, const int64_t dim[3], const in
         Affine inv;
         axis_rotation_host(dim, 0, p.degrees, m);
         affine_invert_host(m, inv.m);
-        if (!(inv.m[0] == 1.0 && inv.m[1] == 0.0 && inv.m[2] == 0.0 && inv.m[3] == 0.0 && inv.m[4] == 0.0 && inv.m[8] == 0.0)) return false;
+        if (!affine_is_x_rotation(inv)) return false;
     }
     return true;
 }

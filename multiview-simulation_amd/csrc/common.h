@@ -19,6 +19,7 @@
 #include "../../include/mvsim.h"
 #include "extract_plan.h"
 #include "interval_plan.h"
+#include "rotate_dev.h"
 #include "sphere_walk.h"
 
 // Attribution switches (tools/attribute_flags.sh, attribute_valu.sh, attribution_run.sh: builds that compile a part of a kernel's work
@@ -88,9 +89,12 @@ struct DevBuf {
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
-struct Affine {
-    double m[12];
-};
+// struct Affine: rotate_dev.h.  A rotation about x (the only axis SimulateMultiViewDataset.main uses, :557,:570,:591): the
+// inverse model has row 0 = (1,0,0,0) exactly and no x term in rows 1 and 2 -- what every row-walking rotate kernel requires
+inline bool affine_is_x_rotation(const Affine& a)
+{
+    return a.m[0] == 1.0 && a.m[1] == 0.0 && a.m[2] == 0.0 && a.m[3] == 0.0 && a.m[4] == 0.0 && a.m[8] == 0.0;
+}
 
 struct FftPlan {
     int64_t      P[3]      = {0, 0, 0};

@@ -328,9 +328,7 @@ int rotate_attenuate_fftx(mvsim_ctx* ctx, const float* gt, float* rot_or_null, f
     *done = false;
     if (plane_nz) *plane_nz = nullptr;
     if (ctx->opt.fused_fftx == 0) return MVSIM_OK;
-    const bool x_identity = inv.m[0] == 1.0 && inv.m[1] == 0.0 && inv.m[2] == 0.0 && inv.m[3] == 0.0 &&
-                            inv.m[4] == 0.0 && inv.m[8] == 0.0;
-    if (!x_identity) return MVSIM_OK;
+    if (!affine_is_x_rotation(inv)) return MVSIM_OK;
     ConvPlan pl;
     if (!conv_plan(dim, kdim, ctx->opt, &pl)) return MVSIM_OK;
     const int nx = pl.n[0], ny = pl.n[1], nz = pl.n[2], kx = pl.k[0];

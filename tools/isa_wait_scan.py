@@ -52,7 +52,7 @@ def demangle(names):
 
 
 if __name__ == "__main__":
-    files = sys.argv[1:] or [os.path.join(CSRC, f) for f in ("fft_passes.hip", "zconv.hip", "fft_driver.hip", "rotate_fft.hip", "kernels.hip", "extract.hip")]
+    files = sys.argv[1:] or [os.path.join(CSRC, f) for f in ("fft_passes.hip", "zconv.hip", "fft_driver.hip", "rotate_fft.hip", "rotate.hip", "kernels.hip", "extract.hip")]
     for f in files:
         loads, hits = scan(f)
         names = demangle(sorted(hits, key=lambda k: -hits[k]))

@@ -43,5 +43,5 @@ for _ in range(4):
     ctx.simulate_view_dev(d_gt, (nx, ny, nz), psf.copy(), p, d_acq)
 t = ctx.timings()
 n = nx * ny * nz
-print(f"{nx}x{ny}x{nz}, PSF {kx}x{ky}x{kz}, inc {inc}{' ' + ' '.join(sys.argv[8:]) if sys.argv[8:] else ''}: {t['total_ms']:.2f} ms/view = {n / t['total_ms'] / 1e6:.1f} Gvoxel/s  "
-      + " ".join(f"{k}={v:.2f}" for k, v in t.items() if k != "total_ms"))
+print(f"{nx}x{ny}x{nz}, PSF {kx}x{ky}x{kz}, inc {inc}{' ' + ' '.join(sys.argv[8:]) if sys.argv[8:] else ''}: {t['total_ms']:.3f} ms/view = {n / t['total_ms'] / 1e6:.1f} Gvoxel/s  "
+      + " ".join(f"{k}={v:.3f}" for k, v in t.items() if k != "total_ms"))
