@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <unordered_set>
 #include <utility>
 #include <vector>
@@ -403,6 +404,15 @@ struct ExtractOps {               // the operands of one launch_extract
 };
 int launch_extract(hipStream_t s, const ExtractPlan& pl, const ExtractOps& o);
 int launch_resolve(hipStream_t s, const ExtractPlan& pl, const ExtractOps& o);   // the sampler's second launch alone (the fused tail)
+// run-time flags -> a kernel's template arguments (the launchers of extract.hip and extract_interval.hip)
+template <class F> inline void dispatch1(bool a, F&& f)
+{
+    if (a) f(std::true_type{}); else f(std::false_type{});
+}
+template <class F> inline void dispatch2(bool a, bool b, F&& f)
+{
+    dispatch1(a, [&](auto A) { dispatch1(b, [&](auto B) { f(A, B); }); });
+}
 // mvsim_extract_path: the plan of nzo = (dim[2] - 1) / inc + 1 acquired planes as path = {EXTRACT_K_*, segments can refuse, blocks, items
 // per segment}.  index_inc: 0 = inc; qshare: 0 = no work queue, else 1..16 sixteenths.
 void extract_path(const int64_t dim[3], int inc, int index_inc, uint64_t index_offset, bool aligned16, int qshare, int64_t path[4]);

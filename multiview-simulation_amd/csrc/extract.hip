@@ -1,13 +1,43 @@
 // The extract + Poisson stage (gfx950, wave64): extractSlices with adjustImage on the fly and the two-launch Poisson sampler -- the four
 // kernels of phase 1, the resolver, the walk over what full segments refused -- and the one launcher that runs an ExtractPlan
-// (extract_plan.h).  Device arithmetic: poisson_dev.h; design notes: DESIGN.md 4.4.
-#include <type_traits>
+// (extract_plan.h).  The arithmetic of a voxel: poisson_recipe.h; phase 1, its block frame, the group walk and the resolver's loop:
+// poisson_dev.h; design notes: DESIGN.md 4.4.
 #include <vector>
 
 #include "common.h"
 #include "poisson_dev.h"
 
 namespace mvsim {
+
+// Stacked views (vt != null, blockIdx.y = view): the view's operands from the device table, over the kernel's own.  One helper per
+// operand set; without a table the operands stay what the kernel was launched with.
+__device__ __forceinline__ void view_operands(const ExtractView* __restrict__ vt, const float* __restrict__& in, float* __restrict__& out,
+                                              const double* __restrict__& scal, uint32_t& k0, uint32_t& k1, uint32_t& stream)
+{
+    if (vt) { const ExtractView e = vt[blockIdx.y]; in = e.in; out = e.out; scal = e.scal; k0 = e.k0; k1 = e.k1; stream = e.stream; }
+}
+
+__device__ __forceinline__ void view_operands(const ExtractView* __restrict__ vt, const float* __restrict__& in, float* __restrict__& out,
+                                              const double* __restrict__& scal, uint32_t& k0, uint32_t& k1, uint32_t& stream,
+                                              PItem* __restrict__& queue, unsigned int* __restrict__& qcount)
+{
+    if (vt) {
+        const ExtractView e = vt[blockIdx.y];
+        in = e.in; out = e.out; scal = e.scal; k0 = e.k0; k1 = e.k1; stream = e.stream;
+        queue = reinterpret_cast<PItem*>(e.queue); qcount = e.qcount;
+    }
+}
+
+// The ResolveJob set.  QUEUE == false: k_poisson_refused, which reads no queue, does not take the field.
+template <bool QUEUE>
+__device__ __forceinline__ void view_job(const ExtractView* __restrict__ vt, ResolveJob& job)
+{
+    if (vt) {
+        const ExtractView e = vt[blockIdx.y];
+        job.out = e.out; job.qcount = e.qcount; job.k0 = e.k0; job.k1 = e.k1; job.stream = e.stream;
+        if (QUEUE) job.queue = reinterpret_cast<const PItem*>(e.queue);
+    }
+}
 
 // ------------------------------------------------------------------------------------------------
 // extractSlices + adjust + Poisson (SimulateMultiViewDataset.java:195-251, Tools.java:73-86):
@@ -21,7 +51,7 @@ __global__ __launch_bounds__(256) void k_extract(const float* __restrict__ in, f
                                                  uint32_t k0, uint32_t k1, uint32_t stream,
                                                  unsigned long long index_offset, const ExtractView* __restrict__ vt)
 {
-    if (vt) { const ExtractView e = vt[blockIdx.y]; in = e.in; out = e.out; scal = e.scal; k0 = e.k0; k1 = e.k1; stream = e.stream; }
+    view_operands(vt, in, out, scal, k0, k1, stream);
     double corr = 1.0;
     if (ADJUST) corr = scal[1];
     const long long total = plane * nzo;
@@ -32,7 +62,7 @@ __global__ __launch_bounds__(256) void k_extract(const float* __restrict__ in, f
         const long long src = k * inc * plane + i;
         float v = in[src];
         if (ADJUST) v = adjust_one(v, corr, min_value);
-        if (NOISE) v = poisson_counter((double)v * mul, k0, k1, stream, index_offset + (unsigned long long)(k * idx_inc * plane + i));
+        if (NOISE) v = poisson_voxel((double)v * mul, k0, k1, stream, index_offset + (unsigned long long)(k * idx_inc * plane + i));
         out[o] = v;
     }
 }
@@ -46,7 +76,7 @@ __global__ __launch_bounds__(256) void k_extract4(const float* __restrict__ in, 
                                                   uint32_t k0, uint32_t k1, uint32_t stream,
                                                   unsigned long long index_offset, const ExtractView* __restrict__ vt)
 {
-    if (vt) { const ExtractView e = vt[blockIdx.y]; in = e.in; out = e.out; scal = e.scal; k0 = e.k0; k1 = e.k1; stream = e.stream; }
+    view_operands(vt, in, out, scal, k0, k1, stream);
     double corr = 1.0;
     if (ADJUST) corr = scal[1];
     const long long total4 = plane4 * nzo;
@@ -68,9 +98,12 @@ __global__ __launch_bounds__(256) void k_extract4(const float* __restrict__ in, 
             v.z = adjust_one(v.z, corr, min_value);
             v.w = adjust_one(v.w, corr, min_value);
         }
-        if (NOISE)
-            v = poisson_counter4((double)v.x * mul, (double)v.y * mul, (double)v.z * mul, (double)v.w * mul, k0, k1,
-                                 stream, index_offset + 4ull * (unsigned long long)idx4);
+        if (NOISE) {
+            const double lam[4] = {(double)v.x * mul, (double)v.y * mul, (double)v.z * mul, (double)v.w * mul};
+            float cnt[4];
+            poisson_counter4(lam, k0, k1, stream, index_offset + 4ull * (unsigned long long)idx4, cnt);
+            v = make_float4(cnt[0], cnt[1], cnt[2], cnt[3]);
+        }
         out4[o] = v;
     }
 }
@@ -86,7 +119,7 @@ __global__ __launch_bounds__(256) void k_extract4(const float* __restrict__ in, 
 //   k_poisson_resolve: one queue item per lane, looped until resolved; no LDS, no barriers, full occupancy, and
 //                      every lane starts with real work -- the divergent fp64 code (logs, divisions) no longer
 //                      runs once per voxel slot with 1-in-7 lanes active.
-// Same arithmetic per (voxel, attempt) as poisson_counter: bit-identical counts.
+// Same arithmetic per (voxel, attempt) as poisson_voxel: bit-identical counts.
 template <bool ADJUST, bool CHECKED>
 __global__ __launch_bounds__(256) void k_extract4_noise2(const float* __restrict__ in, float* __restrict__ out,
                                                          long long plane4, long long nzo, int inc, int idx_inc,
@@ -96,20 +129,13 @@ __global__ __launch_bounds__(256) void k_extract4_noise2(const float* __restrict
                                                          unsigned int* __restrict__ qcount, unsigned int segcap,
                                                          const ExtractView* __restrict__ vt)
 {
-    if (vt) {
-        const ExtractView e = vt[blockIdx.y];
-        in = e.in; out = e.out; scal = e.scal; k0 = e.k0; k1 = e.k1; stream = e.stream;
-        queue = reinterpret_cast<PItem*>(e.queue); qcount = e.qcount;
-    }
+    view_operands(vt, in, out, scal, k0, k1, stream, queue, qcount);
     __shared__ unsigned long long qctr;
     __shared__ unsigned int qovf[2];
     __shared__ P1Scratch scratch[4];
-    if (threadIdx.x == 0) { qctr = 0ull; qovf[0] = 0u; qovf[1] = 0u; }
-    __syncthreads();
+    p1_frame_open(&qctr, qovf);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    P1Args pa;
-    pa.mul = mul; pa.mulf = (float)mul; pa.k0 = k0; pa.k1 = k1; pa.stream = stream;
-    pa.seg = queue + (unsigned long long)blockIdx.x * segcap; pa.segcap = segcap; pa.ctr = &qctr; pa.ovf = qovf;
+    const P1Args pa = p1_frame_args(mul, k0, k1, stream, queue, segcap, &qctr, qovf);
     double corr = 1.0;
     if (ADJUST) corr = scal[1];
     const long long total4 = plane4 * nzo;
@@ -143,19 +169,13 @@ __global__ __launch_bounds__(256) void k_extract4_noise2(const float* __restrict
         poisson_phase1<CHECKED>(vv, valid, index_offset + 4ull * (unsigned long long)idx4, 4ull * (unsigned long long)o, pa, &scratch[wave], lane, ov);
         if (valid) out4[o] = make_float4(ov[0], ov[1], ov[2], ov[3]);
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        p1_publish(qcount + (size_t)QCOUNT_WORDS * blockIdx.x, qctr, qovf);
-        if (blockIdx.x == 0) p1_publish_header(qcount, gridDim.x, segcap);
-    }
+    p1_frame_close<true>(qcount, &qctr, qovf, segcap);
 }
 
 // The same two-launch sampler for planes that are no multiple of four voxels (the reference's own 289^3 run: 83 521 voxels per
-// plane) or buffers that are not 16-byte aligned.  Philox groups are four consecutive voxels of the SOURCE index (poisson_dev.h),
-// and a plane then starts anywhere inside a group: a lane takes one group of one acquired plane -- up to four voxels, the ones
-// that fall inside the plane (scalar loads and stores under a mask; the others enter phase 1 as zeros, which it ignores) --, and the
-// 64 lanes of a wave take 64 consecutive groups of the SAME plane, so that a wave's outputs stay consecutive (what phase 1's pair
-// compaction assumes).  Same arithmetic per (voxel, attempt) as every other form: bit-identical counts.
+// plane) or buffers that are not 16-byte aligned: the group-by-group walk of poisson_dev.h (group_walk_phase1) over contiguous planes
+// (scalar loads and stores under a mask; the components outside the plane enter phase 1 as zeros, which it ignores).  Same arithmetic
+// per (voxel, attempt) as every other form: bit-identical counts.
 template <bool ADJUST, bool CHECKED>
 __global__ __launch_bounds__(256) void k_extract_noise2_any(const float* __restrict__ in, float* __restrict__ out,
                                                             long long plane, long long nzo, int inc, int idx_inc,
@@ -165,69 +185,22 @@ __global__ __launch_bounds__(256) void k_extract_noise2_any(const float* __restr
                                                             unsigned int* __restrict__ qcount, unsigned int segcap,
                                                             long long slots_per_plane, const ExtractView* __restrict__ vt)
 {
-    if (vt) {
-        const ExtractView e = vt[blockIdx.y];
-        in = e.in; out = e.out; scal = e.scal; k0 = e.k0; k1 = e.k1; stream = e.stream;
-        queue = reinterpret_cast<PItem*>(e.queue); qcount = e.qcount;
-    }
+    view_operands(vt, in, out, scal, k0, k1, stream, queue, qcount);
     __shared__ unsigned long long qctr;
     __shared__ unsigned int qovf[2];
     __shared__ P1Scratch scratch[4];
-    if (threadIdx.x == 0) { qctr = 0ull; qovf[0] = 0u; qovf[1] = 0u; }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    P1Args pa;
-    pa.mul = mul; pa.mulf = (float)mul; pa.k0 = k0; pa.k1 = k1; pa.stream = stream;
-    pa.seg = queue + (unsigned long long)blockIdx.x * segcap; pa.segcap = segcap; pa.ctr = &qctr; pa.ovf = qovf;
-    double corr = 1.0;
-    if (ADJUST) corr = scal[1];
-    const long long slots = slots_per_plane * nzo;        // wave slots: 64 groups each
-    for (long long sl = (long long)blockIdx.x * 4 + wave; sl < slots; sl += (long long)gridDim.x * 4) {
-        const long long k = sl / slots_per_plane, jb = sl - k * slots_per_plane;
-        const unsigned long long ibase = index_offset + (unsigned long long)(k * idx_inc) * (unsigned long long)plane;   // RNG index of the plane's voxel 0
-        const unsigned long long g = (ibase >> 2) + (unsigned long long)(jb * 64 + lane);      // this lane's Philox group
-        const long long i0 = (long long)(4ull * g - ibase);                                   // its first voxel inside the plane (may be < 0)
-        const float* __restrict__ src = in + k * inc * plane;
-        float vv[4];
-        bool any = false;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const long long i = i0 + c;
-            const bool ok = i >= 0 && i < plane;
-            float v = 0.f;
-            if (ok) {
-                v = src[i];
-                if (ADJUST) v = adjust_one(v, corr, min_value);
-            }
-            vv[c] = ok ? v : 0.f;
-            any |= ok;
-        }
-        float ov[4];
-        // (output position of component 0; negative for a plane's first group when the plane starts inside it -- the valid components
-        // land at non-negative positions all the same, in 64-bit wrap-around arithmetic)
-        poisson_phase1<CHECKED>(vv, any, 4ull * g, (unsigned long long)(k * plane + i0), pa, &scratch[wave], lane, ov);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const long long i = i0 + c;
-            if (i >= 0 && i < plane) out[k * plane + i] = ov[c];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        p1_publish(qcount + (size_t)QCOUNT_WORDS * blockIdx.x, qctr, qovf);
-        if (blockIdx.x == 0) p1_publish_header(qcount, gridDim.x, segcap);
-    }
+    p1_frame_open(&qctr, qovf);
+    const P1Args pa = p1_frame_args(mul, k0, k1, stream, queue, segcap, &qctr, qovf);
+    const FetchContiguous<ADJUST> fetch{in, inc, ADJUST ? scal[1] : 1.0, min_value};
+    group_walk_phase1<CHECKED>(fetch, out, plane, nzo, idx_inc, index_offset, slots_per_plane, pa, scratch);
+    p1_frame_close<true>(qcount, &qctr, qovf, segcap);
 }
 
 // One block per queue segment (same grid as k_extract4_noise2; the grid-stride walk of that kernel spreads the
 // bright voxels evenly over the segments).
 __global__ __launch_bounds__(256) void k_poisson_resolve(ResolveJob job, const ExtractView* __restrict__ vt)
 {
-    if (vt) {
-        const ExtractView e = vt[blockIdx.y];
-        job.out = e.out; job.queue = reinterpret_cast<const PItem*>(e.queue); job.qcount = e.qcount;
-        job.k0 = e.k0; job.k1 = e.k1; job.stream = e.stream;
-    }
+    view_job<true>(vt, job);
     __shared__ unsigned int ticket;
     __shared__ double tab[RESOLVE_TAB];
     resolve_segment_body(job, (long long)blockIdx.x, (int)threadIdx.x, &ticket, tab);
@@ -241,10 +214,7 @@ constexpr unsigned int REFUSED_LIST = 4096;                // positions the bloc
 __global__ __launch_bounds__(256) void k_poisson_refused(ResolveJob job, int segments, unsigned int full_items, unsigned int* hint,
                                                          const ExtractView* __restrict__ vt)
 {
-    if (vt) {
-        const ExtractView e = vt[blockIdx.y];
-        job.out = e.out; job.qcount = e.qcount; job.k0 = e.k0; job.k1 = e.k1; job.stream = e.stream;
-    }
+    view_job<false>(vt, job);                                         // (its queue is not read here)
     if (job.qcount[QCOUNT_HEADER + 2] == 0u) return;                 // no block of this view was refused anything (the resolver's word)
     __shared__ unsigned int list[REFUSED_LIST];
     __shared__ unsigned int count;
@@ -258,7 +228,7 @@ __global__ __launch_bounds__(256) void k_poisson_refused(ResolveJob job, int seg
         const unsigned int m = count;
         for (unsigned int i = (unsigned int)t; i < m; i += 256u) {
             const unsigned int o = list[i];
-            job.out[o] = resolve_in_place(-job.out[o], job, resolve_index_of(job, o));
+            job.out[o] = poisson_voxel((double)-job.out[o] * job.mul, job.k0, job.k1, job.stream, resolve_index_of(job, o));
         }
         __syncthreads();                                              // every lane has read `count` and its entries
         if (t == 0) count = 0u;
@@ -281,13 +251,6 @@ __global__ __launch_bounds__(256) void k_poisson_refused(ResolveJob job, int seg
     flush();
     // what a context on the automatic share builds its next queue with (api.cpp: queue_mode_next reads the word without synchronising)
     if (t == 0 && hint && need != 0u) __hip_atomic_fetch_max(hint, need > 16u ? 16u : need, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// two run-time flags -> a kernel's two template arguments
-template <class F> static void dispatch2(bool a, bool b, F&& f)
-{
-    auto second = [&](auto A) { if (b) f(A, std::true_type{}); else f(A, std::false_type{}); };
-    if (a) second(std::true_type{}); else second(std::false_type{});
 }
 
 // The second launch of the sampler: one block per queue segment, and behind it -- where the segments can refuse (pl.checked) -- the walk

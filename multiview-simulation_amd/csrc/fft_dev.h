@@ -155,13 +155,6 @@ template <> __device__ __forceinline__ void dft<9>(float2* u)
     }
 }
 
-// Tools.adjustImage on one voxel: (float)(v * corr), then + minValue as a second float rounding (Tools.java:150-155)
-__device__ __forceinline__ float adjust_one_f(float v, double corr, float min_value)
-{
-    const float t = (float)((double)v * corr);
-    return t + min_value;
-}
-
 // ---------------------------------------------------------------------------------- Stockham passes in LDS
 // Compiler-level ordering point for LDS traffic of ONE wave (the hardware executes a wave's DS
 // operations in issue order, so no s_barrier is needed between a wave's own writes and reads).

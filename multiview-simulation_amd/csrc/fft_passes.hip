@@ -609,7 +609,7 @@ __global__ __launch_bounds__(CfgX<PLAN::len>::T) void k_fft_x_c2r(const float2* 
     unsigned int* qovf = reinterpret_cast<unsigned int*>(red + 33);
     constexpr size_t SCR_OFF = ((size_t)(NR * LP + M) * sizeof(float2) + 34 * sizeof(double) + 15) & ~(size_t)15;
     P1Scratch* scratch = reinterpret_cast<P1Scratch*>(reinterpret_cast<char*>(lds) + SCR_OFF);
-    if (FUSE && tid == 0) { *qctr = 0ull; qovf[0] = 0u; qovf[1] = 0u; }
+    if (FUSE) p1_frame_zero(qctr, qovf);                                     // (the barrier behind the twiddle table comes before any append)
     // Every global load of the wave -- its share of the transform's twiddle table, the plane flags of its rows, the rows themselves and
     // the post-processing twiddles of its items -- is requested before anything waits: requested where they are used, they made a chain
     // of five dependent round trips to the caches in a block that lives for a few microseconds.
@@ -730,9 +730,7 @@ __global__ __launch_bounds__(CfgX<PLAN::len>::T) void k_fft_x_c2r(const float2* 
     if (FUSE) {
         // nx % 4 == 0 and 16-byte aligned outputs are guaranteed by the launcher
         const double corr = f.scal[1];
-        P1Args pa;
-        pa.mul = f.mul; pa.mulf = (float)f.mul; pa.k0 = f.k0; pa.k1 = f.k1; pa.stream = f.stream;
-        pa.seg = f.queue + (unsigned long long)blockIdx.x * f.segcap; pa.segcap = f.segcap; pa.ctr = qctr; pa.ovf = qovf;
+        const P1Args pa = p1_frame_args(f.mul, f.k0, f.k1, f.stream, f.queue, f.segcap, qctr, qovf);
         const int nq4 = nx >> 2;
         for (int j = 0; j < LW; ++j) {
             const long long row = row0 + j;
@@ -750,10 +748,10 @@ __global__ __launch_bounds__(CfgX<PLAN::len>::T) void k_fft_x_c2r(const float2* 
                 if (valid) {
                     const float2 z0 = zrow[2 * q];
                     const float2 z1 = (2 * q + 1 < M) ? zrow[2 * q + 1] : make_float2(0.f, 0.f);
-                    vv[0] = adjust_one_f(z0.x * scale, corr, f.min_value);
-                    vv[1] = adjust_one_f(-z0.y * scale, corr, f.min_value);
-                    vv[2] = adjust_one_f(z1.x * scale, corr, f.min_value);
-                    vv[3] = adjust_one_f(-z1.y * scale, corr, f.min_value);
+                    vv[0] = adjust_one(z0.x * scale, corr, f.min_value);
+                    vv[1] = adjust_one(-z0.y * scale, corr, f.min_value);
+                    vv[2] = adjust_one(z1.x * scale, corr, f.min_value);
+                    vv[3] = adjust_one(-z1.y * scale, corr, f.min_value);
                     if (f.con) *reinterpret_cast<float4*>(f.con + row * nx + 4 * q) = make_float4(vv[0], vv[1], vv[2], vv[3]);
                 }
                 if (acquired) {
@@ -765,8 +763,7 @@ __global__ __launch_bounds__(CfgX<PLAN::len>::T) void k_fft_x_c2r(const float2* 
                 }
             }
         }
-        __syncthreads();
-        if (tid == 0 && f.noise) p1_publish(f.qcount + (size_t)QCOUNT_WORDS * blockIdx.x, *qctr, qovf);   // no queue without noise (qcount is null then)
+        p1_frame_close<false>(f.qcount, qctr, qovf, f.segcap, f.noise);          // no header by design; no queue without noise (qcount is null then)
         return;
     }
     double acc = 0.0;

@@ -2,7 +2,7 @@
 // acquisitions, makeIsotropic, weight image, weights (rotate and attenuate: rotate.hip; slice extraction + Poisson:
 // extract.hip).  All are HBM-bound; design notes and algorithmic bytes per voxel are in DESIGN.md.
 #include "common.h"
-#include "poisson_dev.h"
+#include "poisson_recipe.h"
 
 namespace mvsim {
 

@@ -1,416 +1,16 @@
-// Counter-based Poisson sampling for the extractSlices / poissonProcess stage
-// (replaces uncommons/PoissonGenerator.java:95-109 + java.util.Random, which cost ~lambda+1
-// Math.log calls per voxel on one strictly sequential stream).
-//
-// Generator : Philox4x32-10, key = 64-bit seed
-// Sampler   : lambda < 10  -> inversion by sequential search on a 32-bit uniform; the 4 voxels of
-//                             group index>>2 share ONE Philox block, ctr = (index>>2, stream, 0)
-//             lambda >= 10 -> Hoermann's PTRS transformed rejection on 32-bit uniforms; attempt 0 of the
-//                             voxel pair index>>1 shares one block, ctr = (index>>1, stream, 1); retries
-//                             take two attempts per block, ctr = (index, stream, 2 + (a-1)/2)
-// All accept/reject arithmetic is IEEE +,-,*,/,sqrt,fma on doubles plus the bit-defined log/exp
-// below (built with -ffp-contract=off), so a CPU implementation of the same recipe gives
-// identical counts.
+// The queue machinery of the two-launch Poisson sampler (device side): phase 1 (what a wave settles at once and what it queues), the
+// block frame around it, the group-by-group walk of planes that are no multiple of four voxels, the resolver's segment loop and the
+// walk over what full segments refused.  The arithmetic of one voxel -- generator, regimes, accept/reject, poisson_voxel -- is
+// poisson_recipe.h; the kernels are extract.hip, extract_interval.hip and pass E of fft_passes.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
 #include "extract_plan.h"
+#include "poisson_recipe.h"
 
 namespace mvsim {
-
-struct Philox4 {
-    uint32_t x, y, z, w;
-};
-
-__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                                 uint32_t k0, uint32_t k1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        // one 32x32 -> 64 multiply per product (v_mad_u64_u32) instead of separate mul_hi / mul_lo
-        const uint64_t p0 = (uint64_t)0xD2511F53u * (uint64_t)c0;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * (uint64_t)c2;
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c1 ^ k0;
-        const uint32_t n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return Philox4{c0, c1, c2, c3};
-}
-
-__device__ __forceinline__ double u53(uint32_t a, uint32_t b)
-{
-    return (double)(((uint64_t)(a >> 5) << 26) | (uint64_t)(b >> 6)) * 0x1.0p-53;
-}
-
-// log(x), x > 0: fdlibm-style reduction to [sqrt(1/2), sqrt(2)), degree-14 odd polynomial.
-__device__ __forceinline__ double det_log(double x)
-{
-    if (!(x > 0.0)) return -1.0e300;
-    uint64_t u = (uint64_t)__double_as_longlong(x);
-    int e = (int)(u >> 52) - 1023;
-    if (e == -1023) {
-        x = x * 0x1.0p54;
-        u = (uint64_t)__double_as_longlong(x);
-        e = (int)(u >> 52) - 1023 - 54;
-    }
-    u = (u & 0x000FFFFFFFFFFFFFULL) | 0x3FF0000000000000ULL;
-    double m = __longlong_as_double((long long)u);
-    if (m > 1.4142135623730951) { m = m * 0.5; e += 1; }
-    const double f = m - 1.0;
-    const double s = f / (2.0 + f);
-    const double z = s * s;
-    const double w = z * z;
-    const double t1 = w * (3.999999999940941908e-01 + w * (2.222219843214978396e-01 + w * 1.531383769920937332e-01));
-    const double t2 = z * (6.666666666666735130e-01 + w * (2.857142874366239149e-01 + w * (1.818357216161805012e-01 + w * 1.479819860511658591e-01)));
-    const double R = t2 + t1;
-    const double hfsq = 0.5 * f * f;
-    const double dk = (double)e;
-    return dk * 6.93147180369123816490e-01 - ((hfsq - (s * (hfsq + R) + dk * 1.90821492927058770002e-10)) - f);
-}
-
-// exp(-lambda), 0 < lambda < 10, division free: 2^k * sum_{n<=13} r^n / n!  (Horner, explicit FMAs)
-__device__ __forceinline__ double det_exp_neg(double lambda)
-{
-    const double x = -lambda;
-    const double kf = floor(x * 1.44269504088896338700e+00 + 0.5);
-    const double r = (x - kf * 6.93147180369123816490e-01) - kf * 1.90821492927058770002e-10;
-    double p = 1.0 / 6227020800.0;
-    p = fma(p, r, 1.0 / 479001600.0);
-    p = fma(p, r, 1.0 / 39916800.0);
-    p = fma(p, r, 1.0 / 3628800.0);
-    p = fma(p, r, 1.0 / 362880.0);
-    p = fma(p, r, 1.0 / 40320.0);
-    p = fma(p, r, 1.0 / 5040.0);
-    p = fma(p, r, 1.0 / 720.0);
-    p = fma(p, r, 1.0 / 120.0);
-    p = fma(p, r, 1.0 / 24.0);
-    p = fma(p, r, 1.0 / 6.0);
-    p = fma(p, r, 0.5);
-    p = fma(p, r, 1.0);
-    p = fma(p, r, 1.0);
-    return p * __longlong_as_double((long long)((uint64_t)((int)kf + 1023) << 52));
-}
-
-// log(k!) : table to 16, Stirling series beyond.
-__device__ const double kLogFact[17] = {
-    0.0, 0.0, 0.6931471805599453, 1.791759469228055, 3.1780538303479458, 4.787491742782046, 6.579251212010101,
-    8.525161361065415, 10.60460290274525, 12.801827480081469, 15.104412573075516, 17.502307845873887,
-    19.987214495661885, 22.552163853123425, 25.19122118273868, 27.89927138384089, 30.671860106080672};
-
-// (`lf`: where the table is read from -- the resolver keeps a copy in LDS: a dependent GLOBAL load inside its divergent attempt costs every
-// lane of the wave a trip to the cache)
-__device__ __forceinline__ double det_lgamma_int(long long k, const double* lf = kLogFact)
-{
-    if (k <= 16) return lf[k < 0 ? 0 : k];
-    const double x = (double)k + 1.0;
-    const double ix = 1.0 / x;
-    const double ix2 = ix * ix;
-    const double ser = ix * (8.3333333333333333e-02 + ix2 * (-2.7777777777777778e-03 + ix2 * (7.9365079365079365e-04 + ix2 * -5.9523809523809524e-04)));
-    return ((x - 0.5) * det_log(x) - x) + 0.9189385332046727 + ser;
-}
-
-// 1/k, k = 0..63 (k = 0 unused), correctly rounded at compile time
-__device__ const double kInvK[64] = {
-    0.0,       1.0 / 1,  1.0 / 2,  1.0 / 3,  1.0 / 4,  1.0 / 5,  1.0 / 6,  1.0 / 7,  1.0 / 8,  1.0 / 9,  1.0 / 10,
-    1.0 / 11,  1.0 / 12, 1.0 / 13, 1.0 / 14, 1.0 / 15, 1.0 / 16, 1.0 / 17, 1.0 / 18, 1.0 / 19, 1.0 / 20, 1.0 / 21,
-    1.0 / 22,  1.0 / 23, 1.0 / 24, 1.0 / 25, 1.0 / 26, 1.0 / 27, 1.0 / 28, 1.0 / 29, 1.0 / 30, 1.0 / 31, 1.0 / 32,
-    1.0 / 33,  1.0 / 34, 1.0 / 35, 1.0 / 36, 1.0 / 37, 1.0 / 38, 1.0 / 39, 1.0 / 40, 1.0 / 41, 1.0 / 42, 1.0 / 43,
-    1.0 / 44,  1.0 / 45, 1.0 / 46, 1.0 / 47, 1.0 / 48, 1.0 / 49, 1.0 / 50, 1.0 / 51, 1.0 / 52, 1.0 / 53, 1.0 / 54,
-    1.0 / 55,  1.0 / 56, 1.0 / 57, 1.0 / 58, 1.0 / 59, 1.0 / 60, 1.0 / 61, 1.0 / 62, 1.0 / 63};
-
-// Inversion by sequential search for 0 < lambda < 10 on the 32-bit word `w` of the group block.
-__device__ __forceinline__ float poisson_small(double lambda, uint32_t w, const double* invk = kInvK)
-{
-    const double u = ((double)w + 0.5) * 0x1.0p-32;
-    double p = det_exp_neg(lambda);
-    double F = p;
-    int k = 0;
-    while (u >= F && k < 63) {
-        k += 1;
-        p = (p * lambda) * invk[k];
-        F = F + p;
-    }
-    return (float)k;
-}
-
-__device__ __forceinline__ double u32_open(uint32_t w) { return ((double)w + 0.5) * 0x1.0p-32; }
-
-// An integer-valued double (a floor: the count PTRS proposes) as float.  The recipe's (float)(long long)d rounds that integer to the nearest
-// float, and so does (float)d -- the same value for every |d| < 2^63 -- in ONE conversion; f64 -> i64 -> f32 has no instruction of its own
-// and costs ~16 per value (two per pair in every PTRS trip of phase 1: 4 % of its vector instructions).
-__device__ __forceinline__ float count_as_float(double d) { return (float)d; }
-
-constexpr uint32_t kPtrsMaxAttempts = 60000u;   // cap (never reached in practice: p ~ 0.1^k); then floor(lambda)
-
-// ---- Hoermann PTRS for lambda >= 10 on 32-bit uniforms, split into pieces so that the one-voxel and the
-// four-voxel drivers execute exactly the same arithmetic.
-struct PtrsSetup {
-    double b, a, bm2, vrq, bm34, ianum;
-};
-
-__device__ __forceinline__ PtrsSetup ptrs_setup(double lambda)
-{
-    PtrsSetup s;
-    const double slam = sqrt(lambda);
-    s.b = 0.931 + 2.53 * slam;
-    s.a = -0.059 + 0.02483 * s.b;
-    s.bm2 = s.b - 2.0;
-    s.vrq = 0.9277 * s.bm2 - 3.6224;        // V <= vr  <=>  V*(b-2) <= 0.9277*(b-2) - 3.6224
-    s.bm34 = s.b - 3.4;
-    s.ianum = 1.1239 * s.bm34 + 1.1328;      // invalpha = ianum / bm34
-    return s;
-}
-
-// One attempt's squeeze.  Returns 0: accepted (kd is the sample), 1: rejected, 2: needs the exact test.
-__device__ __forceinline__ int ptrs_fast(const PtrsSetup& s, double lambda, uint32_t w0, uint32_t w1, double& us,
-                                         double& V, double& kd)
-{
-    const double U = u32_open(w0) - 0.5;
-    V = u32_open(w1);
-    us = 0.5 - fabs(U);
-    kd = floor((2.0 * s.a / us + s.b) * U + lambda + 0.43);
-    if (us >= 0.07 && V * s.bm2 <= s.vrq) return 0;
-    if (kd < 0.0 || (us < 0.013 && V > us)) return 1;
-    return 2;
-}
-
-// The exact acceptance test of one attempt.
-__device__ __forceinline__ bool ptrs_exact(const PtrsSetup& s, double lambda, double us, double V, double kd,
-                                           double& loglam, bool& have_loglam, const double* lf = kLogFact)
-{
-    const double us2 = us * us;
-    const double lhs = det_log((V * us2 * s.ianum) / (s.bm34 * (s.a + s.b * us2)));
-    if (!have_loglam) { loglam = det_log(lambda); have_loglam = true; }
-    const double rhs = (-lambda + kd * loglam) - det_lgamma_int((long long)kd, lf);
-    return lhs <= rhs;
-}
-
-// Retry attempts a >= 1 until accepted: ctr = (index, stream, 2 + (a-1)/2), two attempts per block.
-__device__ __forceinline__ double ptrs_retry(const PtrsSetup& s, double lambda, double& loglam, bool& have_loglam,
-                                             uint32_t k0, uint32_t k1, uint32_t stream, uint64_t index)
-{
-    const uint32_t c0 = (uint32_t)index, c1 = (uint32_t)(index >> 32);
-    Philox4 r = Philox4{0u, 0u, 0u, 0u};
-    for (uint32_t attempt = 1; attempt < kPtrsMaxAttempts; ++attempt) {
-        uint32_t w0, w1;
-        if (((attempt - 1u) & 1u) == 0u) {
-            r = philox4x32_10(c0, c1, stream, 2u + (attempt - 1u) / 2u, k0, k1);
-            w0 = r.x; w1 = r.y;
-        } else {
-            w0 = r.z; w1 = r.w;
-        }
-        double us, V, kd;
-        const int st = ptrs_fast(s, lambda, w0, w1, us, V, kd);
-        if (st == 0) return kd;
-        if (st == 2 && ptrs_exact(s, lambda, us, V, kd, loglam, have_loglam)) return kd;
-    }
-    return lambda;
-}
-
-// fp32 screening of the exact test.  D = lhs - rhs is re-derived in a cancellation-free form (valid for k >= 16,
-// Stirling branch):  with t = (k+1-lambda)/lambda,
-//     rhs = lambda*g(t) + log1p(t) - log(k+1)/2 - log(2 pi)/2 - ser(k+1),   g(t) = t - (1+t) log1p(t) = -t^2/2 + t^3/6 - ...
-// so every term is O(1..50) and single precision is accurate to ~1e-5 absolute.  Returns +1 (surely accept),
-// -1 (surely reject) or 0 (too close to call: run the bit-defined fp64 test).  Pure optimisation: whenever it
-// answers, the answer equals the fp64 decision (margin >= 100x the error bound), so counts are unchanged.
-// The promise needs the fp64 test itself to be that accurate: its rhs sums terms of magnitude ~lambda log(lambda), so its own rounding
-// grows like ~4 * 2^-53 * lambda log(lambda) -- 7e-8 at lambda = 1e7 (the margin to eps stays ~300x), but 1e-5 at 1e9 and 1e-2 at 1e12,
-// where the screen's cancellation-free D and the fp64 decision part.  Above kScreenMaxLambda the fp64 test always decides.
-constexpr double kScreenMaxLambda = 1.0e7;
-__device__ __forceinline__ int ptrs_screen(const PtrsSetup& s, double lambda, double us, double V, double kd, const double* lf = kLogFact)
-{
-    if (!(lambda < kScreenMaxLambda)) return 0;
-    const float lam = (float)lambda;
-    if (kd <= 16.0) {
-        // table branch of log(k!): -lambda + k log(lambda) - log(k!) has terms of magnitude <= ~100 here
-        // (lambda < ~60 for such k to be proposed at all), so single precision is good to ~1e-5 absolute
-        if (lambda > 64.0) return 0;
-        const float usq = (float)us * (float)us;
-        const float q0 = ((float)V * usq * (float)s.ianum) / ((float)s.bm34 * ((float)s.a + (float)s.b * usq));
-        const float kf = (float)kd;
-        const float ll = __logf(lam);
-        const float d0 = __logf(q0) - ((kf * ll - lam) - (float)lf[(int)kd]);
-        const float e0 = 1.0e-4f + 4.0e-6f * (kf * ll + lam);
-        return d0 < -e0 ? 1 : (d0 > e0 ? -1 : 0);
-    }
-    const float x = (float)kd + 1.0f;
-    const float t = (float)((kd + 1.0 - lambda) / lambda);          // formed in double: no cancellation error
-    const float usf = (float)us;
-    const float us2 = usf * usf;
-    const float q = ((float)V * us2 * (float)s.ianum) / ((float)s.bm34 * ((float)s.a + (float)s.b * us2));
-    const float lhs = __logf(q);
-    float lg;                                                         // lambda * g(t) + log1p(t)
-    if (fabsf(t) < 0.25f) {
-        // g(t) = sum_{n>=2} (-1)^(n-1) t^n / (n (n-1));  log1p(t) = sum_{n>=1} (-1)^(n-1) t^n / n
-        float g = 1.0f / 156.0f;                                      // n = 13
-        g = fmaf(g, -t, 1.0f / 132.0f);
-        g = fmaf(g, -t, 1.0f / 110.0f);
-        g = fmaf(g, -t, 1.0f / 90.0f);
-        g = fmaf(g, -t, 1.0f / 72.0f);
-        g = fmaf(g, -t, 1.0f / 56.0f);
-        g = fmaf(g, -t, 1.0f / 42.0f);
-        g = fmaf(g, -t, 1.0f / 30.0f);
-        g = fmaf(g, -t, 1.0f / 20.0f);
-        g = fmaf(g, -t, 1.0f / 12.0f);
-        g = fmaf(g, -t, 1.0f / 6.0f);
-        g = fmaf(g, -t, 1.0f / 2.0f);
-        g = -g * t * t;
-        lg = lam * g + __logf(1.0f + t);
-    } else {
-        const float l1p = __logf(1.0f + t);
-        lg = lam * (t - (1.0f + t) * l1p) + l1p;
-    }
-    const float ix = 1.0f / x;
-    const float ix2 = ix * ix;
-    const float ser = ix * (8.3333333e-02f + ix2 * (-2.7777778e-03f + ix2 * 7.9365079e-04f));
-    const float lx = __logf(x);
-    const float rhs = lg - 0.5f * lx - 0.9189385f - ser;
-    const float d = lhs - rhs;
-    // error budget: each term carries <= ~3 ulp of single precision relative to its own magnitude (q: 5 roundings,
-    // series: fma chain, v_log_f32: 1 ulp), i.e. <= 4e-7 * (|lhs| + |lg| + lx + 1); the margin below is >= 10x that.
-    const float eps = 2.0e-5f + 4.0e-6f * (fabsf(lhs) + fabsf(lg) + lx);
-    if (d < -eps) return 1;
-    if (d > eps) return -1;
-    return 0;
-}
-
-// One attempt of one voxel from its two random words (used by the block-level work queue of
-// k_extract4_noise): returns true when the voxel is resolved.
-__device__ __forceinline__ bool ptrs_step_words(double lambda, uint32_t w0, uint32_t w1, float& res, const double* lf = kLogFact)
-{
-    const PtrsSetup s = ptrs_setup(lambda);
-    double us, V, kd;
-    const int st = ptrs_fast(s, lambda, w0, w1, us, V, kd);
-    if (st == 1) return false;
-#ifndef MVSIM_EXP_NOEXACT
-    if (st == 2) {
-        const int sc = ptrs_screen(s, lambda, us, V, kd, lf);
-        if (sc < 0) return false;
-        if (sc == 0) {
-            double loglam = 0.0;
-            bool have = false;
-            if (!ptrs_exact(s, lambda, us, V, kd, loglam, have, lf)) return false;
-        }
-    }
-#endif
-    res = count_as_float(kd);
-    return true;
-}
-
-// Random words of retry attempt a >= 1 of voxel `index`.
-__device__ __forceinline__ void ptrs_retry_words(uint64_t index, uint32_t attempt, uint32_t k0, uint32_t k1, uint32_t stream,
-                                                 uint32_t& w0, uint32_t& w1)
-{
-    const Philox4 r = philox4x32_10((uint32_t)index, (uint32_t)(index >> 32), stream, 2u + (attempt - 1u) / 2u, k0, k1);
-    const bool second = ((attempt - 1u) & 1u) != 0u;
-    w0 = second ? r.z : r.x;
-    w1 = second ? r.w : r.y;
-}
-
-// (w0, w1) are the attempt-0 words, taken by the caller from the block shared by the voxel pair index>>1.
-__device__ __forceinline__ float poisson_ptrs(double lambda, uint32_t w0, uint32_t w1, uint32_t k0, uint32_t k1,
-                                              uint32_t stream, uint64_t index)
-{
-    const PtrsSetup s = ptrs_setup(lambda);
-    double loglam = 0.0;
-    bool have_loglam = false;
-    double us, V, kd;
-    const int st = ptrs_fast(s, lambda, w0, w1, us, V, kd);
-    if (st == 0) return (float)(long long)kd;
-    if (st == 2 && ptrs_exact(s, lambda, us, V, kd, loglam, have_loglam)) return (float)(long long)kd;
-    return (float)(long long)ptrs_retry(s, lambda, loglam, have_loglam, k0, k1, stream, index);
-}
-
-// Counter sampler v3 for one voxel (generic path: recomputes the shared blocks of index>>2 / index>>1).
-// lambda <= 0 or NaN -> 0 (the reference's loop does not terminate there; documented deviation Q9).
-__device__ __forceinline__ float poisson_counter(double lambda, uint32_t k0, uint32_t k1, uint32_t stream,
-                                                 uint64_t index)
-{
-    if (!(lambda > 0.0)) return 0.0f;
-    if (lambda < 10.0) {
-        const uint64_t g = index >> 2;
-        const Philox4 r = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), stream, 0u, k0, k1);
-        const uint32_t lane = (uint32_t)index & 3u;
-        const uint32_t w = lane == 0 ? r.x : (lane == 1 ? r.y : (lane == 2 ? r.z : r.w));
-        return poisson_small(lambda, w);
-    }
-    const uint64_t pr = index >> 1;
-    const Philox4 r = philox4x32_10((uint32_t)pr, (uint32_t)(pr >> 32), stream, 1u, k0, k1);
-    const bool odd = (index & 1) != 0;
-    return poisson_ptrs(lambda, odd ? r.z : r.x, odd ? r.w : r.y, k0, k1, stream, index);
-}
-
-// Four voxels index4 .. index4+3 (index4 % 4 == 0) sharing their group / pair blocks.
-__device__ __forceinline__ float4 poisson_counter4(double l0, double l1, double l2, double l3, uint32_t k0,
-                                                   uint32_t k1, uint32_t stream, uint64_t index4)
-{
-    float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
-    const bool s0 = l0 > 0.0 && l0 < 10.0, s1 = l1 > 0.0 && l1 < 10.0, s2 = l2 > 0.0 && l2 < 10.0,
-               s3 = l3 > 0.0 && l3 < 10.0;
-    if (s0 || s1 || s2 || s3) {
-        const uint64_t g = index4 >> 2;
-        const Philox4 r = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), stream, 0u, k0, k1);
-        if (s0) out.x = poisson_small(l0, r.x);
-        if (s1) out.y = poisson_small(l1, r.y);
-        if (s2) out.z = poisson_small(l2, r.z);
-        if (s3) out.w = poisson_small(l3, r.w);
-    }
-    // Bright voxels.  Phase 1: the attempt-0 squeeze of every bright voxel of the lane (all lanes busy).
-    // Phase 2: the unresolved voxels (exact test and/or retries, ~14 %) are processed one per lane per round, so
-    // the expensive divergent code runs max-pending-per-lane times per wave instead of once per voxel slot.
-    const bool b0 = l0 >= 10.0, b1 = l1 >= 10.0, b2 = l2 >= 10.0, b3 = l3 >= 10.0;
-    uint32_t pend = 0u;                       // bit v: unresolved; bit 4+v: attempt 0 still needs its exact test
-    double pus[4], pV[4], pkd[4];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) { pus[v] = 0.0; pV[v] = 0.0; pkd[v] = 0.0; }
-    if (b0 || b1) {
-        const uint64_t pr = index4 >> 1;
-        const Philox4 r = philox4x32_10((uint32_t)pr, (uint32_t)(pr >> 32), stream, 1u, k0, k1);
-        if (b0) {
-            const int st = ptrs_fast(ptrs_setup(l0), l0, r.x, r.y, pus[0], pV[0], pkd[0]);
-            if (st == 0) out.x = (float)(long long)pkd[0]; else pend |= (st == 2 ? 0x11u : 0x01u);
-        }
-        if (b1) {
-            const int st = ptrs_fast(ptrs_setup(l1), l1, r.z, r.w, pus[1], pV[1], pkd[1]);
-            if (st == 0) out.y = (float)(long long)pkd[1]; else pend |= (st == 2 ? 0x22u : 0x02u);
-        }
-    }
-    if (b2 || b3) {
-        const uint64_t pr = (index4 >> 1) + 1;
-        const Philox4 r = philox4x32_10((uint32_t)pr, (uint32_t)(pr >> 32), stream, 1u, k0, k1);
-        if (b2) {
-            const int st = ptrs_fast(ptrs_setup(l2), l2, r.x, r.y, pus[2], pV[2], pkd[2]);
-            if (st == 0) out.z = (float)(long long)pkd[2]; else pend |= (st == 2 ? 0x44u : 0x04u);
-        }
-        if (b3) {
-            const int st = ptrs_fast(ptrs_setup(l3), l3, r.z, r.w, pus[3], pV[3], pkd[3]);
-            if (st == 0) out.w = (float)(long long)pkd[3]; else pend |= (st == 2 ? 0x88u : 0x08u);
-        }
-    }
-    while (pend & 0xFu) {
-        const int v = __ffs((int)(pend & 0xFu)) - 1;
-        const double lam = v == 0 ? l0 : (v == 1 ? l1 : (v == 2 ? l2 : l3));
-        const double us = v == 0 ? pus[0] : (v == 1 ? pus[1] : (v == 2 ? pus[2] : pus[3]));
-        const double V = v == 0 ? pV[0] : (v == 1 ? pV[1] : (v == 2 ? pV[2] : pV[3]));
-        const double kd0 = v == 0 ? pkd[0] : (v == 1 ? pkd[1] : (v == 2 ? pkd[2] : pkd[3]));
-        const bool exact0 = ((pend >> (4 + v)) & 1u) != 0u;
-        const PtrsSetup s = ptrs_setup(lam);
-        double loglam = 0.0;
-        bool have_loglam = false;
-        double res;
-        if (exact0 && ptrs_exact(s, lam, us, V, kd0, loglam, have_loglam)) res = kd0;
-        else res = ptrs_retry(s, lam, loglam, have_loglam, k0, k1, stream, index4 + (uint64_t)v);
-        const float fr = (float)(long long)res;
-        if (v == 0) out.x = fr; else if (v == 1) out.y = fr; else if (v == 2) out.z = fr; else out.w = fr;
-        pend &= ~(0x11u << v);
-    }
-    return out;
-}
 
 // ------------------------------------------------------------------------------------------------------------
 // Phase 1 of the production sampler, one wave at a time (used by k_extract4_noise and by the adjust + Poisson
@@ -422,7 +22,7 @@ __device__ __forceinline__ float4 poisson_counter4(double l0, double l1, double 
 //                                                attempt 0) are COMPACTED into a wave-private LDS list (ballot + prefix
 //                                                count) and the attempt-0 squeeze then runs one pair per lane with all lanes
 //                                                busy; what the squeeze does not accept is queued
-// Same arithmetic per (voxel, attempt) as poisson_counter: bit-identical counts.  Three things are pure execution
+// Same arithmetic per (voxel, attempt) as poisson_voxel: bit-identical counts.  Three things are pure execution
 // shortcuts that cannot change a decision:
 //   - the regime (small / bright) is read off an fp32 product with a guard band; inside the band the fp64 product decides;
 //   - the shortcut of the inversion regime, "u < exp(-lambda)" whenever u < 1 - lambda - 1e-12, is tested in fp32 with a
@@ -565,13 +165,13 @@ __device__ __forceinline__ void poisson_phase1(const float vv[4], bool valid, un
         ov[c] = 0.f;
     }
     if (small_any) {
-        const unsigned long long g = index4 >> 2;
 #ifdef MVSIM_EXP_NOPHILOX
+        const unsigned long long g = index4 >> 2;
         const Philox4 r = Philox4{(uint32_t)g * 2654435761u, (uint32_t)g * 40503u + 77u, (uint32_t)g ^ 0x9E3779B9u, (uint32_t)(g >> 3)};
 #else
-        const Philox4 r = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), a.stream, 0u, a.k0, a.k1);
+        const Philox4 r = group_block(index4, a.stream, a.k0, a.k1);
 #endif
-        const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+        const uint32_t w[4] = {group_word(r, 0u), group_word(r, 1u), group_word(r, 2u), group_word(r, 3u)};
 #pragma unroll
         for (int c = 0; c < 4; ++c)
             if (cls[c] == 1) {
@@ -628,21 +228,21 @@ __device__ __forceinline__ void poisson_phase1(const float vv[4], bool valid, un
         const unsigned int od = (unsigned int)__builtin_amdgcn_ds_bpermute((int)(owner << 2), (int)index_delta);
         if (!act) continue;
         const float2 pv = *reinterpret_cast<const float2*>(&ws->vin[4u * owner + first]);
-        const unsigned long long idx = index_base + od + first;          // even: the pair's attempt-0 block is idx >> 1
-        const unsigned long long pr = idx >> 1;
-        const Philox4 r = philox4x32_10((uint32_t)pr, (uint32_t)(pr >> 32), a.stream, 1u, a.k0, a.k1);
+        const unsigned long long idx = index_base + od + first;          // even: the first voxel of the pair
+        const Philox4 r = pair_block(idx, a.stream, a.k0, a.k1);
         float2 res = make_float2(0.f, 0.f);
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             const float v = e ? pv.y : pv.x;
             if (p1_class(v, a) == 2) {
-                const uint32_t w0 = e ? r.z : r.x, w1 = e ? r.w : r.y;
+                uint32_t w0, w1;
+                pair_words(r, (uint64_t)e, w0, w1);
                 float k;
 #ifdef MVSIM_P1_F64
                 const double lam = (double)v * a.mul;
                 double us, V, kd;
                 const bool ok = ptrs_fast(ptrs_setup(lam), lam, w0, w1, us, V, kd) == 0;
-                k = (float)(long long)kd;
+                k = count_as_float(kd);
 #else
                 const bool ok = ptrs_squeeze_f32((double)v * a.mul, w0, w1, k);
 #endif
@@ -666,11 +266,136 @@ __device__ __forceinline__ void poisson_phase1(const float vv[4], bool valid, un
     p1_wave_order();                                        // the scratch is reused by the wave's next slot
 }
 
-
-__device__ __forceinline__ float adjust_one(float v, double corr, float min_value)
+// ---- The block frame around phase 1 (the three queue kernels and pass E).  The append counter and the two refusal words are LDS of the
+// kernel (pass E: of its dynamic LDS), so the frame takes pointers.
+// Thread 0 zeroes the words; a block barrier has to follow before the first append (pass E: the one behind its twiddle table).
+__device__ __forceinline__ void p1_frame_zero(unsigned long long* ctr, unsigned int* ovf)
 {
-    const float t = (float)((double)v * corr);  // pass 1, Tools.java:150-151
-    return t + min_value;                       // pass 2, Tools.java:154-155 (second rounding, Q6)
+    if (threadIdx.x == 0) { *ctr = 0ull; ovf[0] = 0u; ovf[1] = 0u; }
+}
+
+__device__ __forceinline__ void p1_frame_open(unsigned long long* ctr, unsigned int* ovf)
+{
+    p1_frame_zero(ctr, ovf);
+    __syncthreads();
+}
+
+// `queue`: the segments of the launch (of the view); the block's own is segment blockIdx.x
+__device__ __forceinline__ P1Args p1_frame_args(double mul, uint32_t k0, uint32_t k1, uint32_t stream, PItem* queue, unsigned int segcap,
+                                                unsigned long long* ctr, unsigned int* ovf)
+{
+    P1Args pa;
+    pa.mul = mul; pa.mulf = (float)mul; pa.k0 = k0; pa.k1 = k1; pa.stream = stream;
+    pa.seg = queue + (unsigned long long)blockIdx.x * segcap; pa.segcap = segcap; pa.ctr = ctr; pa.ovf = ovf;
+    return pa;
+}
+
+// The end of the block's phase 1: its three count words, and from block 0 the header (HEADER == false: a queue of the fused tail, which
+// has none -- QueueLayout, fixed_header -- and whose pass E runs without a queue when there is no noise: `on`).
+template <bool HEADER>
+__device__ __forceinline__ void p1_frame_close(unsigned int* qcount, const unsigned long long* ctr, const unsigned int* ovf, unsigned int segcap,
+                                               bool on = true)
+{
+    __syncthreads();
+    if (threadIdx.x == 0 && on) {
+        p1_publish(qcount + (size_t)QCOUNT_WORDS * blockIdx.x, *ctr, ovf);
+        if (HEADER && blockIdx.x == 0) p1_publish_header(qcount, gridDim.x, segcap);
+    }
+}
+
+// ---- The group-by-group walk: planes that are no multiple of four voxels, buffers that are not 16-byte aligned, tiles of an interval.
+// Philox groups are four consecutive voxels of the RNG index, and a plane then starts anywhere inside a group: a lane takes one group
+// of one acquired plane -- up to four voxels, the ones that fall inside the plane --, and the 64 lanes of a wave slot take 64
+// consecutive groups of the SAME plane, so that a wave's outputs stay consecutive (what phase 1's pair compaction assumes).  Phase 1
+// (k_extract_noise2_any, k_extract_interval_noise2) and the walk over refused voxels (refused_collect) must agree on it exactly.
+struct GroupSlot {
+    long long k;                  // acquired plane
+    unsigned long long g;         // the lane's Philox group
+    long long i0;                 // its first voxel inside the plane (may be < 0); component c is voxel i0 + c
+    __device__ __forceinline__ bool has(int c, long long plane) const { const long long i = i0 + c; return i >= 0 && i < plane; }
+    // output position of component 0 (negative for a plane's first group when the plane starts inside it: the valid components land at
+    // non-negative positions all the same, in 64-bit wrap-around arithmetic)
+    __device__ __forceinline__ long long out0(long long plane) const { return k * plane + i0; }
+};
+
+__device__ __forceinline__ GroupSlot group_slot(long long sl, int lane, long long slots_per_plane, long long plane, long long idx_inc,
+                                                unsigned long long index_offset)
+{
+    GroupSlot s;
+    s.k = sl / slots_per_plane;
+    const long long jb = sl - s.k * slots_per_plane;
+    const unsigned long long ibase = index_offset + (unsigned long long)(s.k * idx_inc) * (unsigned long long)plane;   // RNG index of the plane's voxel 0
+    s.g = (ibase >> 2) + (unsigned long long)(jb * 64 + lane);
+    s.i0 = (long long)(4ull * s.g - ibase);
+    return s;
+}
+
+// How the walk reads the voxels of a slot: fetch(s, plane, vv) fills vv[c] for the components inside the plane, zeros elsewhere.
+// Planes one behind the other, `inc` planes apart; ADJUST applies the two adjustImage passes on the fly.
+template <bool ADJUST>
+struct FetchContiguous {
+    const float* __restrict__ in;
+    long long inc;
+    double corr;
+    float min_value;
+    __device__ __forceinline__ void operator()(const GroupSlot& s, long long plane, float vv[4]) const
+    {
+        const float* __restrict__ src = in + s.k * inc * plane;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const bool ok = s.has(c, plane);
+            float v = 0.f;
+            if (ok) {
+                v = src[s.i0 + c];
+                if (ADJUST) v = adjust_one(v, corr, min_value);
+            }
+            vv[c] = ok ? v : 0.f;
+        }
+    }
+};
+
+// A tile of tx voxels per row inside a wider volume.  A group may straddle a row end (tx % 4 != 0) or several rows (tx < 4): tile-local
+// i gives y = i / tx, x = i - y * tx for the group's first voxel inside the plane -- one 32-bit division by the wave-uniform tx per lane
+// (plane < 2^32 where a queue is planned) -- and a carry takes the other components across row ends.  Offsets into the volume are 64-bit.
+struct FetchPitched {
+    const float* __restrict__ in;
+    long long inc, plane_pitch, row_pitch;
+    unsigned int tx;
+    __device__ __forceinline__ void operator()(const GroupSlot& s, long long plane, float vv[4]) const
+    {
+        const float* __restrict__ src = in + s.k * inc * plane_pitch;
+        // (x, y) of the group's first voxel inside the plane; a lane past the plane's end divides too and reads nothing
+        const unsigned int ifirst = (unsigned int)(s.i0 < 0 ? 0 : s.i0);
+        unsigned int y = ifirst / tx, x = ifirst - y * tx;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float v = 0.f;
+            if (s.has(c, plane)) {
+                v = src[(long long)y * row_pitch + x];
+                if (++x == tx) { x = 0u; ++y; }
+            }
+            vv[c] = v;
+        }
+    }
+};
+
+// Phase 1 over the wave slots of a block (four waves, one slot each per trip), whatever the fetch.
+template <bool CHECKED, class FETCH>
+__device__ __forceinline__ void group_walk_phase1(const FETCH& fetch, float* __restrict__ out, long long plane, long long nzo, long long idx_inc,
+                                                  unsigned long long index_offset, long long slots_per_plane, const P1Args& pa, P1Scratch* scratch)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long slots = slots_per_plane * nzo;        // wave slots: 64 groups each
+    for (long long sl = (long long)blockIdx.x * 4 + wave; sl < slots; sl += (long long)gridDim.x * 4) {
+        const GroupSlot s = group_slot(sl, lane, slots_per_plane, plane, idx_inc, index_offset);
+        float vv[4], ov[4];
+        fetch(s, plane, vv);
+        const bool any = s.has(0, plane) || s.has(1, plane) || s.has(2, plane) || s.has(3, plane);
+        poisson_phase1<CHECKED>(vv, any, 4ull * s.g, (unsigned long long)s.out0(plane), pa, &scratch[wave], lane, ov);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (s.has(c, plane)) out[s.out0(plane) + c] = ov[c];
+    }
 }
 
 struct ResolveJob {
@@ -692,30 +417,7 @@ struct ResolveJob {
     long long           walk_spp;
 };
 
-// One voxel sampled where it stands, attempt by attempt from its own random words: what poisson_counter computes, in the
-// resolver's formulation.
-__device__ __forceinline__ float resolve_in_place(float v, const ResolveJob& j, unsigned long long index)
-{
-    const double lam = (double)v * j.mul;
-    if (lam < 10.0) {
-        const unsigned long long g = index >> 2;
-        const Philox4 r = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), j.stream, 0u, j.k0, j.k1);
-        const uint32_t c = (uint32_t)index & 3u;
-        return poisson_small(lam, c == 0u ? r.x : (c == 1u ? r.y : (c == 2u ? r.z : r.w)));
-    }
-    const unsigned long long pr = index >> 1;
-    const Philox4 r = philox4x32_10((uint32_t)pr, (uint32_t)(pr >> 32), j.stream, 1u, j.k0, j.k1);
-    uint32_t w0 = (index & 1ull) ? r.z : r.x, w1 = (index & 1ull) ? r.w : r.y;
-    float val = 0.f;
-#pragma unroll 1
-    for (uint32_t att = 0u;; ++att) {
-        if (att >= kPtrsMaxAttempts) return (float)(long long)lam;
-        if (att != 0u) ptrs_retry_words(index, att, j.k0, j.k1, j.stream, w0, w1);
-        if (ptrs_step_words(lam, w0, w1, val)) return val;
-    }
-}
-
-// RNG counter of output element o (see ResolveJob)
+// RNG counter of output element o (see ResolveJob; the resolver's retry path spells the same out with a 32-bit division)
 __device__ __forceinline__ unsigned long long resolve_index_of(const ResolveJob& j, unsigned long long o)
 {
     const unsigned long long kpl = j.idx_inc == 1u ? 0ull : o / j.plane;
@@ -733,18 +435,12 @@ __device__ __forceinline__ bool refused_collect(const ResolveJob& j, long long s
     if (first >= j.walk_n) return false;
     const long long u = first + (vec ? t : (t >> 6));
     if (u >= j.walk_n) return true;
-    long long p0 = 4 * u, lo = 0, hi = 4;                                // output position of component 0, valid components [lo, hi)
-    if (!vec) {
-        const long long k = u / j.walk_spp, jb = u - k * j.walk_spp;
-        const unsigned long long ibase = j.index_offset + (unsigned long long)(k * j.idx_inc) * (unsigned long long)j.plane;
-        const unsigned long long g = (ibase >> 2) + (unsigned long long)(jb * 64 + (t & 63));
-        const long long i0 = (long long)(4ull * g - ibase);
-        lo = i0 < 0 ? -i0 : 0;
-        hi = (long long)j.plane - i0 < 4 ? (long long)j.plane - i0 : 4;
-        p0 = k * (long long)j.plane + i0;
-    }
-    for (long long c = lo; c < hi; ++c)
-        if (j.out[p0 + c] < 0.f) list[atomicAdd(count, 1u)] = (unsigned int)(p0 + c);
+    // the float4 walk: group u is output voxels 4 u .. 4 u + 3, all inside; the group walk: the slot's group of lane t & 63
+    GroupSlot s{0, 0ull, 0};
+    if (!vec) s = group_slot(u, t & 63, j.walk_spp, (long long)j.plane, (long long)j.idx_inc, j.index_offset);
+    const long long p0 = vec ? 4 * u : s.out0((long long)j.plane);       // output position of component 0
+    for (int c = 0; c < 4; ++c)
+        if ((vec || s.has(c, (long long)j.plane)) && j.out[p0 + c] < 0.f) list[atomicAdd(count, 1u)] = (unsigned int)(p0 + c);
     return true;
 }
 
@@ -805,6 +501,7 @@ __device__ __forceinline__ void resolve_segment_body(const ResolveJob& j, long l
             if (have) it = seg[i];
         } else {
             a += 1u;
+            // (resolve_index_of's twin, with the 32-bit division an item's position allows: the two must say the same)
             const unsigned int kpl = j.idx_inc == 1u ? 0u : it.out / j.plane;
             const unsigned long long index = j.index_offset + (unsigned long long)it.out + (unsigned long long)kpl * (j.idx_inc - 1u) * j.plane;
             ptrs_retry_words(index, a, j.k0, j.k1, j.stream, it.w0, it.w1);
