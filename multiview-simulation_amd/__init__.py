@@ -159,12 +159,14 @@ class Context(ContextAberrations, ContextPhantoms):
             device = int(os.environ.get("LOCAL_RANK", "0"))
         _lib.check(self._L.mvsim_create(device, C.byref(self._h)))
         self.device = device
+        self._comm_size = None
 
     # -- lifecycle
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h:
             self._L.mvsim_destroy(self._h)
             self._h = C.c_void_p()
+            self._comm_size = None
 
     def __del__(self):
         try:
@@ -881,6 +883,12 @@ class Context(ContextAberrations, ContextPhantoms):
             raise ValueError("unique id must be 128 bytes")
         buf = (C.c_ubyte * _lib.UNIQUE_ID_BYTES).from_buffer_copy(uid)
         _lib.check(self._L.mvsim_comm_init(self._h, nranks, rank, buf))
+        self._comm_size = int(nranks)
+
+    @property
+    def comm_size(self) -> "int | None":
+        """Ranks of this context's communicator (a successful comm_init); None without one."""
+        return getattr(self, "_comm_size", None)
 
     def comm_broadcast_volume(self, dptr: int, count: int, root: int = 0) -> None:
         _lib.check(self._L.mvsim_comm_broadcast_volume(self._h, C.c_void_p(dptr), count, root))
@@ -897,6 +905,7 @@ class Context(ContextAberrations, ContextPhantoms):
 
     def comm_destroy(self) -> None:
         _lib.check(self._L.mvsim_comm_destroy(self._h))
+        self._comm_size = None
 
 
 class Group:

@@ -549,7 +549,6 @@ static int slab_convolve_enqueue(mvsim_ctx* ctx, const float* gt, const int64_t 
     int64_t za = z0 - hl, zb = z1 + c;                     // [za, zb)
     if (za < 0) { zb = std::max<int64_t>(zb, std::min<int64_t>(nz, -za + 1)); za = 0; }
     if (zb > nz) { za = std::min<int64_t>(za, std::max<int64_t>(0, 2 * nz - 1 - zb)); zb = nz; }
-    if (kz >= nz) { za = 0; zb = nz; }
     int64_t P[3];
     if (!custom_fft_sizes(dim, kdim, P, ctx->opt)) {
         set_error("slab tiling: no hand-written FFT size for this volume / PSF");
@@ -565,6 +564,7 @@ static int slab_convolve_enqueue(mvsim_ctx* ctx, const float* gt, const int64_t 
     // (round 6) the slab's planes through the fused rotate + attenuate + x-transform kernel, as an untiled view's: the attenuated planes
     // never cross HBM (z_first = za, zb - za planes; F holds them from plane 0, where pass B of the slab's convolution expects them)
     bool x_done = false;
+    ev_begin(ctx, ST_ROTATE);
     MVSIM_TRY(rotate_attenuate_fftx(ctx, gt, nullptr, nullptr, dim, kdim, inv, p->delta, &x_done, nullptr, (int)za, (int)(zb - za)));
     if (!x_done) {
         MVSIM_TRY(ctx->vol_b.reserve(pbytes * (size_t)(zb - za)));
@@ -576,6 +576,7 @@ static int slab_convolve_enqueue(mvsim_ctx* ctx, const float* gt, const int64_t 
             return MVSIM_EINVAL;
         }
     }
+    ev_end(ctx, ST_ROTATE);
     const SlabRange slab{(int)za, (int)(zb - za), (int)z0, (int)(z1 - z0)};
     // a slab that starts at a multiple of the view's spacing convolves along z -- and sends through passes D and E -- only the planes
     // extractSlices reads, like an untiled compact view (the sum over ALL of the slab's planes comes from the z pass's input rows)

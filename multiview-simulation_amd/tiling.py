@@ -12,6 +12,10 @@ rank r owns the planes [z0, z1) of the view (`mvsim_slab_range`).  Per view and 
 
 The reduction goes through the C ABI's own RCCL communicator (`Context.comm_init`); `allreduce_f64` replaces it only where RCCL
 cannot run -- two gloo ranks sharing one GPU in the rehearsal tests.  Nothing here touches torch.
+
+`mvsim_view_slab_dev` reduces nothing on a context without a communicator (documented: a job of one rank).  With `world > 1` that
+would adjust every slab with its own sum alone, silently; `TiledView.run_on_device` therefore raises before any launch unless the
+communicator's context reports `comm_size == world` (`Context.comm_size`: the size of a successful `comm_init`, None without one).
 """
 from __future__ import annotations
 
@@ -38,8 +42,6 @@ def halo_planes(nz: int, kz: int, z0: int, z1: int):
     if zb > nz:
         za = min(za, max(0, 2 * nz - 1 - zb))
         zb = nz
-    if kz >= nz:
-        za, zb = 0, nz
     return za, zb
 
 
@@ -67,6 +69,10 @@ class TiledView:
         waits for the host.  Needs the C ABI's communicator (or a job of one rank); `run` remains for reductions the caller brings."""
         if self._allreduce is not None and self.world > 1:
             raise RuntimeError("run_on_device reduces through the C ABI's communicator; use run() with a caller-supplied reduction")
+        if self.world > 1 and getattr(self.comm_ctx, "comm_size", None) != self.world:
+            raise RuntimeError(f"run_on_device: {self.world} ranks, but the communicator's context has "
+                               f"comm_size = {getattr(self.comm_ctx, 'comm_size', None)} (Context.comm_init first): every rank would "
+                               "adjust its slab with its own sum")
         nz = int(dim_xyz[2])
         z0, z1 = self.slab(nz)
         got = self.ctx.view_slab_dev(gt_dptr, dim_xyz, psf, params, z0, z1, acq_dptr,

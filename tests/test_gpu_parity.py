@@ -1337,7 +1337,12 @@ def test_rccl_entry_points_single_rank(mvs, synth):
     form of the ground-truth broadcast (a count that does not divide into aligned chunks, so the tail broadcast runs
     too), the ring form, the float all-reduce and the one-double all-reduce."""
     with mvs.Context(0) as c:
+        assert c.comm_size is None
+        with pytest.raises(ValueError):
+            c.comm_init(1, 0, b"short")                                   # no communicator, no size
+        assert c.comm_size is None
         c.comm_init(1, 0, mvs.Context.comm_unique_id())
+        assert c.comm_size == 1                                           # what TiledView.run_on_device asks before it launches
         vol = np.random.default_rng(8).random(100003, dtype=np.float32)
         d = _dev_volume(c, vol)
         try:
@@ -1379,6 +1384,7 @@ def test_rccl_entry_points_single_rank(mvs, synth):
         finally:
             c.dev_free(d)
         c.comm_destroy()
+        assert c.comm_size is None
         with pytest.raises(ValueError):
             c.comm_broadcast_volume(1, 1, 0)                              # communicator gone
 
