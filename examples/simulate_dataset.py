@@ -25,17 +25,9 @@ synth = importlib.import_module("multiview-simulation_amd.synthetic")
 S, T = mvs.SimulateMultiViewDataset, mvs.Tools
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--size", type=int, default=64)
-    ap.add_argument("--views", type=int, default=7)           # angleIncrement = 52 -> 7 views (:540)
-    ap.add_argument("--psf", type=int, default=15)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--reference-inputs", default=None, metavar="DIR",
-                    help="directory holding the reference's Angle<angle>.tif PSFs; uses simulate() as ground truth")
-    ap.add_argument("--tiff", action="store_true", help="write ImageJ TIFF files named as the reference names them")
-    a = ap.parse_args()
-
+def simulate(a):
+    """The dataset as a dict of volumes, named as `main` names its files; a: size, views, psf, reference_inputs
+    (examples/deconvolve_dataset.py runs this in memory)."""
     poissonSNR, lightsheetSpacing, osem, angleOffset = 25.0, 3, 3.0, 15   # :531-548
     attenuation = float(np.float32(0.01))                     # `final float attenuation = 0.01f` widened to double
     angleIncrement = 52 if a.reference_inputs else 360 // a.views      # seven angles (:540)
@@ -70,6 +62,20 @@ def main():
         sumWeights = sumWeights + w                           # :648-661
     out["sum_weights"] = sumWeights
     print(f"sum of weights: min {sumWeights.min():.3f} max {sumWeights.max():.3f}")
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=64)
+    ap.add_argument("--views", type=int, default=7)           # angleIncrement = 52 -> 7 views (:540)
+    ap.add_argument("--psf", type=int, default=15)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--reference-inputs", default=None, metavar="DIR",
+                    help="directory holding the reference's Angle<angle>.tif PSFs; uses simulate() as ground truth")
+    ap.add_argument("--tiff", action="store_true", help="write ImageJ TIFF files named as the reference names them")
+    a = ap.parse_args()
+    out = simulate(a)
     if a.out:
         os.makedirs(a.out, exist_ok=True)
         if a.tiff:

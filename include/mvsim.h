@@ -460,6 +460,64 @@ int mvsim_normalize_weights_dev(mvsim_ctx* ctx, float* const* weights, int n_vie
 /* Host buffers: weights[v] are host pointers of n floats each. */
 int mvsim_normalize_weights(mvsim_ctx* ctx, float* const* weights, int n_views, int64_t n, float osem);
 
+/* ---- multi-view deconvolution: the consumer of the simulated dataset ------------------------------------------------------
+ * Weighted, sequential (OSEM) multi-view Richardson-Lucy over V views phi_v of one size, optional weights w_v of that size, one
+ * PSF P_v per view (each with its own kdim) and an estimate psi.  The reference has no deconvolution; the recipe is this one.
+ * With conv(a, P)[i] = sum_k P[k] a_mirror[i - (k - K/2)] the convolution of mvsim_convolve (mirror-single extension, centre K/2,
+ * no flip), for iteration = 0 .. T-1 and v = 0 .. V-1 in the order given, psi updated after every view:
+ *     b = conv(psi, P_v)
+ *     r = phi_v / fmaxf(b, eps)                 one IEEE float division; a NaN b takes eps
+ *     c = conv(r, F_v)                          F_v: mvsim_decon_flip_psf(P_v), so that c[i] = sum_k P_v[k] r_mirror[i + (k - K/2)]
+ *     n = psi * c                               float
+ *     lambda > 0:  n = (float)((sqrt(1.0 + 2.0 * lambda * (double)n) - 1.0) / lambda)        in double
+ *     n NaN or n < min_value:  n = min_value
+ *     psi = n    without weights,    psi = psi + w_v * (n - psi)    with them (float subtract, multiply, add)
+ * Every step is rounded on its own.  The elementwise steps are exact (bit for bit the float32 arithmetic above); the convolutions
+ * carry the error of mvsim_convolve (<= 1e-5 of range each).
+ * UNLIKE mvsim_convolve, the caller's PSF arrays are NOT written: every PSF is copied and the copy normalised (Tools.normImage).
+ * Start value: params.init_from_psi = 1: what psi holds on entry; else init_value > 0: that constant; else the mean over views of
+ * each view's mean (fp64 sums), rounded to float; constant and mean are floored at min_value.
+ * Device memory beyond the caller's buffers: two volumes of the views' size plus the 2 V prepared PSFs (and what the convolution
+ * itself keeps), all context workspaces that mvsim_release_caches frees. */
+typedef struct mvsim_decon_params {
+    int32_t iterations;      /* >= 1 */
+    int32_t method;          /* as mvsim_convolve: 0 auto, 1 FFT, 2 stencil (a flipped PSF of an even 64 has 65 taps: EINVAL) */
+    int32_t init_from_psi;   /* 0 | 1 */
+    float   init_value;      /* > 0: constant start; <= 0: mean of the views */
+    float   min_value;       /* default 1e-4f */
+    float   eps;             /* default 1e-6f */
+    double  lambda;          /* Tikhonov; default 0 = off */
+} mvsim_decon_params;
+typedef struct mvsim_decon_stat {
+    double  sum_psi;         /* fp64 sum of the new estimate */
+    float   max_change;      /* max |psi_new - psi_old| (float subtraction; NaN differences are skipped) */
+    int64_t n_floored;       /* voxels whose n was NaN or below min_value */
+} mvsim_decon_stat;
+void mvsim_decon_params_default(mvsim_decon_params* p);
+/* Host only.  out[j] = psf[K-1-j] per axis; an axis of EVEN extent gets one leading zero tap (extent K+1), which puts the centre
+ * (K+1)/2 where the correlation needs it.  out holds prod(kdim[d] | 1) floats; out_kdim[d] = kdim[d] | 1. */
+int mvsim_decon_flip_psf(const float* psf, const int64_t kdim[3], float* out, int64_t out_kdim[3]);
+/* Host only: {most blocks an elementwise kernel launches, voxels a block takes per trip of its grid-stride loop}. */
+int mvsim_decon_geometry(int64_t out[2]);
+/* The two elementwise steps on device buffers of n floats, any alignment.  ratio may be `blurred` (in place). */
+int mvsim_decon_ratio_dev(mvsim_ctx* ctx, const float* phi, const float* blurred, int64_t n, float eps, float* ratio);
+/* In place on psi; weight_or_null: device.  stat_host_or_null non-null: the statistics of the step, and the call synchronises.
+ * The three values repeat bit for bit from run to run (per-block partials, one fixed-order final reduction, no atomics). */
+int mvsim_decon_update_dev(mvsim_ctx* ctx, float* psi, const float* corr, const float* weight_or_null, int64_t n,
+                           float min_value, double lambda, mvsim_decon_stat* stat_host_or_null);
+/* views_dev, weights_dev_or_null: HOST arrays of n_views DEVICE pointers (weights: all or none); psf_host: HOST arrays of HOST
+ * PSFs, kdims: 3 extents per view.  psi_dev must not overlap a view or a weight.  Asynchronous on the context's stream unless
+ * stats_or_null is given: iterations * n_views entries, [iteration][view], fetched in ONE download at the end.
+ * MVSIM_EINVAL: n_views outside [1, MVSIM_MAX_VIEWS], iterations < 1, a null or mismatched argument, psi aliasing a view or a
+ * weight, method outside 0..2, eps <= 0, min_value <= 0, lambda < 0 (NaN included). */
+int mvsim_deconvolve_dev(mvsim_ctx* ctx, const float* const* views_dev, const float* const* weights_dev_or_null,
+                         const float* const* psf_host, const int64_t* kdims, int n_views, const int64_t dim[3],
+                         const mvsim_decon_params* params, float* psi_dev, mvsim_decon_stat* stats_or_null);
+/* The same with HOST buffers for views, weights and psi (read only with init_from_psi, always written); synchronous. */
+int mvsim_deconvolve(mvsim_ctx* ctx, const float* const* views, const float* const* weights_or_null,
+                     const float* const* psf_host, const int64_t* kdims, int n_views, const int64_t dim[3],
+                     const mvsim_decon_params* params, float* psi, mvsim_decon_stat* stats_or_null);
+
 /* ---- extractSlices over Intervals of volumes that stay on the device (SimulateTileStitching.java:131-189) ---------------
  * Views.zeroMin(Views.interval(con, min, max)) run through extractSlices: output voxel (x, y, k) of the contiguous tile
  * tx x ty x mvsim_extract_nz(tz, inc), t_d = max_d - min_d + 1, is f(in[(min_x + x) + Nx ((min_y + y) + Ny (min_z + k inc))]).

@@ -797,6 +797,56 @@ JNIEXPORT void JNICALL JNI_FN(simulateViewsBatch)(JNIEnv* env, jclass, jlong h, 
     throw_for(env, mvsim_simulate_views(ctx_of(h), pg, d.d, pp.data(), k.d, par.data(), pa.data(), (int)n));
 }
 
+// mvsim_deconvolve: the multi-view deconvolution on host buffers.  kdims: 3 extents per view; weights: null, or one buffer per view;
+// psi: the start estimate where init_from_psi is set, the result always.  Every length and capacity is checked before the C ABI sees a pointer.
+JNIEXPORT void JNICALL JNI_FN(deconvolve)(JNIEnv* env, jclass, jlong h, jobjectArray views, jobjectArray weights, jobjectArray psfs,
+                                          jlongArray kdims, jlongArray dim, jint iterations, jint method, jboolean init_from_psi,
+                                          jfloat init_value, jfloat min_value, jfloat eps, jdouble lambda, jobject psi)
+{
+    Dim d(env, dim);
+    if (!d.ok) return;
+    if (!views || !psfs || !kdims) { throw_new(env, "java/lang/IllegalArgumentException", "deconvolve: null argument"); return; }
+    const jsize nv = env->GetArrayLength(views);
+    if (nv < 1 || nv > MVSIM_MAX_VIEWS) { throw_new(env, "java/lang/IllegalArgumentException", "deconvolve: 1..32 views"); return; }
+    if (env->GetArrayLength(psfs) != nv || env->GetArrayLength(kdims) != 3 * nv || (weights && env->GetArrayLength(weights) != nv)) {
+        throw_new(env, "java/lang/IllegalArgumentException", "deconvolve: one PSF, three PSF extents and (with weights) one weight buffer per view");
+        return;
+    }
+    jlong kd[3 * MVSIM_MAX_VIEWS];
+    env->GetLongArrayRegion(kdims, 0, 3 * nv, kd);
+    if (env->ExceptionCheck()) return;
+    int64_t k64[3 * MVSIM_MAX_VIEWS];
+    const float *pv[MVSIM_MAX_VIEWS], *pw[MVSIM_MAX_VIEWS], *pp[MVSIM_MAX_VIEWS];
+    for (jsize v = 0; v < nv; ++v) {
+        for (int a = 0; a < 3; ++a) {
+            k64[3 * v + a] = kd[3 * v + a];
+            if (kd[3 * v + a] < 1 || kd[3 * v + a] > 65535) { throw_new(env, "java/lang/IllegalArgumentException", "deconvolve: PSF extents must be in 1..65535"); return; }
+        }
+        jobject b = env->GetObjectArrayElement(views, v);
+        if (env->ExceptionCheck()) return;
+        pv[v] = fptr(env, b, d.n(), "deconvolve: view buffer smaller than the dimensions");
+        if (!pv[v]) return;                                 // (no JNI call with that exception pending)
+        b = env->GetObjectArrayElement(psfs, v);
+        if (env->ExceptionCheck()) return;
+        pp[v] = fptr(env, b, k64[3 * v] * k64[3 * v + 1] * k64[3 * v + 2], "deconvolve: PSF buffer smaller than its dimensions");
+        if (!pp[v]) return;
+        pw[v] = nullptr;
+        if (weights) {
+            b = env->GetObjectArrayElement(weights, v);
+            if (env->ExceptionCheck()) return;
+            pw[v] = fptr(env, b, d.n(), "deconvolve: weight buffer smaller than the dimensions");
+            if (!pw[v]) return;
+        }
+    }
+    float* ps = fptr(env, psi, d.n(), "deconvolve: estimate buffer smaller than the dimensions");
+    if (!ps) return;
+    mvsim_decon_params p;
+    mvsim_decon_params_default(&p);
+    p.iterations = iterations; p.method = method; p.init_from_psi = init_from_psi ? 1 : 0; p.init_value = init_value;
+    p.min_value = min_value; p.eps = eps; p.lambda = lambda;
+    throw_for(env, mvsim_deconvolve(ctx_of(h), pv, weights ? pw : nullptr, pp, k64, (int)nv, d.d, &p, ps, nullptr));
+}
+
 // ---- mvsim_group_* -------------------------------------------------------------------------------------------------
 JNIEXPORT jlong JNICALL JNI_FN(groupCreate)(JNIEnv* env, jclass, jint ndev)
 {

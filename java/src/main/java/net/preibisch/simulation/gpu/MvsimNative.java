@@ -106,6 +106,14 @@ final class MvsimNative
 	/** Cross-view weight normalisation (:615-640), in place on every buffer. */
 	static native void normalizeWeights( long ctx, FloatBuffer[] weights, long n, float osem );
 
+	/**
+	 * Multi-view deconvolution (mvsim_deconvolve; include/mvsim.h states the recipe): views, weights (null: none) and psfs hold one direct
+	 * buffer per view, kdims three PSF extents per view.  psi is read where initFromPsi is set and always receives the estimate.  The
+	 * PSF buffers are not written (unlike convolve).  The shim checks every array length and buffer capacity first.
+	 */
+	static native void deconvolve( long ctx, FloatBuffer[] views, FloatBuffer[] weights, FloatBuffer[] psfs, long[] kdims, long[] dim,
+			int iterations, int method, boolean initFromPsi, float initValue, float minValue, float eps, double lambda, FloatBuffer psi );
+
 	/** Fused loop body of SimulateMultiViewDataset.main (:570-585); rot/att/con may be null (then they never leave HBM). */
 	static native double simulateView( long ctx, FloatBuffer gt, long[] dim, FloatBuffer psf, long[] kdim,
 			int axis, int degrees, double delta, float minValue, float targetAverage, int inc, float snr, long seed, int stream,

@@ -24,11 +24,12 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import IntervalJob, MvsimError, MvsimNoDeviceError, Sphere, Timings, ViewOutputs, ViewParams  # noqa: F401
+from ._lib import DeconParams, DeconStat, IntervalJob, MvsimError, MvsimNoDeviceError, Sphere, Timings, ViewOutputs, ViewParams  # noqa: F401
 from .aberrations import ContextAberrations
+from .deconvolution import ContextDeconvolution, MultiViewDeconvolution, decon_geometry, decon_params, flip_psf  # noqa: F401
 from .phantoms import ContextPhantoms
 
-__all__ = ["AffineTransform3D", "Context", "Group", "Hessian", "HypersphereCollectionRealRandomAccessible", "JavaRandom", "Lightsheet",
+__all__ = ["AffineTransform3D", "Context", "DeconParams", "MultiViewDeconvolution", "Group", "Hessian", "HypersphereCollectionRealRandomAccessible", "JavaRandom", "Lightsheet",
            "PerlinNoiseRealRandomAccessible", "PointRejectionSampling", "RayTracingTest", "Raytrace", "RefractiveIndexMap", "ClearingMap", "SimpleCalculatedRealRandomAccessible", "SimulateBeads",
            "SimulateBeads2", "SimulateMultiViewAberrations", "SimulateMultiViewDataset", "Tools", "VolumeInjection", "broadcast_plan", "default_context", "MvsimError", "MvsimNoDeviceError", "ViewParams", "shard_views",
            "version"]
@@ -147,10 +148,11 @@ def _ptr(a: np.ndarray) -> C.c_void_p:
     return C.c_void_p(a.ctypes.data)
 
 
-class Context(ContextAberrations, ContextPhantoms):
+class Context(ContextAberrations, ContextPhantoms, ContextDeconvolution):
     """One ``mvsim_ctx``: bound to one GPU, not thread-safe.  (The refraction simulator's entry points -- refract3d,
     project_to_camera, hessian_at, volume_inject, ... -- are in aberrations.ContextAberrations, the procedural phantom's --
-    perlin_at, spheres_raster, rejection_sample, ... -- in phantoms.ContextPhantoms.)"""
+    perlin_at, spheres_raster, rejection_sample, ... -- in phantoms.ContextPhantoms, the multi-view deconvolution's --
+    deconvolve, deconvolve_dev, decon_ratio_dev, decon_update_dev -- in deconvolution.ContextDeconvolution.)"""
 
     def __init__(self, device: int | None = None):
         self._h = C.c_void_p()

@@ -87,6 +87,20 @@ class IntervalJob(C.Structure):
                 ("snr", C.c_float), ("seed", C.c_uint64), ("stream", C.c_uint32)]
 
 
+class DeconParams(C.Structure):
+    """mvsim_decon_params: the settings of mvsim_deconvolve (mvsim_decon_params_default fills them)."""
+    _fields_ = [("iterations", C.c_int32), ("method", C.c_int32), ("init_from_psi", C.c_int32), ("init_value", C.c_float),
+                ("min_value", C.c_float), ("eps", C.c_float), ("lambda_", C.c_double)]
+
+
+class DeconStat(C.Structure):
+    """mvsim_decon_stat: what one update step reports."""
+    _fields_ = [("sum_psi", C.c_double), ("max_change", C.c_float), ("n_floored", C.c_int64)]
+
+    def as_dict(self):
+        return {"sum_psi": float(self.sum_psi), "max_change": float(self.max_change), "n_floored": int(self.n_floored)}
+
+
 class Timings(C.Structure):
     _fields_ = [(n, C.c_float) for n in
                 ("rotate_ms", "attenuate_ms", "psf_ms", "convolve_ms", "adjust_ms", "extract_ms", "total_ms",
@@ -263,6 +277,15 @@ SIGNATURES = {
     "mvsim_multi_spheres": (C.c_int, [_vp, _vp, _vp, _i64p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
     "mvsim_multi_spheres_dev": (C.c_int, [_vp, _vp, _vp, _i64p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
     "mvsim_sphere_walk_geometry": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "mvsim_decon_params_default": (None, [C.POINTER(DeconParams)]),
+    "mvsim_decon_flip_psf": (C.c_int, [_vp, _i64p, _vp, _i64p]),
+    "mvsim_decon_geometry": (C.c_int, [_i64p]),
+    "mvsim_decon_ratio_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_float, _vp]),
+    "mvsim_decon_update_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_float, C.c_double, C.POINTER(DeconStat)]),
+    "mvsim_deconvolve_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i64p, C.c_int, _i64p,
+                                       C.POINTER(DeconParams), _vp, C.POINTER(DeconStat)]),
+    "mvsim_deconvolve": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i64p, C.c_int, _i64p,
+                                   C.POINTER(DeconParams), _vp, C.POINTER(DeconStat)]),
 }
 
 _lib = None

@@ -424,18 +424,24 @@ int psf_prepare(mvsim_ctx* ctx, float* psf_host, const int64_t kdim[3], const in
     return MVSIM_OK;
 }
 
-int convolve_dev_impl(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const int64_t kdim[3], int method, float* out,
-                      ConvTail* tail)
+int convolve_with_psf(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const float* psf_dev, const int64_t kdim[3], int method,
+                      float* out, ConvTail* tail)
 {
     MVSIM_CHECK_ARG(img != out, "convolve cannot run in place");
     if (pick_method(method, kdim) == 2) {
         if (tail) { tail->zstride = 1; tail->corr_done = false; }
         ev_begin(ctx, ST_CONVOLVE);
-        MVSIM_TRY(launch_stencil(ctx, img, dim, ctx->psf_dev.as<float>(), kdim, out));
+        MVSIM_TRY(launch_stencil(ctx, img, dim, psf_dev, kdim, out));
         ev_end(ctx, ST_CONVOLVE);
         return MVSIM_OK;
     }
-    return fft_convolve(ctx, img, dim, ctx->psf_dev.as<float>(), kdim, out, tail);
+    return fft_convolve(ctx, img, dim, psf_dev, kdim, out, tail);
+}
+
+int convolve_dev_impl(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const int64_t kdim[3], int method, float* out,
+                      ConvTail* tail)
+{
+    return convolve_with_psf(ctx, img, dim, ctx->psf_dev.as<float>(), kdim, method, out, tail);
 }
 
 }  // namespace mvsim

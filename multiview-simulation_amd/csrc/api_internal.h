@@ -1,6 +1,6 @@
 // What the translation units of the C ABI share: api.cpp (context, options, memory, stage operators on device buffers, queries),
 // api_view.cpp (the per-view pipeline on device buffers), api_host.cpp (host-buffer entry points), api_sims.cpp (phantom, bead and
-// refraction-simulator wrappers).  Host orchestration only.
+// refraction-simulator wrappers), api_decon.cpp (the multi-view deconvolution).  Host orchestration only.
 #pragma once
 
 #include "common.h"
@@ -29,6 +29,9 @@ void psf_normalise_host(float* psf_host, int64_t n);
 int psf_prepare(mvsim_ctx* ctx, float* psf_host, const int64_t kdim[3], const int64_t dim[3]);
 int convolve_dev_impl(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const int64_t kdim[3], int method, float* out,
                       ConvTail* tail = nullptr);
+// the same convolution with an explicit device PSF (convolve_dev_impl: the context's own); neither method caches by the PSF's address
+int convolve_with_psf(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const float* psf_dev, const int64_t kdim[3], int method,
+                      float* out, ConvTail* tail = nullptr);
 void view_graphs_release(mvsim_ctx* ctx);                 // api_view.cpp
 void async_release(mvsim_ctx* ctx);                       // api_host.cpp
 // host buffer <-> workspace on the context's stream (api_host.cpp); down() returns with the data on the host

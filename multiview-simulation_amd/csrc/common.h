@@ -251,6 +251,9 @@ struct mvsim_ctx {
     int64_t       extract_path[5] = {-1, 0, 0, 0, 0};   // the sampler form of the last extract this context enqueued (mvsim_get_extract_path)
     int           views_since_flags = 0;    // views run WITHOUT flags since (a volume without empty planes pays nothing for the bookkeeping)
     mvsim::DevBuf weight_img;               // computeWeightImage of the last volume size (mvsim_simulate_iteration_dev)
+    mvsim::DevBuf decon_work[2];            // multi-view deconvolution (api_decon.cpp): the blurred estimate / ratio, and the correlation
+    mvsim::DevBuf decon_psf;                // ... every view's normalised PSF and its flipped twin, uploaded once per call
+    mvsim::DevBuf decon_stat;               // ... per-block partials, per-view sums and the statistics of every step of a call
     int64_t       weight_dim[3] = {0, 0, 0};
     mvsim::DevBuf host_gt, host_rot, host_att, host_con;   // device twins of the host-buffer simulate_view (grow-only)
     mvsim::DevBuf partials;                 // doubles: block partial sums + [sum, corr]
@@ -349,7 +352,7 @@ template <class F> inline void mvsim_ctx::each_workspace(F&& f)
     for (mvsim::DevBuf* b : {&vol_a, &vol_b, &vol_c, &out_buf, &psf_dev, &stencil_psf, &fft_real, &fft_spec_img, &fft_spec_psf, &fft_work,
                              &pqueue, &view_tab, &interval_tab, &sphere_list, &weight_img, &plane_flags, &host_gt, &host_rot, &host_att, &host_con, &cfft_f, &cfft_g,
                              &cfft_g1, &cfft_g2, &partials_z, &async_gt[0], &async_gt[1], &async_acq[0], &async_acq[1], &async_counts[0].dev,
-                             &async_counts[1].dev, &sync_counts.dev})
+                             &async_counts[1].dev, &sync_counts.dev, &decon_work[0], &decon_work[1], &decon_psf, &decon_stat})
         f(*b, 0);
     f(partials, WS_KEPT);
     f(partials_e, WS_KEPT);
