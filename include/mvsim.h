@@ -78,7 +78,9 @@ int  mvsim_join(mvsim_ctx* ctx);
  * 1024..2^31 ((brick, bead) pairs the bead renderer bins at once; larger calls run in chunks with identical results; the refraction
  * simulator's injection bins its (brick, step) pairs under the same cap, and so does the sphere raster of the procedural phantom),
  * "reject_batch" = 1..2^20|auto (trials per launch of mvsim_rejection_sample; the result does not depend on it),
- * "sphere_walk" = host|device|device_only|auto (mvsim_draw_spheres, mvsim_multi_spheres: see mvsim_multi_spheres; the result does not depend on it).
+ * "sphere_walk" = host|device|device_only|auto (mvsim_draw_spheres, mvsim_multi_spheres: see mvsim_multi_spheres; the result does not depend on it),
+ * "dog_pass" = both|xy|z (mvsim_dog_dev: launch only the xy kernel or only the z kernel, for timing a kernel alone; anything but
+ * `both` leaves no valid D).
  * MVSIM_OPTIONS="name=value;name=value" sets any of them process-wide.  Unknown names or values: MVSIM_EINVAL. */
 int  mvsim_set_option(mvsim_ctx* ctx, const char* name, const char* value);
 /* Release cached FFT plans / workspaces / PSF spectra held by the context. */
@@ -517,6 +519,92 @@ int mvsim_deconvolve_dev(mvsim_ctx* ctx, const float* const* views_dev, const fl
 int mvsim_deconvolve(mvsim_ctx* ctx, const float* const* views, const float* const* weights_or_null,
                      const float* const* psf_host, const int64_t* kdims, int n_views, const int64_t dim[3],
                      const mvsim_decon_params* params, float* psi, mvsim_decon_stat* stats_or_null);
+
+/* ---- bead detection: difference-of-Gaussian interest points, sub-voxel localised ------------------------------------------------
+ * The consumer of mvsim_render_beads: a DoG volume over a device-resident image, its strict local maxima above a threshold in a
+ * deterministic order, and a quadratic sub-voxel fit of every maximum.  The reference has no detector; the recipe is this one, and
+ * every arithmetic step is stated so that a literal restatement reproduces the result bit for bit.
+ * Volumes are x fastest with dim = {Nx, Ny, Nz}.  The source is float, or uint16_t converted with one (float)v on load.
+ * 1. Taps (host, fp64, handed to the kernels as floats).  For a sigma s > 0 the diameter is d = max(3, 2 (int)(3 s + 0.5) + 1) and
+ *    r = d / 2;  e[j] = exp(-((j - r) (j - r)) / (2 s s)) for j = 0 .. d-1 with libm exp;  S = e[0] + e[1] + ... in ascending order;
+ *    t[j] = (float)(e[j] / S).  A diameter above MVSIM_DOG_MAX_TAPS (63) is MVSIM_EINVAL.
+ * 2. Blur: separable, x then y then z, one float result per pass and voxel: acc = t[0] v_0, then acc = acc + t[j] v_j for j
+ *    ascending; each product and each sum is its own float operation (no fused multiply-add, the symmetric taps are not folded,
+ *    nothing is reordered).  v_j is the sample at index i + j - r through the mirror-single extension of mvsim_convolve: period
+ *    2 N - 2, folded as often as needed (m = (i + j - r) mod (2 N - 2), taken non-negative; m >= N reads 2 N - 2 - m), so any
+ *    N >= 2 with any legal radius is defined.  Every extent must be >= 2.
+ * 3. D = G1 - G2, one float subtraction; G1 is the blur with sigma1[3], G2 the blur with sigma2[3], each per axis (x, y, z).
+ *    Bright blobs are maxima of D.
+ * 4. Peaks.  A voxel is a peak when it is interior (1 <= x <= Nx-2, likewise y and z; a volume with an extent below 3 has none, no
+ *    error), D > threshold, D > each of the 13 neighbours of its 3x3x3 box with a smaller linear index and D >= each of the 13 with
+ *    a larger one -- float comparisons, so a NaN at the voxel or at any neighbour yields no peak and a plateau of equal voxels
+ *    yields at most one.  The list holds the peaks' linear indices x + Nx (y + Ny z) in ascending order; n_found is the total, and
+ *    only the first min(n_found, capacity) entries are written.
+ * 5. Localisation: one fp64 computation per listed peak from the float values of D, no fused operations.  At base voxel b, with
+ *    p_d = (double)D(b + e_d), m_d = (double)D(b - e_d), c = (double)D(b):
+ *        g_d  = (p_d - m_d) / 2.0
+ *        H_dd = (p_d - 2.0 * c) + m_d
+ *        H_df = (((D(b+e_d+e_f) - D(b-e_d+e_f)) - D(b+e_d-e_f)) + D(b-e_d-e_f)) / 4.0            (each D widened to double first)
+ *    With m00 = H_xx, m01 = m10 = H_xy, m02 = m20 = H_xz, m11 = H_yy, m12 = m21 = H_yz, m22 = H_zz, every product chain and every sum
+ *    evaluated left to right:
+ *        det  = m00*m11*m22 + m01*m12*m20 + m02*m10*m21 - m02*m11*m20 - m00*m12*m21 - m01*m10*m22
+ *        idet = 1.0 / det
+ *        i00 = (m11*m22 - m12*m21) * idet    i01 = (m02*m21 - m01*m22) * idet    i02 = (m01*m12 - m02*m11) * idet
+ *        i10 = (m12*m20 - m10*m22) * idet    i11 = (m00*m22 - m02*m20) * idet    i12 = (m02*m10 - m00*m12) * idet
+ *        i20 = (m10*m21 - m11*m20) * idet    i21 = (m01*m20 - m00*m21) * idet    i22 = (m00*m11 - m01*m10) * idet
+ *        o_d = -((i_d0 * g_x + i_d1 * g_y) + i_d2 * g_z)
+ *    det zero or non-finite, or a non-finite o_d: o = 0 and flag SINGULAR.
+ *    Moves: an axis with |o_d| > 0.5 wants to move its base one voxel in the direction of o_d.  The move is refused if it would
+ *    leave the interior, and refused with flag FROZEN if the axis has already moved in the opposite direction (the axis keeps its
+ *    base and its offset as computed; without this rule a bead centred within ~0.005 of a half voxel oscillates between two bases
+ *    and ends a voxel off).  If no move remains the fit is accepted; if moves remain but max_moves rounds are used up it is accepted
+ *    with flag CAPPED; otherwise every remaining move is applied at once (one round) and the fit is repeated at the new base.
+ *    SINGULAR and FROZEN describe the accepted fit.
+ *    Output: pos[d] = (double)b_d + o_d, value = (float)(c + 0.5 * ((g_x*o_x + g_y*o_y) + g_z*o_z)), flags, voxel = the final base. */
+#define MVSIM_DOG_MAX_TAPS 63
+#define MVSIM_SRC_F32 0
+#define MVSIM_SRC_U16 1
+#define MVSIM_PEAK_SINGULAR 1
+#define MVSIM_PEAK_FROZEN   2
+#define MVSIM_PEAK_CAPPED   4
+#define MVSIM_PEAK_OUTSIDE  8     /* mvsim_localise_peaks_dev only: the listed voxel is no interior voxel; pos = its coordinates, value 0 */
+typedef struct mvsim_dog_params {
+    double  sigma1[3];       /* x, y, z; default 1.8 */
+    double  sigma2[3];       /* default 1.8 * pow(2.0, 0.25) */
+    float   threshold;       /* default 0.008f: the usual proposal for images normalised to [0, 1] (mvsim_beads_normalize) */
+    int32_t max_moves;       /* default 4 */
+} mvsim_dog_params;
+typedef struct mvsim_peak {
+    double  pos[3];          /* b + o, x first */
+    float   value;
+    int32_t flags;           /* MVSIM_PEAK_* */
+    int64_t voxel;           /* linear index of the final base voxel */
+} mvsim_peak;
+void mvsim_dog_params_default(mvsim_dog_params* p);
+/* Host only, no context: the taps of step 1.  taps holds MVSIM_DOG_MAX_TAPS floats; *ntaps = d. */
+int mvsim_dog_taps(double sigma, float* taps, int* ntaps);
+/* Host only: {x extent, y extent of the xy kernel's plane tile, z extent of the z kernel's tile, largest radius (the halo limit),
+ * voxels one block of the peaks kernels takes}. */
+int mvsim_dog_geometry(int64_t out[5]);
+/* Steps 1-3 over a device image of src_type MVSIM_SRC_F32 / MVSIM_SRC_U16 (not written) into dog_dev (floats); any alignment of
+ * either.  Only sigma1 and sigma2 of params are read.  Asynchronous on the context's stream, like every _dev call below. */
+int mvsim_dog_dev(mvsim_ctx* ctx, const void* img_dev, int src_type, const int64_t dim[3], const mvsim_dog_params* params,
+                  float* dog_dev);
+/* Step 4 over a device float volume: voxels_dev receives min(n_found, capacity) int64 indices, *n_found_dev (one int64 in DEVICE
+ * memory) the total.  No atomics: per-block counts, an exclusive scan, an ordered emit. */
+int mvsim_find_peaks_dev(mvsim_ctx* ctx, const float* vol_dev, const int64_t dim[3], float threshold, int64_t capacity,
+                         int64_t* voxels_dev, int64_t* n_found_dev);
+/* Step 5 for the first min(*n_found_dev, capacity) entries of voxels_dev; peaks_dev entries past that are not written. */
+int mvsim_localise_peaks_dev(mvsim_ctx* ctx, const float* vol_dev, const int64_t dim[3], const int64_t* voxels_dev,
+                             const int64_t* n_found_dev, int64_t capacity, int max_moves, mvsim_peak* peaks_dev);
+/* The whole recipe; D, the list and the half-blurred volumes live in context workspaces that mvsim_release_caches frees.
+ * MVSIM_EINVAL: a null pointer, an extent below 2, a sigma <= 0 or non-finite, a diameter above 63, a NaN threshold,
+ * capacity <= 0, max_moves < 0, an unknown src_type. */
+int mvsim_detect_beads_dev(mvsim_ctx* ctx, const void* img_dev, int src_type, const int64_t dim[3], const mvsim_dog_params* params,
+                           int64_t capacity, mvsim_peak* peaks_dev, int64_t* n_found_dev);
+/* The same with HOST buffers in and out; synchronous.  peaks holds capacity entries, min(*n_found, capacity) are written. */
+int mvsim_detect_beads(mvsim_ctx* ctx, const void* img, int src_type, const int64_t dim[3], const mvsim_dog_params* params,
+                       int64_t capacity, mvsim_peak* peaks, int64_t* n_found);
 
 /* ---- extractSlices over Intervals of volumes that stay on the device (SimulateTileStitching.java:131-189) ---------------
  * Views.zeroMin(Views.interval(con, min, max)) run through extractSlices: output voxel (x, y, k) of the contiguous tile

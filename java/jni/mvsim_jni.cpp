@@ -847,6 +847,35 @@ JNIEXPORT void JNICALL JNI_FN(deconvolve)(JNIEnv* env, jclass, jlong h, jobjectA
     throw_for(env, mvsim_deconvolve(ctx_of(h), pv, weights ? pw : nullptr, pp, k64, (int)nv, d.d, &p, ps, nullptr));
 }
 
+// mvsim_detect_beads: DoG interest points with sub-voxel localisation on a host image.  img: a direct FloatBuffer, or (u16) a direct
+// ShortBuffer, of nx * ny * nz elements; peaks: a direct ByteBuffer of at least 40 * capacity bytes that receives min(found, capacity)
+// mvsim_peak records {double pos[3]; float value; int flags; long voxel} in native byte order.  Returns the number found.  Every length
+// and capacity is checked before the C ABI sees a pointer.
+JNIEXPORT jlong JNICALL JNI_FN(detectBeads)(JNIEnv* env, jclass, jlong h, jobject img, jboolean u16, jlongArray dim, jdouble s1x, jdouble s1y,
+                                            jdouble s1z, jdouble s2x, jdouble s2y, jdouble s2z, jfloat threshold, jint max_moves,
+                                            jlong capacity, jobject peaks)
+{
+    Dim d(env, dim);
+    if (!d.ok) return 0;
+    if (capacity < 1 || capacity > (static_cast<jlong>(1) << 31)) {
+        throw_new(env, "java/lang/IllegalArgumentException", "detectBeads: capacity must be in 1 .. 2^31");
+        return 0;
+    }
+    mvsim_dog_params p;
+    mvsim_dog_params_default(&p);
+    p.sigma1[0] = s1x; p.sigma1[1] = s1y; p.sigma1[2] = s1z;
+    p.sigma2[0] = s2x; p.sigma2[1] = s2y; p.sigma2[2] = s2z;
+    p.threshold = threshold;
+    p.max_moves = max_moves;
+    const void* src = any_ptr(env, img, d.n(), "detectBeads: image buffer missing or smaller than the dimensions");
+    if (!src) return 0;
+    void* out = any_ptr(env, peaks, capacity * static_cast<jlong>(sizeof(mvsim_peak)), "detectBeads: peak buffer missing or smaller than 40 * capacity bytes");
+    if (!out) return 0;
+    int64_t found = 0;
+    throw_for(env, mvsim_detect_beads(ctx_of(h), src, u16 ? MVSIM_SRC_U16 : MVSIM_SRC_F32, d.d, &p, capacity, static_cast<mvsim_peak*>(out), &found));
+    return static_cast<jlong>(found);
+}
+
 // ---- mvsim_group_* -------------------------------------------------------------------------------------------------
 JNIEXPORT jlong JNICALL JNI_FN(groupCreate)(JNIEnv* env, jclass, jint ndev)
 {

@@ -114,6 +114,15 @@ final class MvsimNative
 	static native void deconvolve( long ctx, FloatBuffer[] views, FloatBuffer[] weights, FloatBuffer[] psfs, long[] kdims, long[] dim,
 			int iterations, int method, boolean initFromPsi, float initValue, float minValue, float eps, double lambda, FloatBuffer psi );
 
+	/**
+	 * Bead detection (mvsim_detect_beads; include/mvsim.h states the recipe): DoG interest points with sub-voxel localisation.  img is a direct
+	 * FloatBuffer, or with u16 a direct ShortBuffer, of nx * ny * nz elements; peaks a direct ByteBuffer in native order of at least
+	 * 40 * capacity bytes that receives min(found, capacity) records {double x, y, z; float value; int flags; long voxel}.  Returns the
+	 * number found.  The shim checks every length and capacity first.
+	 */
+	static native long detectBeads( long ctx, java.nio.Buffer img, boolean u16, long[] dim, double sigma1X, double sigma1Y, double sigma1Z,
+			double sigma2X, double sigma2Y, double sigma2Z, float threshold, int maxMoves, long capacity, java.nio.ByteBuffer peaks );
+
 	/** Fused loop body of SimulateMultiViewDataset.main (:570-585); rot/att/con may be null (then they never leave HBM). */
 	static native double simulateView( long ctx, FloatBuffer gt, long[] dim, FloatBuffer psf, long[] kdim,
 			int axis, int degrees, double delta, float minValue, float targetAverage, int inc, float snr, long seed, int stream,

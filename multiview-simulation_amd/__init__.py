@@ -27,9 +27,11 @@ from . import _lib
 from ._lib import DeconParams, DeconStat, IntervalJob, MvsimError, MvsimNoDeviceError, Sphere, Timings, ViewOutputs, ViewParams  # noqa: F401
 from .aberrations import ContextAberrations
 from .deconvolution import ContextDeconvolution, MultiViewDeconvolution, decon_geometry, decon_params, flip_psf  # noqa: F401
+from .detection import ContextDetection, DifferenceOfGaussian, dog_geometry, dog_params, dog_taps  # noqa: F401
+from ._lib import DogParams  # noqa: F401
 from .phantoms import ContextPhantoms
 
-__all__ = ["AffineTransform3D", "Context", "DeconParams", "MultiViewDeconvolution", "Group", "Hessian", "HypersphereCollectionRealRandomAccessible", "JavaRandom", "Lightsheet",
+__all__ = ["AffineTransform3D", "Context", "DeconParams", "DifferenceOfGaussian", "DogParams", "MultiViewDeconvolution", "Group", "Hessian", "HypersphereCollectionRealRandomAccessible", "JavaRandom", "Lightsheet",
            "PerlinNoiseRealRandomAccessible", "PointRejectionSampling", "RayTracingTest", "Raytrace", "RefractiveIndexMap", "ClearingMap", "SimpleCalculatedRealRandomAccessible", "SimulateBeads",
            "SimulateBeads2", "SimulateMultiViewAberrations", "SimulateMultiViewDataset", "Tools", "VolumeInjection", "broadcast_plan", "default_context", "MvsimError", "MvsimNoDeviceError", "ViewParams", "shard_views",
            "version"]
@@ -148,11 +150,12 @@ def _ptr(a: np.ndarray) -> C.c_void_p:
     return C.c_void_p(a.ctypes.data)
 
 
-class Context(ContextAberrations, ContextPhantoms, ContextDeconvolution):
+class Context(ContextAberrations, ContextPhantoms, ContextDeconvolution, ContextDetection):
     """One ``mvsim_ctx``: bound to one GPU, not thread-safe.  (The refraction simulator's entry points -- refract3d,
     project_to_camera, hessian_at, volume_inject, ... -- are in aberrations.ContextAberrations, the procedural phantom's --
     perlin_at, spheres_raster, rejection_sample, ... -- in phantoms.ContextPhantoms, the multi-view deconvolution's --
-    deconvolve, deconvolve_dev, decon_ratio_dev, decon_update_dev -- in deconvolution.ContextDeconvolution.)"""
+    deconvolve, deconvolve_dev, decon_ratio_dev, decon_update_dev -- in deconvolution.ContextDeconvolution, the bead detector's --
+    detect_beads, detect_beads_dev, dog_dev, find_peaks_dev, localise_peaks_dev -- in detection.ContextDetection.)"""
 
     def __init__(self, device: int | None = None):
         self._h = C.c_void_p()
@@ -188,7 +191,7 @@ class Context(ContextAberrations, ContextPhantoms, ContextDeconvolution):
     def set_option(self, name: str, value) -> None:
         """Run-time switch of this context (mvsim_set_option): fft_zpass, fft_backend, fft_pad, fused_rotate,
         poisson_queue, poisson_queue_share, early_sum, graph, fuse_tail, psf_overlap, tail_overlap, attenuate, broadcast, view_batch,
-        view_lanes, acq_transfer, host_threads, sphere_walk (include/mvsim.h and DESIGN.md list them with their values)."""
+        view_lanes, acq_transfer, host_threads, sphere_walk, dog_pass (include/mvsim.h and DESIGN.md list them with their values)."""
         if isinstance(value, bool):
             value = "1" if value else "0"
         _lib.check(self._L.mvsim_set_option(self._h, name.encode(), str(value).encode()))

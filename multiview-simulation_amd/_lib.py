@@ -101,6 +101,21 @@ class DeconStat(C.Structure):
         return {"sum_psi": float(self.sum_psi), "max_change": float(self.max_change), "n_floored": int(self.n_floored)}
 
 
+class DogParams(C.Structure):
+    """mvsim_dog_params: the settings of the bead detector (mvsim_dog_params_default fills them)."""
+    _fields_ = [("sigma1", C.c_double * 3), ("sigma2", C.c_double * 3), ("threshold", C.c_float), ("max_moves", C.c_int32)]
+
+
+class Peak(C.Structure):
+    """mvsim_peak: one localised detection."""
+    _fields_ = [("pos", C.c_double * 3), ("value", C.c_float), ("flags", C.c_int32), ("voxel", C.c_int64)]
+
+
+MVSIM_SRC_F32, MVSIM_SRC_U16 = 0, 1
+MVSIM_DOG_MAX_TAPS = 63
+MVSIM_PEAK_SINGULAR, MVSIM_PEAK_FROZEN, MVSIM_PEAK_CAPPED, MVSIM_PEAK_OUTSIDE = 1, 2, 4, 8
+
+
 class Timings(C.Structure):
     _fields_ = [(n, C.c_float) for n in
                 ("rotate_ms", "attenuate_ms", "psf_ms", "convolve_ms", "adjust_ms", "extract_ms", "total_ms",
@@ -286,6 +301,14 @@ SIGNATURES = {
                                        C.POINTER(DeconParams), _vp, C.POINTER(DeconStat)]),
     "mvsim_deconvolve": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i64p, C.c_int, _i64p,
                                    C.POINTER(DeconParams), _vp, C.POINTER(DeconStat)]),
+    "mvsim_dog_params_default": (None, [C.POINTER(DogParams)]),
+    "mvsim_dog_taps": (C.c_int, [C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "mvsim_dog_geometry": (C.c_int, [_i64p]),
+    "mvsim_dog_dev": (C.c_int, [_vp, _vp, C.c_int, _i64p, C.POINTER(DogParams), _vp]),
+    "mvsim_find_peaks_dev": (C.c_int, [_vp, _vp, _i64p, C.c_float, C.c_int64, _vp, _vp]),
+    "mvsim_localise_peaks_dev": (C.c_int, [_vp, _vp, _i64p, _vp, _vp, C.c_int64, C.c_int, _vp]),
+    "mvsim_detect_beads_dev": (C.c_int, [_vp, _vp, C.c_int, _i64p, C.POINTER(DogParams), C.c_int64, _vp, _vp]),
+    "mvsim_detect_beads": (C.c_int, [_vp, _vp, C.c_int, _i64p, C.POINTER(DogParams), C.c_int64, _vp, _vp]),
 }
 
 _lib = None

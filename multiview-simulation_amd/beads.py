@@ -157,6 +157,7 @@ class SimulateBeads:
         self.sigma = [float(s) for s in sigma]
         self.rnd = JavaRandom(535)                                  # :69
         self.imgs = None
+        self.points = None                                          # drawn once, by getImgs or detect
 
     def matrices(self) -> np.ndarray:
         """axisRotation(rangeSimulation, axis, angle) of every angle (:138), (V, 3, 4)."""
@@ -168,8 +169,9 @@ class SimulateBeads:
     def getImgs(self) -> list:
         """:83-95 -- one float image per angle, rendered together (the transforms are applied on the GPU)."""
         if self.imgs is None:
-            points = self.randomPoints(self.numPoints, self.rangeSimulation, self.rnd)
-            self.imgs = _ctx().render_beads(points, self.intervalRender, self.sigma, matrices=self.matrices())["f32"]
+            if self.points is None:
+                self.points = self.randomPoints(self.numPoints, self.rangeSimulation, self.rnd)
+            self.imgs = _ctx().render_beads(self.points, self.intervalRender, self.sigma, matrices=self.matrices())["f32"]
         return self.imgs
 
     def getImage(self, view: int) -> np.ndarray:
@@ -182,6 +184,15 @@ class SimulateBeads:
         if normalize:
             _ctx().beads_normalize(img)
         return img
+
+    def detect(self, view: int, detector=None, u16: bool = False):
+        """Render view ``view`` on the device and detect its beads there, without a download of the image (the library's own
+        consumer of the bead images; the reference has none).  Returns (peaks, n_found, truth): ``truth`` are the view's true
+        bead positions in image coordinates.  The cloud is drawn once, as getImgs draws it."""
+        from .detection import detect_rendered
+        if self.points is None:
+            self.points = self.randomPoints(self.numPoints, self.rangeSimulation, self.rnd)
+        return detect_rendered(_ctx(), self.points, self.matrices()[view], self.intervalRender, self.sigma, detector, u16)
 
     @staticmethod
     def randomPoints(numPoints: int, range_, rnd) -> np.ndarray:
@@ -326,6 +337,13 @@ class SimulateBeads2:
             m = self.transform(*key).m
             self.imgs[key] = _ctx().render_beads(self.points, self.intervalRender, self.sigma, matrices=m[None])["f32"][0]
         return self.imgs[key]
+
+    def detect(self, tp: int, angle: int, channel: int, tile: int, illumination: int, detector=None, u16: bool = False):
+        """Render this view on the device and detect its beads there, without a download of the image.  Returns
+        (peaks, n_found, truth) as SimulateBeads.detect does."""
+        from .detection import detect_rendered
+        m = self.transform(tp, angle, channel, tile, illumination).m
+        return detect_rendered(_ctx(), self.points, m, self.intervalRender, self.sigma, detector, u16)
 
     def getImage(self, tp: int, angle: int, channel: int, tile: int, illumination: int) -> np.ndarray:
         """LegacySimulatedBeadsImgLoader2.getImage (:65-85): uint16, written by the kernel directly."""

@@ -52,6 +52,7 @@ int parse_option(Options& o, const char* name, const char* value)
     if (n == "exp") return number(2, 0, 15, &o.exp);                                  // A/B bits of tools/ and the tests (common.h)
     if (n == "beads_pair_cap") return number(10, 1024, 1LL << 31, &o.beads_pair_cap);  // pairs per chunk of the bead renderer
     if (n == "reject_batch") return number(7, 1, 1LL << 20, &o.reject_batch, 0);      // trials per launch of the rejection sampler
+    if (n == "dog_pass") return word({{"both", 0}, {"xy", 1}, {"z", 2}}, &o.dog_pass);
     if (n == "sphere_walk") return word({{"host", 0}, {"device", 1}, {"device_only", 2}, {"auto", -1}}, &o.sphere_walk);   // who walks the large sphere's random stream
     if (n == "fuse_tail") return flag(&o.fuse_tail);
     if (n == "psf_overlap") return flag(&o.psf_overlap);

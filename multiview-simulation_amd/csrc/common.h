@@ -203,6 +203,8 @@ struct Options {
     bool    skip_empty = true;         // convolution passes skip planes the fused rotate kernel found empty (exact; option for A/B runs)
     int64_t beads_pair_cap = (int64_t)1 << 28;   // bead renderer and volume injection: (brick, item) pairs one chunk may bin; larger calls run in chunks (beads.hip, aberrations.hip)
     int64_t reject_batch = 0;          // rejection sampler: trials per launch (0 = auto: 4 per wanted sample, 4096 .. 2^20) (procedural.hip)
+    int     dog_pass = 0;              // the DoG kernels a call launches (detect.hip): 0 both, 1 the xy kernel alone, 2 the z kernel alone -- for
+                                       // timing one kernel kind (tools/bench_detect.py); only 0 leaves a valid D
     int     sphere_walk = -1;          // the java.util.Random walk over the large sphere: 0 on the host, 1 on the device (sphere_walk.hip; the host
                                        // walk where the device walk does not vouch for a case; 2: MVSIM_EINVAL there), -1 = each call's default: drawSpheres host, multiSpheres device
 };
@@ -254,6 +256,7 @@ struct mvsim_ctx {
     mvsim::DevBuf decon_work[2];            // multi-view deconvolution (api_decon.cpp): the blurred estimate / ratio, and the correlation
     mvsim::DevBuf decon_psf;                // ... every view's normalised PSF and its flipped twin, uploaded once per call
     mvsim::DevBuf decon_stat;               // ... per-block partials, per-view sums and the statistics of every step of a call
+    mvsim::DevBuf detect_buf[6];            // bead detector (api_detect.cpp): the two half-blurred volumes, D, the peak list, block counts + offsets + ballots, scan temp
     int64_t       weight_dim[3] = {0, 0, 0};
     mvsim::DevBuf host_gt, host_rot, host_att, host_con;   // device twins of the host-buffer simulate_view (grow-only)
     mvsim::DevBuf partials;                 // doubles: block partial sums + [sum, corr]
@@ -356,6 +359,7 @@ template <class F> inline void mvsim_ctx::each_workspace(F&& f)
         f(*b, 0);
     f(partials, WS_KEPT);
     f(partials_e, WS_KEPT);
+    for (mvsim::DevBuf& b : detect_buf) f(b, 0);
     for (mvsim::DevBuf& b : beads_buf) f(b, WS_NO_EPOCH);
     for (mvsim::DevBuf& b : proc_buf) f(b, WS_NO_EPOCH);
     for (mvsim::DevBuf& b : walk_buf) f(b, WS_NO_EPOCH);
