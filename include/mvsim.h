@@ -606,6 +606,130 @@ int mvsim_detect_beads_dev(mvsim_ctx* ctx, const void* img_dev, int src_type, co
 int mvsim_detect_beads(mvsim_ctx* ctx, const void* img, int src_type, const int64_t dim[3], const mvsim_dog_params* params,
                        int64_t capacity, mvsim_peak* peaks, int64_t* n_found);
 
+/* ---- bead registration: geometric descriptors, ratio-test matching, RANSAC, affine fit ------------------------------------------
+ * The consumer of mvsim_detect_beads: two device-resident lists of positions in two coordinate frames go in, the affine transform
+ * from list A to list B comes out.  The reference has no matcher; the recipe is this one, and every arithmetic step is stated so that
+ * a literal restatement reproduces the result bit for bit.  All arithmetic is fp64, every + - * / sqrt an operation of its own (no
+ * fused multiply-add), sqrt correctly rounded.
+ * A point list is n positions of 3 doubles (x, y, z) at a byte stride >= 24 that is a multiple of 8: 24 for a packed array, 40 for
+ * the mvsim_peak records of the detector (pos comes first).  n = min(max(*n_dev, 0), capacity) is read from DEVICE memory by the
+ * kernels, so detection and registration chain on one stream without a synchronisation; capacity <= MVSIM_REG_MAX_POINTS.  The
+ * method is all-pairs.  The squared distance of two points is d2 = (dx*dx + dy*dy) + dz*dz.
+ * 1. Neighbours.  K = 3 + redundancy.  For every point whose three coordinates are finite: the K OTHER finite points (by index; an
+ *    exact duplicate at d2 = 0 is a neighbour like any other) with the smallest (d2, index), in that order.  A non-finite point is
+ *    nobody's neighbour and has no neighbours.  Missing ranks are index -1 with d2 = +inf.  A point with a missing rank has no
+ *    descriptors.
+ * 2. Descriptors.  The S = C(K, 3) rank triples (i < j < k) in lexicographic order (mvsim_descriptor_subsets; S = 1, 4, 10).  For a
+ *    point p and the neighbours a, b, c of a triple the descriptor is the 6 doubles |pa|, |pb|, |pc|, |ab|, |ac|, |bc|, each the sqrt
+ *    of a d2.  Descriptor s of point i is at doubles 6 (S i + s) ...; a point without descriptors holds NaN in all of them, and a
+ *    point whose FIRST double is NaN counts as having none.
+ * 3. Matching A -> B.  The distance of two descriptors u, w is ((((( e0 + e1) + e2) + e3) + e4) + e5) with e_t = (u_t - w_t)*(u_t - w_t).
+ *    v(a, b) is the smallest distance over the S x S descriptor pairs of a and b, NaN distances left out, +inf when none is left.
+ *    b1 and b2 are the two described points of B with the smallest (v, index).  a yields the candidate (a, b1) when b2 exists and
+ *    v(a, b1) * ratio2 < v(a, b2), ratio2 = ratio * ratio computed once on the host.  The candidates are listed in ascending a
+ *    (count, scan, emit: no atomics); n_candidates is the total and only the first min(n_candidates, capacity) are written.
+ * 4. Affine fit over an ordered selection of candidates (p -> q), candidate i holding p = A[a_i], q = B[b_i].  EVERY sum below is
+ *    taken the same way: over chunks of MVSIM_REG_FIT_CHUNK (256) consecutive candidate indices, unselected candidates skipped; a
+ *    chunk's sum starts from +0.0 and adds ascending, the total starts from +0.0 and adds the chunks' sums ascending.
+ *        n = number selected;  cp = (sum p) / n,  cq = (sum q) / n                    (6 sums, 6 divisions by (double)n)
+ *        p' = p - cp, q' = q - cq
+ *        Sm = sum p' p'^T: m00 = xx, m01 = m10 = xy, m02 = m20 = xz, m11 = yy, m12 = m21 = yz, m22 = zz       (6 sums of products)
+ *        C  = sum q' p'^T: c_rc = sum q'_r p'_c                                                                  (9 sums of products)
+ *        det and the inverse i_rc of Sm exactly as step 5 of the detector writes them (adjugate times idet = 1.0 / det)
+ *        A_rc = ((c_r0 * i_0c + c_r1 * i_1c) + c_r2 * i_2c)
+ *        t_r  = cq_r - ((A_r0 * cp_x + A_r1 * cp_y) + A_r2 * cp_z)
+ *    n < 4, or det zero or non-finite: no model.  The model is the 3 x 4 row-major matrix m = [A | t].
+ * 5. RANSAC over M = min(n_candidates, capacity) candidates.  M < 4 sets FEW_CANDIDATES.  Hypothesis h = 0 .. hypotheses-1 owns a
+ *    java.util.Random(seed + h) and draws nextInt(M) until it holds 4 distinct indices, at most 32 draws, otherwise it is void.  The 4
+ *    indices sorted ascending are fitted by step 4.  A candidate is an inlier of a model when e2 <= eps2 with
+ *    e_r = (((m_r0 * p_x + m_r1 * p_y) + m_r2 * p_z) + m_r3) - q_r,  e2 = (e_x*e_x + e_y*e_y) + e_z*e_z,  eps2 = max_epsilon * max_epsilon
+ *    computed once on the host; a NaN e2 is no inlier, and a candidate whose a or b is no index of its list holds NaN positions.  A
+ *    void or model-less hypothesis counts 0.  The best hypothesis has the highest count, ties go to the lowest h.  M < 4 or a best
+ *    count below 4: NO_MODEL, m is NaN, best_hypothesis -1, no inliers, and step 6 does not run.
+ * 6. Refit.  model = the best hypothesis's, mask = its inliers, refits = 0.  Repeat: if refits == max_refits set CAPPED and stop; fit
+ *    the masked candidates by step 4 -- no model: set NO_MODEL, keep the model and stop; refits += 1; take the new model, recompute the
+ *    mask; stop when it is the mask of the round before.  n_inliers counts the final mask -- always the inliers of the reported
+ *    model --, mean_error is (sum of sqrt(e2) over the inliers, summed as in step 4) / n_inliers, max_error the largest sqrt(e2)
+ *    (both NaN without inliers).  FEW_INLIERS when n_inliers < min_inliers or (double)n_inliers < min_inlier_ratio * (double)M; the
+ *    matrix is reported all the same. */
+#define MVSIM_REG_MAX_POINTS 65536
+#define MVSIM_REG_FIT_CHUNK  256
+#define MVSIM_REG_MAX_REFITS 4096   /* the refit rounds run inside one kernel: a mask that keeps alternating must end */
+#define MVSIM_REG_FEW_CANDIDATES 1
+#define MVSIM_REG_NO_MODEL       2
+#define MVSIM_REG_CAPPED         4
+#define MVSIM_REG_FEW_INLIERS    8
+typedef struct mvsim_match_params {
+    double  ratio;             /* default 3.0 (a convention); >= 1 */
+    double  max_epsilon;       /* default 5.0 voxels; > 0 */
+    double  min_inlier_ratio;  /* default 0.1 */
+    int64_t seed;              /* default 0: hypothesis h draws from java.util.Random(seed + h) */
+    int32_t redundancy;        /* default 1; 0 .. 2 */
+    int32_t hypotheses;        /* default 10000; >= 1 */
+    int32_t max_refits;        /* default 8; 0 .. MVSIM_REG_MAX_REFITS */
+    int32_t min_inliers;       /* default 12; >= 4 */
+} mvsim_match_params;          /* 48 bytes */
+typedef struct mvsim_match {
+    int32_t a, b;              /* indices into list A and list B */
+    double  v_best, v_second;  /* v(a, b1), v(a, b2) */
+} mvsim_match;                 /* 24 bytes */
+typedef struct mvsim_registration {
+    double  m[12];             /* 3 x 4 row-major, A -> B: q = m[:, :3] p + m[:, 3] */
+    double  mean_error, max_error;   /* over the inliers, voxels */
+    int64_t n_a, n_b;          /* points with descriptors (0 from mvsim_ransac_affine_dev, which sees no descriptors) */
+    int64_t n_candidates;      /* the total, also beyond the capacity */
+    int64_t n_inliers;
+    int64_t best_hypothesis;   /* -1: none */
+    int32_t refits, flags;     /* MVSIM_REG_* */
+} mvsim_registration;          /* 160 bytes */
+void mvsim_match_params_default(mvsim_match_params* p);
+/* Host only, no context.  The launch geometry for lists of capacity_a and capacity_b points: out = {queries (lanes) per block of the
+ * two all-pairs kernels, points per staged tile of k_knn, splits of list A's candidate range for capacity_a, tiles per split;
+ * B points per staged tile of k_match, splits of list B for (capacity_a, capacity_b, redundancy), tiles per split; candidates per
+ * staged tile of the RANSAC kernel}.  The split rule: with Q blocks of queries and T tiles, splits = min(T, max(1, ceil(1024 / Q))),
+ * tiles per split = ceil(T / splits), and only the ceil(T / tiles per split) splits that own a tile are launched.  (d2, index) and
+ * (v, index) are total orders, so every split gives the same bits. */
+int mvsim_match_geometry(int64_t capacity_a, int64_t capacity_b, int redundancy, int64_t out[8]);
+/* Host only: the S = C(3 + redundancy, 3) rank triples of step 2, 3 ints each; *n_subsets = S.  triples holds 30 ints. */
+int mvsim_descriptor_subsets(int redundancy, int32_t* triples, int* n_subsets);
+/* Host only, no context: step 4 over n pairs p[i] -> q[i] (packed, 3 doubles each) selected by mask (one byte per pair; NULL: all).
+ * Returns MVSIM_OK with *has_model = 1 and m filled, or *has_model = 0 and m untouched. */
+int mvsim_fit_affine(const double* p, const double* q, const unsigned char* mask_or_null, int64_t n, double m[12], int* has_model);
+/* Step 1 on a device list: idx_dev receives K int32 and d2_dev K doubles per point, for the first n points (entries past them are
+ * not written).  Asynchronous on the context's stream, like every _dev call below. */
+int mvsim_knn_dev(mvsim_ctx* ctx, const void* pos_dev, int64_t stride, const int64_t* n_dev, int64_t capacity, int redundancy,
+                  int32_t* idx_dev, double* d2_dev);
+/* Step 2 from the positions and the neighbour indices of step 1: 6 S doubles per point for the first n points; *n_described_dev (one
+ * int64 in DEVICE memory) the number of points with descriptors. */
+int mvsim_bead_descriptors_dev(mvsim_ctx* ctx, const void* pos_dev, int64_t stride, const int64_t* n_dev, int64_t capacity, int redundancy,
+                               const int32_t* idx_dev, double* desc_dev, int64_t* n_described_dev);
+/* Step 3 over two descriptor arrays as step 2 leaves them: candidates_dev receives min(n_candidates, capacity) records,
+ * *n_candidates_dev (one int64 in DEVICE memory) the total.  1 <= capacity <= MVSIM_REG_MAX_POINTS. */
+int mvsim_match_descriptors_dev(mvsim_ctx* ctx, const double* desc_a_dev, const int64_t* n_a_dev, int64_t capacity_a,
+                                const double* desc_b_dev, const int64_t* n_b_dev, int64_t capacity_b, int redundancy, double ratio,
+                                int64_t capacity, mvsim_match* candidates_dev, int64_t* n_candidates_dev);
+/* Steps 5 and 6 over any candidate list: result_dev receives one mvsim_registration, mask_dev_or_null one byte per candidate
+ * (min(n_candidates, capacity) of them; 1 = inlier).  Of params, redundancy and ratio are checked and not used. */
+int mvsim_ransac_affine_dev(mvsim_ctx* ctx, const void* pos_a_dev, int64_t stride_a, const int64_t* n_a_dev, int64_t capacity_a,
+                            const void* pos_b_dev, int64_t stride_b, const int64_t* n_b_dev, int64_t capacity_b,
+                            const mvsim_match* candidates_dev, const int64_t* n_candidates_dev, int64_t capacity,
+                            const mvsim_match_params* params, mvsim_registration* result_dev, unsigned char* mask_dev_or_null);
+/* The whole recipe; every intermediate lives in context workspaces that mvsim_release_caches frees.  The candidate list has
+ * capacity_a entries (a point of A yields at most one); candidates_dev_or_null receives it (capacity_a records, n_candidates of
+ * them written), mask_dev_or_null one byte per candidate.
+ * MVSIM_EINVAL: a null pointer, a stride below 24 or no multiple of 8, a capacity <= 0 or above MVSIM_REG_MAX_POINTS, redundancy
+ * outside 0 .. 2, ratio, max_epsilon or min_inlier_ratio not finite, ratio < 1, max_epsilon <= 0, hypotheses <= 0, max_refits < 0
+ * or above MVSIM_REG_MAX_REFITS, min_inliers < 4. */
+int mvsim_register_beads_dev(mvsim_ctx* ctx, const void* pos_a_dev, int64_t stride_a, const int64_t* n_a_dev, int64_t capacity_a,
+                             const void* pos_b_dev, int64_t stride_b, const int64_t* n_b_dev, int64_t capacity_b,
+                             const mvsim_match_params* params, mvsim_registration* result_dev, mvsim_match* candidates_dev_or_null,
+                             unsigned char* mask_dev_or_null);
+/* The same with HOST buffers; synchronous.  n_a, n_b >= 0 points; candidates_or_null holds max(n_a, 1) records, mask_or_null as many
+ * bytes; min(result->n_candidates, n_a) of each are written. */
+int mvsim_register_beads(mvsim_ctx* ctx, const void* pos_a, int64_t stride_a, int64_t n_a, const void* pos_b, int64_t stride_b, int64_t n_b,
+                         const mvsim_match_params* params, mvsim_registration* result, mvsim_match* candidates_or_null,
+                         unsigned char* mask_or_null);
+
 /* ---- extractSlices over Intervals of volumes that stay on the device (SimulateTileStitching.java:131-189) ---------------
  * Views.zeroMin(Views.interval(con, min, max)) run through extractSlices: output voxel (x, y, k) of the contiguous tile
  * tx x ty x mvsim_extract_nz(tz, inc), t_d = max_d - min_d + 1, is f(in[(min_x + x) + Nx ((min_y + y) + Ny (min_z + k inc))]).

@@ -17,6 +17,7 @@
 #include <jni.h>
 
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "mvsim.h"
@@ -874,6 +875,47 @@ JNIEXPORT jlong JNICALL JNI_FN(detectBeads)(JNIEnv* env, jclass, jlong h, jobjec
     int64_t found = 0;
     throw_for(env, mvsim_detect_beads(ctx_of(h), src, u16 ? MVSIM_SRC_U16 : MVSIM_SRC_F32, d.d, &p, capacity, static_cast<mvsim_peak*>(out), &found));
     return static_cast<jlong>(found);
+}
+
+// mvsim_register_beads: bead-based registration A -> B of two packed position lists (direct DoubleBuffers of 3 n doubles).  result: a
+// direct ByteBuffer of at least 160 bytes that receives one mvsim_registration {double m[12], meanError, maxError; long nA, nB,
+// nCandidates, nInliers, bestHypothesis; int refits, flags} in native byte order; candidates (or null): at least 24 * max(nA, 1) bytes
+// for the mvsim_match records {int a, b; double vBest, vSecond}; mask (or null): at least max(nA, 1) bytes, one per candidate.  Returns
+// the number of candidates.  Every length, null and capacity is checked before the C ABI sees a pointer.
+JNIEXPORT jlong JNICALL JNI_FN(registerBeads)(JNIEnv* env, jclass, jlong h, jobject pos_a, jlong n_a, jobject pos_b, jlong n_b, jint redundancy,
+                                              jdouble ratio, jdouble max_epsilon, jdouble min_inlier_ratio, jlong seed, jint hypotheses,
+                                              jint max_refits, jint min_inliers, jobject result, jobject candidates, jobject mask)
+{
+    if (n_a < 0 || n_a > MVSIM_REG_MAX_POINTS || n_b < 0 || n_b > MVSIM_REG_MAX_POINTS) {
+        throw_new(env, "java/lang/IllegalArgumentException", "registerBeads: list lengths must be in 0 .. 65536");
+        return 0;
+    }
+    const void* pa = any_ptr(env, pos_a, 3 * n_a, "registerBeads: position buffer A missing or smaller than 3 nA doubles");
+    if (!pa) return 0;
+    const void* pb = any_ptr(env, pos_b, 3 * n_b, "registerBeads: position buffer B missing or smaller than 3 nB doubles");
+    if (!pb) return 0;
+    void* res = any_ptr(env, result, static_cast<jlong>(sizeof(mvsim_registration)), "registerBeads: result buffer missing or smaller than 160 bytes");
+    if (!res) return 0;
+    const jlong slots = n_a > 0 ? n_a : 1;
+    void* cand = nullptr;
+    void* msk = nullptr;
+    if (candidates) {
+        cand = any_ptr(env, candidates, slots * static_cast<jlong>(sizeof(mvsim_match)), "registerBeads: candidate buffer smaller than 24 * max(nA, 1) bytes");
+        if (!cand) return 0;
+    }
+    if (mask) {
+        msk = any_ptr(env, mask, slots, "registerBeads: mask buffer smaller than max(nA, 1) bytes");
+        if (!msk) return 0;
+    }
+    mvsim_match_params p;
+    mvsim_match_params_default(&p);
+    p.redundancy = redundancy; p.ratio = ratio; p.max_epsilon = max_epsilon; p.min_inlier_ratio = min_inlier_ratio; p.seed = seed;
+    p.hypotheses = hypotheses; p.max_refits = max_refits; p.min_inliers = min_inliers;
+    mvsim_registration r;
+    const int rc = mvsim_register_beads(ctx_of(h), pa, 24, n_a, pb, 24, n_b, &p, &r, static_cast<mvsim_match*>(cand), static_cast<unsigned char*>(msk));
+    if (rc != MVSIM_OK) { throw_for(env, rc); return 0; }
+    std::memcpy(res, &r, sizeof(r));
+    return static_cast<jlong>(r.n_candidates);
 }
 
 // ---- mvsim_group_* -------------------------------------------------------------------------------------------------

@@ -123,6 +123,17 @@ final class MvsimNative
 	static native long detectBeads( long ctx, java.nio.Buffer img, boolean u16, long[] dim, double sigma1X, double sigma1Y, double sigma1Z,
 			double sigma2X, double sigma2Y, double sigma2Z, float threshold, int maxMoves, long capacity, java.nio.ByteBuffer peaks );
 
+	/**
+	 * Bead registration (mvsim_register_beads; include/mvsim.h states the recipe): geometric descriptors, ratio-test matching, RANSAC and an
+	 * affine refit from list A to list B.  posA / posB are direct DoubleBuffers of 3 n doubles (x, y, z per point); result a direct
+	 * ByteBuffer in native order of at least 160 bytes that receives {double m[12], meanError, maxError; long nA, nB, nCandidates, nInliers,
+	 * bestHypothesis; int refits, flags}; candidates (or null) at least 24 * max(nA, 1) bytes for records {int a, b; double vBest, vSecond};
+	 * mask (or null) at least max(nA, 1) bytes, one per candidate.  Returns the number of candidates.  The shim checks every length first.
+	 */
+	static native long registerBeads( long ctx, java.nio.DoubleBuffer posA, long nA, java.nio.DoubleBuffer posB, long nB, int redundancy,
+			double ratio, double maxEpsilon, double minInlierRatio, long seed, int hypotheses, int maxRefits, int minInliers,
+			java.nio.ByteBuffer result, java.nio.ByteBuffer candidates, java.nio.ByteBuffer mask );
+
 	/** Fused loop body of SimulateMultiViewDataset.main (:570-585); rot/att/con may be null (then they never leave HBM). */
 	static native double simulateView( long ctx, FloatBuffer gt, long[] dim, FloatBuffer psf, long[] kdim,
 			int axis, int degrees, double delta, float minValue, float targetAverage, int inc, float snr, long seed, int stream,

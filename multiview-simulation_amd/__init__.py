@@ -28,10 +28,11 @@ from ._lib import DeconParams, DeconStat, IntervalJob, MvsimError, MvsimNoDevice
 from .aberrations import ContextAberrations
 from .deconvolution import ContextDeconvolution, MultiViewDeconvolution, decon_geometry, decon_params, flip_psf  # noqa: F401
 from .detection import ContextDetection, DifferenceOfGaussian, dog_geometry, dog_params, dog_taps  # noqa: F401
-from ._lib import DogParams  # noqa: F401
+from ._lib import DogParams, MatchParams  # noqa: F401
+from .registration import BeadRegistration, ContextRegistration, descriptor_subsets, fit_affine, match_geometry, match_params  # noqa: F401
 from .phantoms import ContextPhantoms
 
-__all__ = ["AffineTransform3D", "Context", "DeconParams", "DifferenceOfGaussian", "DogParams", "MultiViewDeconvolution", "Group", "Hessian", "HypersphereCollectionRealRandomAccessible", "JavaRandom", "Lightsheet",
+__all__ = ["AffineTransform3D", "BeadRegistration", "Context", "DeconParams", "DifferenceOfGaussian", "DogParams", "MatchParams", "MultiViewDeconvolution", "Group", "Hessian", "HypersphereCollectionRealRandomAccessible", "JavaRandom", "Lightsheet",
            "PerlinNoiseRealRandomAccessible", "PointRejectionSampling", "RayTracingTest", "Raytrace", "RefractiveIndexMap", "ClearingMap", "SimpleCalculatedRealRandomAccessible", "SimulateBeads",
            "SimulateBeads2", "SimulateMultiViewAberrations", "SimulateMultiViewDataset", "Tools", "VolumeInjection", "broadcast_plan", "default_context", "MvsimError", "MvsimNoDeviceError", "ViewParams", "shard_views",
            "version"]
@@ -150,12 +151,14 @@ def _ptr(a: np.ndarray) -> C.c_void_p:
     return C.c_void_p(a.ctypes.data)
 
 
-class Context(ContextAberrations, ContextPhantoms, ContextDeconvolution, ContextDetection):
+class Context(ContextAberrations, ContextPhantoms, ContextDeconvolution, ContextDetection, ContextRegistration):
     """One ``mvsim_ctx``: bound to one GPU, not thread-safe.  (The refraction simulator's entry points -- refract3d,
     project_to_camera, hessian_at, volume_inject, ... -- are in aberrations.ContextAberrations, the procedural phantom's --
     perlin_at, spheres_raster, rejection_sample, ... -- in phantoms.ContextPhantoms, the multi-view deconvolution's --
     deconvolve, deconvolve_dev, decon_ratio_dev, decon_update_dev -- in deconvolution.ContextDeconvolution, the bead detector's --
-    detect_beads, detect_beads_dev, dog_dev, find_peaks_dev, localise_peaks_dev -- in detection.ContextDetection.)"""
+    detect_beads, detect_beads_dev, dog_dev, find_peaks_dev, localise_peaks_dev -- in detection.ContextDetection, the bead
+    registration's -- register_beads, register_beads_dev, knn_dev, bead_descriptors_dev, match_descriptors_dev, ransac_affine_dev -- in
+    registration.ContextRegistration.)"""
 
     def __init__(self, device: int | None = None):
         self._h = C.c_void_p()

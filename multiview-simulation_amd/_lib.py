@@ -111,6 +111,26 @@ class Peak(C.Structure):
     _fields_ = [("pos", C.c_double * 3), ("value", C.c_float), ("flags", C.c_int32), ("voxel", C.c_int64)]
 
 
+class MatchParams(C.Structure):
+    """mvsim_match_params: the settings of the bead registration (mvsim_match_params_default fills them)."""
+    _fields_ = [("ratio", C.c_double), ("max_epsilon", C.c_double), ("min_inlier_ratio", C.c_double), ("seed", C.c_int64),
+                ("redundancy", C.c_int32), ("hypotheses", C.c_int32), ("max_refits", C.c_int32), ("min_inliers", C.c_int32)]
+
+
+class Match(C.Structure):
+    """mvsim_match: one candidate correspondence."""
+    _fields_ = [("a", C.c_int32), ("b", C.c_int32), ("v_best", C.c_double), ("v_second", C.c_double)]
+
+
+class Registration(C.Structure):
+    """mvsim_registration: what the RANSAC and refit stage reports."""
+    _fields_ = [("m", C.c_double * 12), ("mean_error", C.c_double), ("max_error", C.c_double), ("n_a", C.c_int64), ("n_b", C.c_int64),
+                ("n_candidates", C.c_int64), ("n_inliers", C.c_int64), ("best_hypothesis", C.c_int64), ("refits", C.c_int32),
+                ("flags", C.c_int32)]
+
+
+MVSIM_REG_MAX_POINTS, MVSIM_REG_FIT_CHUNK = 65536, 256
+MVSIM_REG_FEW_CANDIDATES, MVSIM_REG_NO_MODEL, MVSIM_REG_CAPPED, MVSIM_REG_FEW_INLIERS = 1, 2, 4, 8
 MVSIM_SRC_F32, MVSIM_SRC_U16 = 0, 1
 MVSIM_DOG_MAX_TAPS = 63
 MVSIM_PEAK_SINGULAR, MVSIM_PEAK_FROZEN, MVSIM_PEAK_CAPPED, MVSIM_PEAK_OUTSIDE = 1, 2, 4, 8
@@ -309,6 +329,18 @@ SIGNATURES = {
     "mvsim_localise_peaks_dev": (C.c_int, [_vp, _vp, _i64p, _vp, _vp, C.c_int64, C.c_int, _vp]),
     "mvsim_detect_beads_dev": (C.c_int, [_vp, _vp, C.c_int, _i64p, C.POINTER(DogParams), C.c_int64, _vp, _vp]),
     "mvsim_detect_beads": (C.c_int, [_vp, _vp, C.c_int, _i64p, C.POINTER(DogParams), C.c_int64, _vp, _vp]),
+    "mvsim_match_params_default": (None, [C.POINTER(MatchParams)]),
+    "mvsim_match_geometry": (C.c_int, [C.c_int64, C.c_int64, C.c_int, _i64p]),
+    "mvsim_descriptor_subsets": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
+    "mvsim_fit_affine": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "mvsim_knn_dev": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, _vp, _vp]),
+    "mvsim_bead_descriptors_dev": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, _vp, _vp, _vp]),
+    "mvsim_match_descriptors_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_int, C.c_double, C.c_int64, _vp, _vp]),
+    "mvsim_ransac_affine_dev": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, C.c_int64,
+                                          C.POINTER(MatchParams), _vp, _vp]),
+    "mvsim_register_beads_dev": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(MatchParams),
+                                           _vp, _vp, _vp]),
+    "mvsim_register_beads": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int64, C.POINTER(MatchParams), _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -194,6 +194,16 @@ class SimulateBeads:
             self.points = self.randomPoints(self.numPoints, self.rangeSimulation, self.rnd)
         return detect_rendered(_ctx(), self.points, self.matrices()[view], self.intervalRender, self.sigma, detector, u16)
 
+    def register(self, view_a: int, view_b: int, detector=None, matcher=None, u16: bool = False):
+        """Render views ``view_a`` and ``view_b`` on the device, detect their beads and register A -> B there; only the result is
+        downloaded.  Returns (registration, candidates, mask, truth): ``truth`` is the true A -> B transform in image coordinates
+        (3 x 4), q_B = M_B M_A^-1 (q_A + min) - min with min from intervalRender."""
+        from .registration import register_rendered
+        if self.points is None:
+            self.points = self.randomPoints(self.numPoints, self.rangeSimulation, self.rnd)
+        m = self.matrices()
+        return register_rendered(_ctx(), self.points, m[view_a], m[view_b], self.intervalRender, self.sigma, detector, matcher, u16)
+
     @staticmethod
     def randomPoints(numPoints: int, range_, rnd) -> np.ndarray:
         """:151-166 -- (numPoints, 3) doubles.  A JavaRandom is replayed natively and advanced; any other object with
@@ -344,6 +354,13 @@ class SimulateBeads2:
         from .detection import detect_rendered
         m = self.transform(tp, angle, channel, tile, illumination).m
         return detect_rendered(_ctx(), self.points, m, self.intervalRender, self.sigma, detector, u16)
+
+    def register(self, view_a, view_b, detector=None, matcher=None, u16: bool = False):
+        """Two views, each a (tp, angle, channel, tile, illumination) key: rendered, detected and registered A -> B on the device.
+        Returns (registration, candidates, mask, truth) as SimulateBeads.register does."""
+        from .registration import register_rendered
+        return register_rendered(_ctx(), self.points, self.transform(*view_a).m, self.transform(*view_b).m, self.intervalRender, self.sigma,
+                                 detector, matcher, u16)
 
     def getImage(self, tp: int, angle: int, channel: int, tile: int, illumination: int) -> np.ndarray:
         """LegacySimulatedBeadsImgLoader2.getImage (:65-85): uint16, written by the kernel directly."""

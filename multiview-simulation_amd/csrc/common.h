@@ -257,6 +257,7 @@ struct mvsim_ctx {
     mvsim::DevBuf decon_psf;                // ... every view's normalised PSF and its flipped twin, uploaded once per call
     mvsim::DevBuf decon_stat;               // ... per-block partials, per-view sums and the statistics of every step of a call
     mvsim::DevBuf detect_buf[6];            // bead detector (api_detect.cpp): the two half-blurred volumes, D, the peak list, block counts + offsets + ballots, scan temp
+    mvsim::DevBuf register_buf[4];          // bead registration (api_register.cpp): the stages' lists of one whole call, split partials, per-point bests, RANSAC pairs + key + mask
     int64_t       weight_dim[3] = {0, 0, 0};
     mvsim::DevBuf host_gt, host_rot, host_att, host_con;   // device twins of the host-buffer simulate_view (grow-only)
     mvsim::DevBuf partials;                 // doubles: block partial sums + [sum, corr]
@@ -360,6 +361,7 @@ template <class F> inline void mvsim_ctx::each_workspace(F&& f)
     f(partials, WS_KEPT);
     f(partials_e, WS_KEPT);
     for (mvsim::DevBuf& b : detect_buf) f(b, 0);
+    for (mvsim::DevBuf& b : register_buf) f(b, 0);
     for (mvsim::DevBuf& b : beads_buf) f(b, WS_NO_EPOCH);
     for (mvsim::DevBuf& b : proc_buf) f(b, WS_NO_EPOCH);
     for (mvsim::DevBuf& b : walk_buf) f(b, WS_NO_EPOCH);
