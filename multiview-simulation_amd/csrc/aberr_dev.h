@@ -395,20 +395,6 @@ __device__ __forceinline__ void camera_ray_start(unsigned long long state, long 
     vec[0] = 0.0; vec[1] = 0.0; vec[2] = 1.0;
 }
 
-// ---- the step list: slot records (ray * maxMoves + move) compacted in ray order, then move order --------------------------------
-__global__ __launch_bounds__(256) void k_compact_steps(const double* __restrict__ slot_xyz, const float* __restrict__ slot_val,
-                                                       const int* __restrict__ moves, const int* __restrict__ offs, int nrays, int max_moves,
-                                                       double* __restrict__ xyz, float* __restrict__ val)
-{
-    const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (s >= (long long)nrays * max_moves) return;
-    const int r = (int)(s / max_moves), mv = (int)(s - (long long)r * max_moves);
-    if (mv >= moves[r]) return;
-    const long long o = (long long)offs[r] + mv;
-    xyz[3 * o] = slot_xyz[3 * s]; xyz[3 * o + 1] = slot_xyz[3 * s + 1]; xyz[3 * o + 2] = slot_xyz[3 * s + 2];
-    val[o] = slot_val[s];
-}
-
 }  // namespace
 
 }  // namespace mvsim

@@ -13,20 +13,17 @@
 //              c (a^k - 1) / (a - 1) mod 2^48 by squaring): ray starts are bit-exact whatever the launch shape.
 //   refract3d  one ray per lane writes a step record (x, y, z, valueIm) per move at slot ray * maxMoves + move and its move count;
 //              an exclusive scan over the counts compacts the records into the step LIST in ray order, then move order.
-//   injection  VolumeInjection.addGaussian in list order into image and weight.  Float addition does not associate, so -- as for
-//              the bead images (beads.hip) -- nothing is scattered with atomics: cull (box per step, bricks it overlaps) -> scan ->
-//              emit (brick, step) pairs -> stable radix sort by brick -> one block per brick adds its steps in list order, every voxel
-//              owned by one lane.  Lists whose pairs exceed the option "beads_pair_cap" run in ranges, each continuing from the
-//              image and weight the previous one left: the same sequential sum.
-//   shared     the device functions of the ray step, the starts and the step list's compaction live in aberr_dev.h; raytrace.hip
-//              traces caller-supplied rays with them.
+//   injection  VolumeInjection.addGaussian in list order into image and weight.  Float addition does not associate, so nothing is
+//              scattered with atomics: the brick binner (bricks.h) gives every brick its steps in list order, and one block per
+//              brick adds them, every voxel owned by one lane.  Lists whose pairs exceed the option "beads_pair_cap" run in ranges,
+//              each continuing from the image and weight the previous one left: the same sequential sum.
+//   shared     the device functions of the ray step and the starts live in aberr_dev.h; raytrace.hip traces caller-supplied rays
+//              with them and owns the tail of a ray range (StepRanges: scan, compaction, step list, injection).
 //   camera     one block per camera pixel, lanes over the pixel's rays; the per-ray fp64 signals go to LDS and ONE lane adds them in
 //              ray order (avgValue, :242).
 #include "aberr_dev.h"
-#include "common.h"
+#include "bricks.h"
 #include "jrandom.h"
-
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -191,22 +188,11 @@ __global__ __launch_bounds__(256) void k_volume_project(const float* __restrict_
 }
 
 // ---- VolumeInjection.addGaussian (:175-197) in list order -------------------------------------------------------------------
-constexpr int BX = 32, BY = 8, BZ = 16;     // brick, as beads.hip: two 32-voxel rows per wave, four waves, 16 planes per lane
-constexpr int CH = 32;                      // steps per LDS chunk
-constexpr int NTAB = BX + BY + BZ;
-
 struct InjRec {
     double loc[3];
     double inten;
     int    lo[3], hi[3];    // box clipped to the image, inclusive
 };
-
-// Java Math.round(double) for finite values: floor, plus one when the fraction is >= 0.5
-__device__ __forceinline__ long long java_round_d(double x)
-{
-    const double f = floor(x);
-    return (long long)f + ((x - f) >= 0.5 ? 1 : 0);
-}
 
 __global__ __launch_bounds__(256) void k_inject_cull(const double* __restrict__ xyz, const double* __restrict__ inten, const float* __restrict__ val,
                                                      double sumw, long long n, InjRec* __restrict__ recs, uint32_t* __restrict__ counts, int nx,
@@ -214,24 +200,22 @@ __global__ __launch_bounds__(256) void k_inject_cull(const double* __restrict__ 
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const int dim[3] = {nx, ny, nz}, size[3] = {s0, s1, s2}, bs[3] = {BX, BY, BZ};
+    const int dim[3] = {nx, ny, nz}, size[3] = {s0, s1, s2};
     InjRec r;
     double v = val ? (double)val[i] : inten[i];
     if (sumw != 0.0) v = v / sumw;                               // addNormalizedGaussian (:168-173)
     r.inten = v;
-    uint32_t cnt = 1;
     for (int d = 0; d < 3; ++d) {
         const double p = xyz[3 * i + d];
         r.loc[d] = p;
         r.lo[d] = 1; r.hi[d] = 0;
-        if (!(fabs(p) < 1.0e9)) { cnt = 0; continue; }          // nowhere near the image (or NaN): every write is dropped
+        if (!(fabs(p) < 1.0e9)) continue;                        // nowhere near the image (or NaN): every write is dropped
         const long long lo = java_round_d(p) - size[d] / 2;      // getCursor (:147-160)
         const long long hi = lo + size[d] - 1;
-        const long long a = lo < 0 ? 0 : lo, b = hi > dim[d] - 1 ? dim[d] - 1 : hi;
-        r.lo[d] = (int)a;
-        r.hi[d] = (int)b;
-        cnt = a > b ? 0u : cnt * (uint32_t)(b / bs[d] - a / bs[d] + 1);
+        r.lo[d] = (int)(lo < 0 ? 0 : lo);
+        r.hi[d] = (int)(hi > dim[d] - 1 ? dim[d] - 1 : hi);
     }
+    const uint32_t cnt = bricks_overlapped(r.lo, r.hi);
     if (cnt == 0) { r.lo[0] = 1; r.hi[0] = 0; }
     recs[i] = r;
     counts[i] = cnt;
@@ -239,50 +223,18 @@ __global__ __launch_bounds__(256) void k_inject_cull(const double* __restrict__ 
 
 __global__ __launch_bounds__(256) void k_inject_emit(const InjRec* __restrict__ recs, const uint32_t* __restrict__ counts,
                                                      const uint32_t* __restrict__ offs, long long n, uint32_t* __restrict__ keys,
-                                                     uint32_t* __restrict__ vals, int nbx, int nby)
+                                                     uint32_t* __restrict__ vals, BrickGrid grid)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n || counts[i] == 0) return;
     const InjRec r = recs[i];
-    uint32_t o = offs[i];
-    for (int bz = r.lo[2] / BZ; bz <= r.hi[2] / BZ; ++bz)
-        for (int by = r.lo[1] / BY; by <= r.hi[1] / BY; ++by)
-            for (int bx = r.lo[0] / BX; bx <= r.hi[0] / BX; ++bx) {
-                keys[o] = (uint32_t)(bx + nbx * (by + nby * bz));
-                vals[o] = (uint32_t)i;
-                ++o;
-            }
-}
-
-// slots past the last pair: a key beyond every brick, so that they sort to the end
-__global__ __launch_bounds__(256) void k_inject_pad(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ offs, long long n,
-                                                    uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, long long slots, uint32_t pad_key)
-{
-    const long long total = n > 0 ? (long long)offs[n - 1] + counts[n - 1] : 0;
-    for (long long i = total + (long long)blockIdx.x * 256 + threadIdx.x; i < slots; i += (long long)gridDim.x * 256) {
-        keys[i] = pad_key;
-        vals[i] = 0u;
-    }
-}
-
-// starts[k] = first sorted pair of brick k (k = 0 .. bricks)
-__global__ __launch_bounds__(256) void k_inject_starts(const uint32_t* __restrict__ keys, long long slots, uint32_t* __restrict__ starts,
-                                                       uint32_t nkeys)
-{
-    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (k > (long long)nkeys) return;
-    long long lo = 0, hi = slots;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if ((long long)keys[mid] < k) lo = mid + 1; else hi = mid;
-    }
-    starts[k] = (uint32_t)lo;
+    brick_emit(r.lo, r.hi, grid, 0u, (uint32_t)i, offs[i], keys, vals);
 }
 
 // one block per brick: image and weight of its voxels continue from what they hold, step after step in list order
 __global__ __launch_bounds__(256) void k_inject_render(const InjRec* __restrict__ recs, const uint32_t* __restrict__ vals,
                                                        const uint32_t* __restrict__ starts, float* __restrict__ image, float* __restrict__ weight,
-                                                       int nx, int ny, int nz, int nbx, int nby, double t0, double t1, double t2)
+                                                       int nx, int ny, int nz, BrickGrid grid, double t0, double t1, double t2)
 {
     __shared__ double s_tab[CH][NTAB];
     __shared__ double s_loc[CH][3], s_int[CH];
@@ -291,15 +243,10 @@ __global__ __launch_bounds__(256) void k_inject_render(const InjRec* __restrict_
     const uint32_t brick = blockIdx.x;
     const uint32_t s = starts[brick], e = starts[brick + 1];
     if (s == e) return;                                 // nothing lands here: the voxels stay as they are
-    const int bx0 = (int)(brick % (uint32_t)nbx) * BX;
-    const int by0 = (int)((brick / (uint32_t)nbx) % (uint32_t)nby) * BY;
-    const int bz0 = (int)(brick / ((uint32_t)nbx * (uint32_t)nby)) * BZ;
-    const int tid = threadIdx.x;
-    const int xl = tid & 31, yl = tid >> 5;
-    const int x = bx0 + xl, y = by0 + yl;
-    const bool inxy = x < nx && y < ny;
-    const long long row = (long long)nx * ny;
-    const long long base = inxy ? (long long)x + (long long)nx * y : 0;
+    const BrickLane f = brick_lane(brick, grid, nx, ny);
+    const int bz0 = f.bz0, xl = f.xl, yl = f.yl, x = f.x, y = f.y, tid = threadIdx.x;
+    const bool inxy = f.inxy;
+    const long long row = f.row, base = f.base;
 
     float acc_i[BZ], acc_w[BZ];
 #pragma unroll
@@ -319,17 +266,7 @@ __global__ __launch_bounds__(256) void k_inject_render(const InjRec* __restrict_
             s_int[tid] = r.inten;
         }
         __syncthreads();
-        for (int t = tid; t < m * NTAB; t += 256) {
-            const int c = t / NTAB, i = t - c * NTAB;
-            const int d = i < BX ? 0 : (i < BX + BY ? 1 : 2);
-            const int pos = d == 0 ? bx0 + i : (d == 1 ? by0 + i - BX : bz0 + i - BX - BY);
-            double v = 0.0;
-            if (pos >= s_lo[c][d] && pos <= s_hi[c][d]) {
-                const double xd = s_loc[c][d] - (double)pos;
-                v = exp(-(xd * xd) / tss[d]);           // getGaussValue (:162-166)
-            }
-            s_tab[c][i] = v;
-        }
+        brick_fill_tables(m, f, tss, s_tab, s_loc, s_lo, s_hi);      // getGaussValue (:162-166)
         __syncthreads();
         for (int c = 0; c < m; ++c) {
             if (x < s_lo[c][0] || x > s_hi[c][0] || y < s_lo[c][1] || y > s_hi[c][1]) continue;
@@ -355,30 +292,16 @@ __global__ __launch_bounds__(256) void k_inject_render(const InjRec* __restrict_
     }
 }
 
-// device buffers that live for one call
-struct Scratch {
-    DevBuf b[12];
-    ~Scratch() { for (DevBuf& x : b) x.release(); }
-};
-
-int64_t bricks_spanned(int64_t len, int b, int64_t nbricks)
-{
-    const int64_t k = (len + b - 2) / b + 1;
-    return k < nbricks ? k : nbricks;
-}
-
 }  // namespace
 
-// VolumeInjection's constructor (:56-72) for sigma > 0, with Util.getSuggestedKernelDiameter (ImgLib2, recalled)
+// VolumeInjection's constructor (:56-72) for sigma > 0
 void aberr_inject_geometry(const double sigma[3], int size[3], double tss[3])
 {
     for (int d = 0; d < 3; ++d) {
-        const int s = 2 * (int)(3 * sigma[d] + 0.5) + 1;
-        size[d] = s > 3 ? s : 3;
+        size[d] = suggested_kernel_diameter(sigma[d]);
         tss[d] = 2 * sigma[d] * sigma[d];
     }
 }
-
 
 // xyz (3 doubles per step) with either inten (doubles) or val (floats), all on the device; sumw != 0 divides every intensity by it
 int aberr_inject_dev(mvsim_ctx* ctx, float* image, float* weight, const int64_t dim[3], const double sigma[3], const double* xyz,
@@ -388,62 +311,34 @@ int aberr_inject_dev(mvsim_ctx* ctx, float* image, float* weight, const int64_t 
     int size[3];
     double tss[3];
     aberr_inject_geometry(sigma, size, tss);
-    const int nbx = (int)((dim[0] + BX - 1) / BX), nby = (int)((dim[1] + BY - 1) / BY), nbz = (int)((dim[2] + BZ - 1) / BZ);
-    const uint64_t nb = (uint64_t)nbx * nby * nbz;
-    if (nb >= ((uint64_t)1 << 31)) {
-        set_error("invalid argument: volume injection: image of %llu bricks", (unsigned long long)nb);
-        return MVSIM_EINVAL;
-    }
-    const int bs[3] = {BX, BY, BZ};
-    const int64_t nbd[3] = {nbx, nby, nbz};
-    int64_t per_item = 1;
-    for (int d = 0; d < 3; ++d) per_item *= bricks_spanned(std::min<int64_t>(size[d], dim[d]), bs[d], nbd[d]);
+    BrickGrid grid;
+    MVSIM_TRY(brick_grid(dim, "volume injection", &grid));
+    const int64_t per_item = bricks_spanned(size, dim, grid);
     const int64_t cap = ctx->opt.beads_pair_cap;
     const int64_t per_range = std::max<int64_t>(1, std::min<int64_t>(cap / per_item, ((int64_t)1 << 31) / per_item - 1));
     const int64_t max_items = std::min(n, per_range), max_slots = max_items * per_item + 1;
 
     Scratch ws;
-    size_t scan_tmp = 0, sort_tmp = 0;
-    MVSIM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)max_items, ctx->stream));
-    MVSIM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr,
-                                                 (uint32_t*)nullptr, (int)max_slots, 0, 32, ctx->stream));
+    BrickBins bins;                              // per_range keeps a range's slots below 2^31: the refusal is never reached
+    MVSIM_TRY(bins.reserve(ctx->stream, max_items, max_slots, grid.nb, ws.b[1], ws.b[2], ws.b[3], ws.b[4],
+                           "invalid argument: volume injection: a range of %lld pairs"));
     MVSIM_TRY(ws.b[0].reserve((size_t)max_items * sizeof(InjRec)));
-    MVSIM_TRY(ws.b[1].reserve((size_t)(2 * max_items + (int64_t)nb + 1) * sizeof(uint32_t)));
-    MVSIM_TRY(ws.b[2].reserve((size_t)(2 * max_slots) * sizeof(uint32_t)));
-    MVSIM_TRY(ws.b[3].reserve((size_t)(2 * max_slots) * sizeof(uint32_t)));
-    MVSIM_TRY(ws.b[4].reserve(std::max<size_t>(16, std::max(scan_tmp, sort_tmp))));
     InjRec* recs = ws.b[0].as<InjRec>();
-    uint32_t* counts = ws.b[1].as<uint32_t>();
-    uint32_t* offs = counts + max_items;
-    uint32_t* starts = offs + max_items;
-    uint32_t* keys = ws.b[2].as<uint32_t>();
-    uint32_t* vals = ws.b[3].as<uint32_t>();
-    int end_bit = 1;
-    while (end_bit < 32 && (nb >> end_bit) != 0) ++end_bit;
 
     for (int64_t first = 0; first < n; first += per_range) {
         const int64_t cnt = std::min(per_range, n - first), slots = cnt * per_item + 1;
         const unsigned blocks = (unsigned)((cnt + 255) / 256);
         hipLaunchKernelGGL(k_inject_cull, dim3(blocks), dim3(256), 0, ctx->stream, xyz + 3 * first, inten ? inten + first : nullptr,
-                           val ? val + first : nullptr, sumw, (long long)cnt, recs, counts, (int)dim[0], (int)dim[1], (int)dim[2], size[0],
+                           val ? val + first : nullptr, sumw, (long long)cnt, recs, bins.counts, (int)dim[0], (int)dim[1], (int)dim[2], size[0],
                            size[1], size[2]);
         MVSIM_HIP(hipGetLastError());
-        size_t t = ws.b[4].bytes;
-        MVSIM_HIP(hipcub::DeviceScan::ExclusiveSum(ws.b[4].p, t, counts, offs, (int)cnt, ctx->stream));
-        hipLaunchKernelGGL(k_inject_emit, dim3(blocks), dim3(256), 0, ctx->stream, recs, counts, offs, (long long)cnt, keys, vals, nbx, nby);
+        MVSIM_TRY(bins.scan(ctx->stream, cnt));
+        hipLaunchKernelGGL(k_inject_emit, dim3(blocks), dim3(256), 0, ctx->stream, recs, bins.counts, bins.offs, (long long)cnt, bins.keys[0],
+                           bins.vals[0], grid);
         MVSIM_HIP(hipGetLastError());
-        const long long pad_blocks = std::min<long long>(4096, (slots + 255) / 256);
-        hipLaunchKernelGGL(k_inject_pad, dim3((unsigned)pad_blocks), dim3(256), 0, ctx->stream, counts, offs, (long long)cnt, keys, vals,
-                           (long long)slots, (uint32_t)nb);
-        MVSIM_HIP(hipGetLastError());
-        t = ws.b[4].bytes;
-        MVSIM_HIP(hipcub::DeviceRadixSort::SortPairs(ws.b[4].p, t, keys, keys + max_slots, vals, vals + max_slots, (int)slots, 0, end_bit,
-                                                     ctx->stream));
-        hipLaunchKernelGGL(k_inject_starts, dim3((unsigned)((nb + 1 + 255) / 256)), dim3(256), 0, ctx->stream, keys + max_slots,
-                           (long long)slots, starts, (uint32_t)nb);
-        MVSIM_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_inject_render, dim3((unsigned)nb), dim3(256), 0, ctx->stream, recs, vals + max_slots, starts, image, weight,
-                           (int)dim[0], (int)dim[1], (int)dim[2], nbx, nby, tss[0], tss[1], tss[2]);
+        MVSIM_TRY(bins.finish(ctx->stream, cnt, slots, grid.nb));
+        hipLaunchKernelGGL(k_inject_render, dim3(grid.nb), dim3(256), 0, ctx->stream, recs, bins.vals[1], bins.starts, image, weight,
+                           (int)dim[0], (int)dim[1], (int)dim[2], grid, tss[0], tss[1], tss[2]);
         MVSIM_HIP(hipGetLastError());
     }
     MVSIM_HIP(hipStreamSynchronize(ctx->stream));          // the workspaces go away with this call
@@ -457,55 +352,17 @@ int aberr_refract3d_dev(mvsim_ctx* ctx, const float* img, const float* ri_img, c
 {
     const double sigma[3] = {0.5, 0.5, 0.5};                                                       // :280
     const int max_moves = (int)dim[2];                                                            // :304
-    const int64_t cap_steps = std::max<int64_t>(max_moves, std::min<int64_t>(ctx->opt.beads_pair_cap / 8, (int64_t)1 << 25));
-    const int64_t rays_per_range = std::max<int64_t>(1, cap_steps / max_moves);
-    const int64_t max_rays = std::min(std::max<int64_t>(num_rays, 1), rays_per_range), max_slots = max_rays * max_moves;
     if (steps) steps->n = 0;
-
-    Scratch ws;
-    size_t scan_tmp = 0;
-    MVSIM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, (int*)nullptr, (int*)nullptr, (int)max_rays, ctx->stream));
-    MVSIM_TRY(ws.b[0].reserve((size_t)max_slots * 3 * sizeof(double)));
-    MVSIM_TRY(ws.b[1].reserve((size_t)max_slots * sizeof(float)));
-    MVSIM_TRY(ws.b[2].reserve((size_t)max_rays * 2 * sizeof(int)));
-    MVSIM_TRY(ws.b[3].reserve((size_t)max_slots * 3 * sizeof(double)));
-    MVSIM_TRY(ws.b[4].reserve((size_t)max_slots * sizeof(float)));
-    MVSIM_TRY(ws.b[5].reserve(std::max<size_t>(16, scan_tmp)));
-    double* slot_xyz = ws.b[0].as<double>();
-    float* slot_val = ws.b[1].as<float>();
-    int* moves = ws.b[2].as<int>();
-    int* offs = moves + max_rays;
-    double* xyz = ws.b[3].as<double>();
-    float* val = ws.b[4].as<float>();
+    StepRanges sr;
+    MVSIM_TRY(sr.reserve(ctx, num_rays, max_moves));
     SheetParams sp{state & JR_MASK, abc[0], abc[1], abc[2], illum ? 1 : 0, z};
 
-    for (int64_t r0 = 0; r0 < num_rays; r0 += rays_per_range) {
-        const int nr = (int)std::min(rays_per_range, num_rays - r0);
+    for (int64_t r0 = 0; r0 < num_rays; r0 += sr.rays_per_range) {
+        const int nr = (int)std::min(sr.rays_per_range, num_rays - r0);
         hipLaunchKernelGGL(k_refract3d_trace, dim3((unsigned)((nr + 63) / 64)), dim3(64), 0, ctx->stream, img, ri_img, (int)dim[0], (int)dim[1],
-                           (int)dim[2], sp, ri, (long long)r0, nr, max_moves, slot_xyz, slot_val, moves);
+                           (int)dim[2], sp, ri, (long long)r0, nr, max_moves, sr.slot_xyz, sr.slot_val, sr.moves);
         MVSIM_HIP(hipGetLastError());
-        size_t t = ws.b[5].bytes;
-        MVSIM_HIP(hipcub::DeviceScan::ExclusiveSum(ws.b[5].p, t, moves, offs, nr, ctx->stream));
-        hipLaunchKernelGGL(k_compact_steps, dim3((unsigned)(((long long)nr * max_moves + 255) / 256)), dim3(256), 0, ctx->stream, slot_xyz,
-                           slot_val, moves, offs, nr, max_moves, xyz, val);
-        MVSIM_HIP(hipGetLastError());
-        int last[2];
-        MVSIM_HIP(hipMemcpyAsync(&last[0], moves + nr - 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        MVSIM_HIP(hipMemcpyAsync(&last[1], offs + nr - 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        MVSIM_HIP(hipStreamSynchronize(ctx->stream));
-        const int64_t nsteps = (int64_t)last[0] + last[1];
-        if (steps) {
-            if (steps->n + nsteps > steps->capacity) {
-                set_error("invalid argument: refract3d: the step list needs more than its capacity of %lld steps", (long long)steps->capacity);
-                return MVSIM_EINVAL;
-            }
-            if (steps->xyz) MVSIM_HIP(hipMemcpyAsync(steps->xyz + 3 * steps->n, xyz, (size_t)nsteps * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            if (steps->value) MVSIM_HIP(hipMemcpyAsync(steps->value + steps->n, val, (size_t)nsteps * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-            if (steps->moves) MVSIM_HIP(hipMemcpyAsync(steps->moves + r0, moves, (size_t)nr * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            steps->n += nsteps;
-        }
-        if (image && weight) MVSIM_TRY(aberr_inject_dev(ctx, image, weight, dim, sigma, xyz, nullptr, val, nsteps, sumw));
-        MVSIM_HIP(hipStreamSynchronize(ctx->stream));
+        MVSIM_TRY(sr.finish(ctx, "refract3d", r0, nr, dim, sigma, sumw, image, weight, steps));
     }
     return MVSIM_OK;
 }

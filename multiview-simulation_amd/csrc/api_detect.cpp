@@ -10,7 +10,7 @@ int dog_taps_host(double sigma, float* taps, int* ntaps)
 {
     MVSIM_CHECK_ARG(std::isfinite(sigma) && sigma > 0.0, "dog: sigma must be a positive finite number");
     MVSIM_CHECK_ARG(sigma <= 64.0, "dog: sigma needs more than MVSIM_DOG_MAX_TAPS taps");
-    const int d = std::max(3, 2 * (int)(3.0 * sigma + 0.5) + 1);
+    const int d = suggested_kernel_diameter(sigma);
     MVSIM_CHECK_ARG(d <= MVSIM_DOG_MAX_TAPS, "dog: sigma needs more than MVSIM_DOG_MAX_TAPS taps");
     const int r = d / 2;
     double e[MVSIM_DOG_MAX_TAPS];

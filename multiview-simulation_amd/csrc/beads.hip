@@ -5,8 +5,8 @@
 //   cull   one thread per (view, bead): the view's 3x4 matrix in fp64 (((x m00 + y m01) + z m02) + m03, no fused multiply-add:
 //          the build compiles with -ffp-contract=off), isInsideAdjust (:120-130), the box with Java's Math.round (:178-184)
 //          clipped to the image (Views.extendZero drops the writes outside it), and the number of bricks the box overlaps
-//   bin    an exclusive scan over those counts gives every bead its slot; each bead writes its (brick, bead) pairs there in
-//          bead order; a stable radix sort by brick (hipcub, LSD: stable) then leaves every brick's list in ascending bead order
+//   bin    the brick binner (bricks.h) with one job per view of a chunk, keys = job-in-chunk * bricks + brick: every brick's
+//          list in ascending bead order
 //   render one block per brick, every voxel written exactly once (empty bricks included): the brick's beads pass through LDS
 //          in chunks as per-axis factor tables exp(-(x*x) / two_sq_sigma) over the brick's extent -- +0.0 outside the bead's
 //          box, which adds +0.0f to an accumulator that is never -0 and so changes nothing -- and every lane accumulates
@@ -16,9 +16,7 @@
 // differ by one ulp on rare arguments).  Float denormals are kept (the build does not flush them).  Calls whose pairs would
 // exceed the option "beads_pair_cap" run in chunks of whole views, or of bead ranges of one view: a range after the first
 // continues from the float image the previous range left, which is the same sequential sum.
-#include "common.h"
-
-#include <hipcub/hipcub.hpp>
+#include "bricks.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -28,10 +26,6 @@
 namespace mvsim {
 
 namespace {
-
-constexpr int BX = 32, BY = 8, BZ = 16;     // brick: two 32-voxel rows per wave, four waves, 16 planes per lane
-constexpr int CH = 32;                      // beads per LDS chunk
-constexpr int NTAB = BX + BY + BZ;
 
 struct BeadJob {
     double    m[12];
@@ -49,14 +43,6 @@ struct BeadRec {
     double loc[3];          // location after isInsideAdjust
     int    lo[3], hi[3];    // box clipped to the image, inclusive (lo > hi: nothing to add)
 };
-
-// Java Math.round(double) for the finite values that reach it here: floor, plus one when the fraction is >= 0.5 (x - floor(x)
-// is exact), so -2.5 -> -2 and 0.49999999999999994 -> 0 as on Java 7 and later.
-__device__ __forceinline__ long long java_round_d(double x)
-{
-    const double f = floor(x);
-    return (long long)f + ((x - f) >= 0.5 ? 1 : 0);
-}
 
 // Math.round(float) -> int (NaN -> 0, saturating), then UnsignedShortType.set(int): the low 16 bits
 __device__ __forceinline__ uint16_t java_round_u16(float x)
@@ -93,29 +79,22 @@ __global__ __launch_bounds__(256) void k_beads_cull(const double* __restrict__ p
         // interval.dimension(d) - 1 == max - min == the image's extent; a NaN coordinate is dropped (see mvsim.h)
         if (!(p[d] >= 0.0) || p[d] > (double)dim[d]) { keep = false; break; }
     }
-    uint32_t cnt = 0;
     for (int d = 0; d < 3; ++d) { r.loc[d] = p[d]; r.lo[d] = 1; r.hi[d] = 0; }
-    if (keep) {
-        const int bs[3] = {BX, BY, BZ};
-        cnt = 1;
+    if (keep)
         for (int d = 0; d < 3; ++d) {
             const long long lo = (long long)(int)java_round_d(p[d]) - size[d] / 2;
             const long long hi = lo + size[d] - 1;
-            const long long a = lo < 0 ? 0 : lo, b = hi > dim[d] - 1 ? dim[d] - 1 : hi;
-            r.lo[d] = (int)a;
-            r.hi[d] = (int)b;
-            cnt = a > b ? 0u : cnt * (uint32_t)(b / bs[d] - a / bs[d] + 1);
+            r.lo[d] = (int)(lo < 0 ? 0 : lo);
+            r.hi[d] = (int)(hi > dim[d] - 1 ? dim[d] - 1 : hi);
         }
-    }
     recs[jb.bead_base + i] = r;
-    counts[jb.bead_base + i] = cnt;
+    counts[jb.bead_base + i] = bricks_overlapped(r.lo, r.hi);
 }
 
 // every bead writes its (brick, bead) pairs at its scanned slot: keys = job-in-chunk * bricks + brick, values = bead record
 __global__ __launch_bounds__(256) void k_beads_emit(const BeadJob* __restrict__ jobs, const BeadRec* __restrict__ recs,
                                                     const uint32_t* __restrict__ counts, const uint32_t* __restrict__ offs,
-                                                    uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, int nbx, int nby,
-                                                    uint32_t nb)
+                                                    uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, BrickGrid grid)
 {
     const BeadJob& jb = jobs[blockIdx.y];
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -123,47 +102,12 @@ __global__ __launch_bounds__(256) void k_beads_emit(const BeadJob* __restrict__ 
     const uint32_t g = (uint32_t)(jb.bead_base + i);
     if (counts[g] == 0) return;
     const BeadRec r = recs[g];
-    uint32_t o = offs[g];
-    const uint32_t base = (uint32_t)blockIdx.y * nb;
-    for (int bz = r.lo[2] / BZ; bz <= r.hi[2] / BZ; ++bz)
-        for (int by = r.lo[1] / BY; by <= r.hi[1] / BY; ++by)
-            for (int bx = r.lo[0] / BX; bx <= r.hi[0] / BX; ++bx) {
-                keys[o] = base + (uint32_t)(bx + nbx * (by + nby * bz));
-                vals[o] = g;
-                ++o;
-            }
-}
-
-// slots past the last pair: a key beyond every brick, so that they sort to the end
-__global__ __launch_bounds__(256) void k_beads_pad(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ offs,
-                                                   long long nbeads, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
-                                                   long long slots, uint32_t pad_key)
-{
-    const long long total = nbeads > 0 ? (long long)offs[nbeads - 1] + counts[nbeads - 1] : 0;
-    for (long long i = total + (long long)blockIdx.x * 256 + threadIdx.x; i < slots; i += (long long)gridDim.x * 256) {
-        keys[i] = pad_key;
-        vals[i] = 0u;
-    }
-}
-
-// starts[k] = first sorted pair of brick k (k = 0 .. bricks; starts[bricks] = number of pairs)
-__global__ __launch_bounds__(256) void k_beads_starts(const uint32_t* __restrict__ keys, long long slots, uint32_t* __restrict__ starts,
-                                                      uint32_t nkeys)
-{
-    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (k > (long long)nkeys) return;
-    long long lo = 0, hi = slots;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if ((long long)keys[mid] < k) lo = mid + 1; else hi = mid;
-    }
-    starts[k] = (uint32_t)lo;
+    brick_emit(r.lo, r.hi, grid, (uint32_t)blockIdx.y * grid.nb, g, offs[g], keys, vals);
 }
 
 __global__ __launch_bounds__(256) void k_beads_render(const BeadJob* __restrict__ jobs, const BeadRec* __restrict__ recs,
                                                       const uint32_t* __restrict__ vals, const uint32_t* __restrict__ starts,
-                                                      int nx, int ny, int nz, int nbx, int nby, uint32_t nb, double t0, double t1,
-                                                      double t2)
+                                                      int nx, int ny, int nz, BrickGrid grid, double t0, double t1, double t2)
 {
     __shared__ double s_tab[CH][NTAB];
     __shared__ double s_loc[CH][3];
@@ -171,15 +115,10 @@ __global__ __launch_bounds__(256) void k_beads_render(const BeadJob* __restrict_
 
     const BeadJob& jb = jobs[blockIdx.y];
     const uint32_t brick = blockIdx.x;
-    const int bx0 = (int)(brick % (uint32_t)nbx) * BX;
-    const int by0 = (int)((brick / (uint32_t)nbx) % (uint32_t)nby) * BY;
-    const int bz0 = (int)(brick / ((uint32_t)nbx * (uint32_t)nby)) * BZ;
-    const int tid = threadIdx.x;
-    const int xl = tid & 31, yl = tid >> 5;            // lanes 0-31 / 32-63 of a wave: two rows
-    const int x = bx0 + xl, y = by0 + yl;
-    const bool inxy = x < nx && y < ny;
-    const long long row = (long long)nx * ny;
-    const long long base = inxy ? (long long)x + (long long)nx * y : 0;
+    const BrickLane f = brick_lane(brick, grid, nx, ny);
+    const int bz0 = f.bz0, xl = f.xl, yl = f.yl, tid = threadIdx.x;
+    const bool inxy = f.inxy;
+    const long long row = f.row, base = f.base;
 
     float acc[BZ];
 #pragma unroll
@@ -188,7 +127,7 @@ __global__ __launch_bounds__(256) void k_beads_render(const BeadJob* __restrict_
         acc[k] = (jb.init && inxy && z < nz) ? jb.init[base + row * z] : 0.0f;
     }
 
-    const uint32_t key = blockIdx.y * nb + brick;
+    const uint32_t key = blockIdx.y * grid.nb + brick;
     const uint32_t s = starts[key], e = starts[key + 1];
     const double tss[3] = {t0, t1, t2};
     for (uint32_t c0 = s; c0 < e; c0 += CH) {
@@ -199,17 +138,7 @@ __global__ __launch_bounds__(256) void k_beads_render(const BeadJob* __restrict_
             for (int d = 0; d < 3; ++d) { s_loc[tid][d] = r.loc[d]; s_lo[tid][d] = r.lo[d]; s_hi[tid][d] = r.hi[d]; }
         }
         __syncthreads();
-        for (int t = tid; t < m * NTAB; t += 256) {
-            const int c = t / NTAB, i = t - c * NTAB;
-            const int d = i < BX ? 0 : (i < BX + BY ? 1 : 2);
-            const int pos = d == 0 ? bx0 + i : (d == 1 ? by0 + i - BX : bz0 + i - BX - BY);
-            double v = 0.0;
-            if (pos >= s_lo[c][d] && pos <= s_hi[c][d]) {
-                const double xd = s_loc[c][d] - (double)pos;
-                v = exp(-(xd * xd) / tss[d]);          // SimulateBeads.java:199-200
-            }
-            s_tab[c][i] = v;
-        }
+        brick_fill_tables(m, f, tss, s_tab, s_loc, s_lo, s_hi);     // SimulateBeads.java:199-200
         __syncthreads();
         for (int c = 0; c < m; ++c) {
             const int zl = s_lo[c][2] - bz0, zh = s_hi[c][2] - bz0;
@@ -284,20 +213,6 @@ __global__ __launch_bounds__(256) void k_norm_apply(float* __restrict__ img, lon
         img[i] = (img[i] - mn) / range;
 }
 
-// Util.getSuggestedKernelDiameter (ImgLib2, recalled): max(3, 2 * (int)(3 sigma + 0.5) + 1) for sigma > 0, else 3
-int kernel_diameter(double sigma)
-{
-    if (!(sigma > 0)) return 3;
-    const int s = 2 * (int)(3 * sigma + 0.5) + 1;
-    return s > 3 ? s : 3;
-}
-
-int64_t bricks_spanned(int64_t len, int b, int64_t nbricks)
-{
-    const int64_t k = (len + b - 2) / b + 1;
-    return k < nbricks ? k : nbricks;
-}
-
 struct Piece {
     int       view;
     long long first, count;   // bead range within the view's list
@@ -315,20 +230,12 @@ int render_beads_dev(mvsim_ctx* ctx, const double* xyz, const int64_t* view_offs
                      const int64_t dim[3], const int64_t imin[3], const double sigma[3], float* const* out_f32,
                      uint16_t* const* out_u16)
 {
-    const int nbx = (int)((dim[0] + BX - 1) / BX), nby = (int)((dim[1] + BY - 1) / BY), nbz = (int)((dim[2] + BZ - 1) / BZ);
-    const uint64_t nb = (uint64_t)nbx * nby * nbz;
+    BrickGrid grid;
+    MVSIM_TRY(brick_grid(dim, "renderBeads", &grid));
+    const uint64_t nb = grid.nb;
     int size[3];
-    int64_t per_bead = 1;
-    const int bs[3] = {BX, BY, BZ};
-    const int64_t nbd[3] = {nbx, nby, nbz};
-    for (int d = 0; d < 3; ++d) {
-        size[d] = kernel_diameter(sigma[d]) * 2;                                      // SimulateBeads.java:180
-        per_bead *= bricks_spanned(std::min<int64_t>(size[d], dim[d]), bs[d], nbd[d]);
-    }
-    if (nb >= ((uint64_t)1 << 31)) {
-        set_error("invalid argument: renderBeads: image of %llu bricks", (unsigned long long)nb);
-        return MVSIM_EINVAL;
-    }
+    for (int d = 0; d < 3; ++d) size[d] = suggested_kernel_diameter(sigma[d]) * 2;    // SimulateBeads.java:180
+    const int64_t per_bead = bricks_spanned(size, dim, grid);
 
     // bead ranges of the views, then pieces of at most `cap` pairs, packed into chunks
     std::vector<long long> vfirst(nviews), vcount(nviews);
@@ -406,33 +313,19 @@ int render_beads_dev(mvsim_ctx* ctx, const double* xyz, const int64_t* view_offs
         max_slots = std::max(max_slots, beads * per_bead + 1);
         max_keys = std::max(max_keys, (long long)((chunk_begin[c + 1] - chunk_begin[c]) * nb));
     }
-    size_t scan_tmp = 0, sort_tmp = 0;
-    MVSIM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)max_beads, ctx->stream));
-    MVSIM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr,
-                                                 (uint32_t*)nullptr, (int)max_slots, 0, 32, ctx->stream));
-    if (max_slots >= ((long long)1 << 31) || max_beads >= ((long long)1 << 31)) {
-        set_error("invalid argument: renderBeads: a chunk of %lld pairs (option beads_pair_cap)", max_slots);
-        return MVSIM_EINVAL;
-    }
     MVSIM_HIP(hipStreamSynchronize(ctx->stream));          // the workspaces may still be read by an earlier call's kernels
+    BrickBins bins;
+    MVSIM_TRY(bins.reserve(ctx->stream, max_beads, max_slots, max_keys, ctx->beads_buf[3], ctx->beads_buf[4], ctx->beads_buf[5], ctx->beads_buf[6],
+                           "invalid argument: renderBeads: a chunk of %lld pairs (option beads_pair_cap)"));
     MVSIM_TRY(ctx->beads_buf[0].reserve(std::max<size_t>(1, (size_t)n * 3 * sizeof(double))));
     MVSIM_TRY(ctx->beads_buf[1].reserve(jobs.size() * sizeof(BeadJob)));
     MVSIM_TRY(ctx->beads_buf[2].reserve((size_t)max_beads * sizeof(BeadRec)));
-    MVSIM_TRY(ctx->beads_buf[3].reserve((size_t)(2 * max_beads + max_keys + 1) * sizeof(uint32_t)));
-    MVSIM_TRY(ctx->beads_buf[4].reserve((size_t)(2 * max_slots) * sizeof(uint32_t)));
-    MVSIM_TRY(ctx->beads_buf[5].reserve((size_t)(2 * max_slots) * sizeof(uint32_t)));
-    MVSIM_TRY(ctx->beads_buf[6].reserve(std::max<size_t>(16, std::max(scan_tmp, sort_tmp))));
     // pageable sources: synchronous copies (the caller may free its lists as soon as the call returns)
     if (n > 0) MVSIM_HIP(hipMemcpy(ctx->beads_buf[0].p, xyz, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice));
     MVSIM_HIP(hipMemcpy(ctx->beads_buf[1].p, jobs.data(), jobs.size() * sizeof(BeadJob), hipMemcpyHostToDevice));
 
     const double* pts = ctx->beads_buf[0].as<double>();
     BeadRec* recs = ctx->beads_buf[2].as<BeadRec>();
-    uint32_t* counts = ctx->beads_buf[3].as<uint32_t>();
-    uint32_t* offs = counts + max_beads;
-    uint32_t* starts = offs + max_beads;
-    uint32_t* keys = ctx->beads_buf[4].as<uint32_t>();
-    uint32_t* vals = ctx->beads_buf[5].as<uint32_t>();
     const double two_sq[3] = {2 * sigma[0] * sigma[0], 2 * sigma[1] * sigma[1], 2 * sigma[2] * sigma[2]};   // :183
     for (size_t c = 0; c < nchunks; ++c) {
         const size_t j0 = chunk_begin[c], nj = chunk_begin[c + 1] - j0;
@@ -443,27 +336,16 @@ int render_beads_dev(mvsim_ctx* ctx, const double* xyz, const int64_t* view_offs
         const uint32_t nkeys = (uint32_t)(nj * nb);
         const dim3 gb((unsigned)((most + 255) / 256), (unsigned)nj);
         if (beads > 0) {
-            hipLaunchKernelGGL(k_beads_cull, gb, dim3(256), 0, ctx->stream, pts, jd, recs, counts, (int)dim[0], (int)dim[1], (int)dim[2],
+            hipLaunchKernelGGL(k_beads_cull, gb, dim3(256), 0, ctx->stream, pts, jd, recs, bins.counts, (int)dim[0], (int)dim[1], (int)dim[2],
                                (double)imin[0], (double)imin[1], (double)imin[2], size[0], size[1], size[2]);
             MVSIM_HIP(hipGetLastError());
-            size_t t = ctx->beads_buf[6].bytes;
-            MVSIM_HIP(hipcub::DeviceScan::ExclusiveSum(ctx->beads_buf[6].p, t, counts, offs, (int)beads, ctx->stream));
-            hipLaunchKernelGGL(k_beads_emit, gb, dim3(256), 0, ctx->stream, jd, recs, counts, offs, keys, vals, nbx, nby, (uint32_t)nb);
+            MVSIM_TRY(bins.scan(ctx->stream, beads));
+            hipLaunchKernelGGL(k_beads_emit, gb, dim3(256), 0, ctx->stream, jd, recs, bins.counts, bins.offs, bins.keys[0], bins.vals[0], grid);
             MVSIM_HIP(hipGetLastError());
         }
-        const long long pad_blocks = std::min<long long>(4096, (slots + 255) / 256);
-        hipLaunchKernelGGL(k_beads_pad, dim3((unsigned)pad_blocks), dim3(256), 0, ctx->stream, counts, offs, beads, keys, vals, slots, nkeys);
-        MVSIM_HIP(hipGetLastError());
-        int end_bit = 1;
-        while (end_bit < 32 && ((uint64_t)nkeys >> end_bit) != 0) ++end_bit;
-        size_t t = ctx->beads_buf[6].bytes;
-        MVSIM_HIP(hipcub::DeviceRadixSort::SortPairs(ctx->beads_buf[6].p, t, keys, keys + max_slots, vals, vals + max_slots, (int)slots,
-                                                     0, end_bit, ctx->stream));
-        hipLaunchKernelGGL(k_beads_starts, dim3((unsigned)(((long long)nkeys + 1 + 255) / 256)), dim3(256), 0, ctx->stream,
-                           keys + max_slots, slots, starts, nkeys);
-        MVSIM_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_beads_render, dim3((unsigned)nb, (unsigned)nj), dim3(256), 0, ctx->stream, jd, recs, vals + max_slots, starts,
-                           (int)dim[0], (int)dim[1], (int)dim[2], nbx, nby, (uint32_t)nb, two_sq[0], two_sq[1], two_sq[2]);
+        MVSIM_TRY(bins.finish(ctx->stream, beads, slots, nkeys));
+        hipLaunchKernelGGL(k_beads_render, dim3((unsigned)nb, (unsigned)nj), dim3(256), 0, ctx->stream, jd, recs, bins.vals[1], bins.starts,
+                           (int)dim[0], (int)dim[1], (int)dim[2], grid, two_sq[0], two_sq[1], two_sq[2]);
         MVSIM_HIP(hipGetLastError());
     }
     return MVSIM_OK;

@@ -90,6 +90,20 @@ struct DevBuf {
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// device buffers that live for one call
+struct Scratch {
+    DevBuf b[12];
+    ~Scratch() { for (DevBuf& x : b) x.release(); }
+};
+
+// Util.getSuggestedKernelDiameter (ImgLib2, recalled): max(3, 2 * (int)(3 sigma + 0.5) + 1) for sigma > 0, else 3
+inline int suggested_kernel_diameter(double sigma)
+{
+    if (!(sigma > 0)) return 3;
+    const int s = 2 * (int)(3 * sigma + 0.5) + 1;
+    return s > 3 ? s : 3;
+}
+
 // struct Affine: rotate_dev.h.  A rotation about x (the only axis SimulateMultiViewDataset.main uses, :557,:570,:591): the
 // inverse model has row 0 = (1,0,0,0) exactly and no x term in rows 1 and 2 -- what every row-walking rotate kernel requires
 inline bool affine_is_x_rotation(const Affine& a)
@@ -503,6 +517,21 @@ int aberr_hessian_at_dev(mvsim_ctx* ctx, const float* img, const int64_t dim[3],
 int aberr_hessian_images_dev(mvsim_ctx* ctx, const float* img, const int64_t dim[3], int z0, int planes, float* eigval, float* eigvec);
 // raytrace.hip
 int64_t trace_rays_per_range(int64_t pair_cap, int64_t max_moves);
+// The step-range workspace of the two tracers (trace_rays_dev, aberr_refract3d_dev): rays run in ranges of rays_per_range; a trace
+// kernel fills slot_xyz / slot_val (record of ray r, move m at r * max_moves + m) and moves for the nr rays of a range from r0 on, and
+// finish() scans the moves, compacts the records into xyz / val, appends them to `steps` (null: not wanted; `who` names the caller in
+// the capacity refusal), injects them into image and weight (null: no injection) and synchronises.
+struct StepRanges {
+    Scratch ws;
+    int64_t rays_per_range = 0, max_rays = 0;
+    int     max_moves = 0;
+    double *slot_xyz = nullptr, *xyz = nullptr;
+    float  *slot_val = nullptr, *val = nullptr;
+    int    *moves = nullptr, *offs = nullptr;
+    int reserve(mvsim_ctx* ctx, int64_t nrays, int max_moves);
+    int finish(mvsim_ctx* ctx, const char* who, int64_t r0, int nr, const int64_t dim[3], const double sigma[3], double sumw, float* image,
+               float* weight, mvsim_ray_steps* steps);
+};
 int trace_rays_dev(mvsim_ctx* ctx, const float* ri_img, const float* img, const int64_t dim[3], const double* pos3, const double* dir3,
                    const float* intensity, int64_t n, const mvsim_trace_params* tp, double sumw, float* image, float* weight,
                    mvsim_ray_steps* steps, double* end_pos3, double* end_dir3, int64_t* n_capped);

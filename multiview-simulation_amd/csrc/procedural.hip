@@ -9,18 +9,15 @@
 //   spheres  the value of the lowest-index sphere with sqrt(dx dx + dy dy + dz dz) <= radius, else the background.  The test is
 //            made without a square root per voxel: sqrt is correctly rounded and monotone, so for every radius there is one largest
 //            double T with sqrt(T) <= radius, found once per sphere (k_sph_prep), and sqrt(d) <= radius  <=>  d <= T.
-//            The raster bins and gathers as beads.hip does: cull against 32 x 8 x 16 bricks with each sphere's own radius, exclusive
-//            scan, (brick, sphere) pairs in sphere order, stable radix sort by brick -- every brick's list in ascending sphere index
-//            -- then one block per brick streams its list through LDS; a lane stops at its first containing sphere, the block leaves
-//            the list once every lane has one.  Calls whose pairs exceed the option "beads_pair_cap" run in sphere ranges; a bit mask
-//            of the voxels that earlier ranges own keeps a later range from replacing them.
+//            The raster goes through the brick binner (bricks.h), culling with each sphere's own radius: every brick's list in
+//            ascending sphere index, which one block per brick streams through LDS; a lane stops at its first containing sphere, the
+//            block leaves the list once every lane has one.  Calls whose pairs exceed the option "beads_pair_cap" run in sphere
+//            ranges; a bit mask of the voxels that earlier ranges own keeps a later range from replacing them.
 //   sampler  one lane per trial: trial t starts at jr_jump(state, 8 t) (four nextDouble() of two steps each, accepted or not),
 //            evaluates the density with the device functions of the `at` kernels, and a hipcub scan compacts the accepted trials in
 //            trial order.
-#include "common.h"
+#include "bricks.h"
 #include "jrandom.h"
-
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cfloat>
@@ -31,8 +28,6 @@ namespace mvsim {
 
 namespace {
 
-constexpr int BX = 32, BY = 8, BZ = 16;     // brick of the sphere raster: as beads.hip
-constexpr int CH = 32;                      // spheres per LDS chunk
 constexpr int VPL = 8;                      // voxels per lane of the Perlin raster
 
 struct SphRec {
@@ -185,18 +180,15 @@ __global__ __launch_bounds__(256) void k_sph_prep(const double* __restrict__ cen
 // box can still compare <= radius), clipped to the raster.  The host sizes the sphere ranges with the same function.
 __host__ __device__ inline uint32_t sph_box(const double c[3], double r, const Box3& bx, int lo[3], int hi[3])
 {
-    const int bs[3] = {BX, BY, BZ};
-    uint32_t cnt = 1;
     for (int d = 0; d < 3; ++d) {
         double a = floor(c[d] - r) - 1.0 - (double)bx.o[d], b = ceil(c[d] + r) + 1.0 - (double)bx.o[d];
         a = a > 0.0 ? a : 0.0;
         b = b < (double)(bx.n[d] - 1) ? b : (double)(bx.n[d] - 1);
-        if (!(a <= b)) { lo[d] = 1; hi[d] = 0; cnt = 0; continue; }
+        if (!(a <= b)) { lo[d] = 1; hi[d] = 0; continue; }
         lo[d] = (int)a;
         hi[d] = (int)b;
-        cnt = cnt == 0 ? 0u : cnt * (uint32_t)(hi[d] / bs[d] - lo[d] / bs[d] + 1);
     }
-    return cnt;
+    return bricks_overlapped(lo, hi);
 }
 
 __global__ __launch_bounds__(256) void k_sph_cull(const double* __restrict__ centres, const double* __restrict__ radii, long long first,
@@ -212,46 +204,14 @@ __global__ __launch_bounds__(256) void k_sph_cull(const double* __restrict__ cen
 __global__ __launch_bounds__(256) void k_sph_emit(const double* __restrict__ centres, const double* __restrict__ radii, long long first,
                                                   long long count, Box3 bx, const uint32_t* __restrict__ counts,
                                                   const uint32_t* __restrict__ offs, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
-                                                  int nbx, int nby)
+                                                  BrickGrid grid)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= count || counts[i] == 0) return;
     const double c[3] = {centres[3 * (first + i)], centres[3 * (first + i) + 1], centres[3 * (first + i) + 2]};
     int lo[3], hi[3];
     sph_box(c, radii[first + i], bx, lo, hi);
-    uint32_t o = offs[i];
-    for (int bz = lo[2] / BZ; bz <= hi[2] / BZ; ++bz)
-        for (int by = lo[1] / BY; by <= hi[1] / BY; ++by)
-            for (int b = lo[0] / BX; b <= hi[0] / BX; ++b) {
-                keys[o] = (uint32_t)(b + nbx * (by + nby * bz));
-                vals[o] = (uint32_t)i;                         // index within the range: ascending with the sphere index
-                ++o;
-            }
-}
-
-// slots past the last pair: a key beyond every brick, so that they sort to the end
-__global__ __launch_bounds__(256) void k_sph_pad(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ offs, long long count,
-                                                 uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, long long slots, uint32_t pad_key)
-{
-    const long long total = count > 0 ? (long long)offs[count - 1] + counts[count - 1] : 0;
-    for (long long i = total + (long long)blockIdx.x * 256 + threadIdx.x; i < slots; i += (long long)gridDim.x * 256) {
-        keys[i] = pad_key;
-        vals[i] = 0u;
-    }
-}
-
-// starts[k] = first sorted pair of brick k (k = 0 .. bricks; starts[bricks] = number of pairs)
-__global__ __launch_bounds__(256) void k_sph_starts(const uint32_t* __restrict__ keys, long long slots, uint32_t* __restrict__ starts,
-                                                    uint32_t nkeys)
-{
-    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (k > (long long)nkeys) return;
-    long long lo = 0, hi = slots;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if ((long long)keys[mid] < k) lo = mid + 1; else hi = mid;
-    }
-    starts[k] = (uint32_t)lo;
+    brick_emit(lo, hi, grid, 0u, (uint32_t)i, offs[i], keys, vals);      // the index within the range: ascending with the sphere index
 }
 
 // Math.max(float, float): NaN if either is NaN, +0 above -0
@@ -264,7 +224,7 @@ __device__ __forceinline__ float java_max_f(float a, float b)
 
 __global__ __launch_bounds__(256) void k_sph_render(const SphRec* __restrict__ recs, const uint32_t* __restrict__ vals,
                                                     const uint32_t* __restrict__ starts, float* __restrict__ out,
-                                                    unsigned short* __restrict__ owned, Box3 bx, int nbx, int nby, float background,
+                                                    unsigned short* __restrict__ owned, Box3 bx, BrickGrid grid, float background,
                                                     int combine, int first_piece, int last_piece)
 {
     __shared__ double s_c[CH][4];
@@ -272,15 +232,10 @@ __global__ __launch_bounds__(256) void k_sph_render(const SphRec* __restrict__ r
 
     const int nx = bx.n[0], ny = bx.n[1], nz = bx.n[2];
     const uint32_t brick = blockIdx.x;
-    const int bx0 = (int)(brick % (uint32_t)nbx) * BX;
-    const int by0 = (int)((brick / (uint32_t)nbx) % (uint32_t)nby) * BY;
-    const int bzi = (int)(brick / ((uint32_t)nbx * (uint32_t)nby)), bz0 = bzi * BZ;
-    const int tid = threadIdx.x;
-    const int xl = tid & 31, yl = tid >> 5;
-    const int x = bx0 + xl, y = by0 + yl;
-    const bool inxy = x < nx && y < ny;
-    const long long row = (long long)nx * ny;
-    const long long base = inxy ? (long long)x + (long long)nx * y : 0;
+    const BrickLane f = brick_lane(brick, grid, nx, ny);
+    const int bzi = f.bzi, bz0 = f.bz0, x = f.x, y = f.y, tid = threadIdx.x;
+    const bool inxy = f.inxy;
+    const long long row = f.row, base = f.base;
     const long long oidx = inxy ? base + row * bzi : 0;        // the lane's word of the ownership mask
     const int nk = inxy ? min(BZ, nz - bz0) : 0;
     const uint32_t valid = (1u << nk) - 1u;
@@ -490,12 +445,8 @@ int spheres_raster_dev(mvsim_ctx* ctx, const mvsim_sphere_set* s, const SpheresD
 {
     Box3 bx;
     for (int d = 0; d < 3; ++d) { bx.o[d] = origin[d]; bx.n[d] = (int)dim[d]; }
-    const int nbx = (int)((dim[0] + BX - 1) / BX), nby = (int)((dim[1] + BY - 1) / BY), nbz = (int)((dim[2] + BZ - 1) / BZ);
-    const uint64_t nb = (uint64_t)nbx * nby * nbz;
-    if (nb >= ((uint64_t)1 << 31)) {
-        set_error("invalid argument: sphere raster: image of %llu bricks", (unsigned long long)nb);
-        return MVSIM_EINVAL;
-    }
+    BrickGrid grid;
+    MVSIM_TRY(brick_grid(dim, "sphere raster", &grid));
     // sphere ranges of at most `cap` pairs (one sphere alone may exceed it: it cannot be divided)
     const long long cap = ctx->opt.beads_pair_cap;
     std::vector<long long> first{0};
@@ -514,31 +465,14 @@ int spheres_raster_dev(mvsim_ctx* ctx, const mvsim_sphere_set* s, const SpheresD
     const size_t npieces = first.size() - 1;
     for (size_t p = 0; p < npieces; ++p) max_count = std::max(max_count, first[p + 1] - first[p]);
     const long long max_slots = max_pairs + 1;
-    if (max_slots >= ((long long)1 << 31) || max_count >= ((long long)1 << 31)) {
-        set_error("invalid argument: sphere raster: a range of %lld pairs", max_slots);
-        return MVSIM_EINVAL;
-    }
-    size_t scan_tmp = 0, sort_tmp = 0;
-    MVSIM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)max_count, ctx->stream));
-    MVSIM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr,
-                                                 (uint32_t*)nullptr, (int)max_slots, 0, 32, ctx->stream));
-    MVSIM_TRY(ctx->proc_buf[3].reserve((size_t)(2 * max_count + (long long)nb + 1) * sizeof(uint32_t)));
-    MVSIM_TRY(ctx->proc_buf[4].reserve((size_t)(2 * max_slots) * sizeof(uint32_t)));
-    MVSIM_TRY(ctx->proc_buf[5].reserve((size_t)(2 * max_slots) * sizeof(uint32_t)));
-    MVSIM_TRY(ctx->proc_buf[6].reserve(std::max<size_t>(16, std::max(scan_tmp, sort_tmp))));
+    BrickBins bins;
+    MVSIM_TRY(bins.reserve(ctx->stream, max_count, max_slots, grid.nb, ctx->proc_buf[3], ctx->proc_buf[4], ctx->proc_buf[5], ctx->proc_buf[6],
+                           "invalid argument: sphere raster: a range of %lld pairs"));
     unsigned short* owned = nullptr;
     if (npieces > 1) {
-        MVSIM_TRY(ctx->proc_buf[7].reserve((size_t)(dim[0] * dim[1]) * (size_t)nbz * sizeof(unsigned short)));
+        MVSIM_TRY(ctx->proc_buf[7].reserve((size_t)(dim[0] * dim[1]) * (size_t)grid.nbz * sizeof(unsigned short)));
         owned = ctx->proc_buf[7].as<unsigned short>();
     }
-    uint32_t* counts = ctx->proc_buf[3].as<uint32_t>();
-    uint32_t* offs = counts + max_count;
-    uint32_t* starts = offs + max_count;
-    uint32_t* keys = ctx->proc_buf[4].as<uint32_t>();
-    uint32_t* vals = ctx->proc_buf[5].as<uint32_t>();
-    const uint32_t nkeys = (uint32_t)nb;
-    int end_bit = 1;
-    while (end_bit < 32 && ((uint64_t)nkeys >> end_bit) != 0) ++end_bit;
     for (size_t p = 0; p < npieces; ++p) {
         const long long a = first[p], count = first[p + 1] - a;
         long long slots = 1;
@@ -548,24 +482,16 @@ int spheres_raster_dev(mvsim_ctx* ctx, const mvsim_sphere_set* s, const SpheresD
         }
         const dim3 gb((unsigned)((count + 255) / 256));
         if (count > 0) {
-            hipLaunchKernelGGL(k_sph_cull, gb, dim3(256), 0, ctx->stream, sd.centres, sd.radii, a, count, bx, counts);
+            hipLaunchKernelGGL(k_sph_cull, gb, dim3(256), 0, ctx->stream, sd.centres, sd.radii, a, count, bx, bins.counts);
             MVSIM_HIP(hipGetLastError());
-            size_t t = ctx->proc_buf[6].bytes;
-            MVSIM_HIP(hipcub::DeviceScan::ExclusiveSum(ctx->proc_buf[6].p, t, counts, offs, (int)count, ctx->stream));
-            hipLaunchKernelGGL(k_sph_emit, gb, dim3(256), 0, ctx->stream, sd.centres, sd.radii, a, count, bx, counts, offs, keys, vals, nbx, nby);
+            MVSIM_TRY(bins.scan(ctx->stream, count));
+            hipLaunchKernelGGL(k_sph_emit, gb, dim3(256), 0, ctx->stream, sd.centres, sd.radii, a, count, bx, bins.counts, bins.offs, bins.keys[0],
+                               bins.vals[0], grid);
             MVSIM_HIP(hipGetLastError());
         }
-        const long long pad_blocks = std::min<long long>(4096, (slots + 255) / 256);
-        hipLaunchKernelGGL(k_sph_pad, dim3((unsigned)pad_blocks), dim3(256), 0, ctx->stream, counts, offs, count, keys, vals, slots, nkeys);
-        MVSIM_HIP(hipGetLastError());
-        size_t t = ctx->proc_buf[6].bytes;
-        MVSIM_HIP(hipcub::DeviceRadixSort::SortPairs(ctx->proc_buf[6].p, t, keys, keys + max_slots, vals, vals + max_slots, (int)slots, 0,
-                                                     end_bit, ctx->stream));
-        hipLaunchKernelGGL(k_sph_starts, dim3((unsigned)(((long long)nkeys + 1 + 255) / 256)), dim3(256), 0, ctx->stream, keys + max_slots,
-                           slots, starts, nkeys);
-        MVSIM_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_sph_render, dim3((unsigned)nb), dim3(256), 0, ctx->stream, (const SphRec*)sd.recs + a, vals + max_slots, starts,
-                           out, owned, bx, nbx, nby, sd.background, combine, p == 0 ? 1 : 0, p + 1 == npieces ? 1 : 0);
+        MVSIM_TRY(bins.finish(ctx->stream, count, slots, grid.nb));
+        hipLaunchKernelGGL(k_sph_render, dim3(grid.nb), dim3(256), 0, ctx->stream, (const SphRec*)sd.recs + a, bins.vals[1], bins.starts, out,
+                           owned, bx, grid, sd.background, combine, p == 0 ? 1 : 0, p + 1 == npieces ? 1 : 0);
         MVSIM_HIP(hipGetLastError());
     }
     return MVSIM_OK;

@@ -184,6 +184,31 @@ def test_volume_inject_is_bit_exact_on_random_point_lists(ctx, sigma, normalized
     assert _same(image, want_i) and _same(weight, want_w)
 
 
+def test_volume_inject_of_points_that_reach_no_voxel_leaves_the_volumes_as_they_are(ctx):
+    """A non-empty list whose every box misses the volume (no multiple of the 32 x 8 x 16 brick): no pair at all, every brick's list
+    is empty, image and weight keep their bits.  With one NaN coordinate added the C ABI refuses the list before it touches either
+    volume (mvsim.h: positions must be finite) -- the cull's own NaN guard cannot be reached from outside -- and again both keep their bits."""
+    rng = np.random.default_rng(23)
+    shape = (21, 33, 40)
+    dims = np.array(shape[::-1], dtype=np.float64)
+    far = np.concatenate([dims + 20.0 + rng.random((200, 3)) * 50.0,                 # boxes beyond the last voxel on every axis
+                          -20.0 - rng.random((200, 3)) * 50.0,                      # boxes in front of the first
+                          (rng.random((200, 3)) - 0.5) * 1.0e12 + 3.0e12,           # beyond the cull's 1e9: no box is formed
+                          np.array([[10.0, 10.0, -30.0], [10.0, 80.0, 10.0], [-7.0, 10.0, 10.0]])])   # inside on two axes
+    inten = rng.standard_normal(len(far)) * 3.0
+    image = rng.random(shape).astype(np.float32) + 0.5
+    weight = rng.random(shape).astype(np.float32) + 0.5
+    want_i, want_w = image.copy(), weight.copy()
+    for normalized in (False, True):
+        ctx.volume_inject(image, weight, (1.0, 0.7, 2.0), far, inten, normalized)
+        assert _same(image, want_i) and _same(weight, want_w)
+    with_nan = far.copy()
+    with_nan[17, 1] = np.nan
+    with pytest.raises(ValueError):
+        ctx.volume_inject(image, weight, (1.0, 0.7, 2.0), with_nan, inten)
+    assert _same(image, want_i) and _same(weight, want_w)
+
+
 def test_volume_inject_honours_the_order_and_hides_its_chunks(mvs):
     rng = np.random.default_rng(22)
     shape = (36, 40, 48)

@@ -148,6 +148,46 @@ def test_stacked_views_equal_single_views_and_offsets_equal_lists(mvs, ctx):
         assert np.array_equal(copies[v], mvs.beads._adjust(cut[v], *interval))
 
 
+EDGE_INTERVAL = ((0, 0, 0), (40, 33, 21))      # 2 x 5 x 2 bricks of 32 x 8 x 16, none of them whole
+
+
+def _all_zero(r):
+    return all(not f.view(np.uint32).any() for f in r["f32"]) and all(not u.any() for u in r["u16"])
+
+
+def test_empty_bead_list_gives_positive_zero_images(ctx):
+    """No bead at all: the binner sorts its one padded slot, every brick's list is empty, every voxel is written +0.0f / 0."""
+    r = ctx.render_beads(np.zeros((0, 3)), EDGE_INTERVAL, (1.0, 1.0, 3.0), f32=True, u16=True)
+    assert r["f32"][0].shape == (21, 33, 40) and r["u16"][0].shape == (21, 33, 40)
+    assert _all_zero(r)
+
+
+def test_empty_view_between_two_views_of_one_call(ctx):
+    """view_offsets with an empty view in the middle: a job without pairs between jobs with pairs, its keys a run of empty lists."""
+    rng = np.random.default_rng(31)
+    sigma = (1.0, 1.0, 3.0)
+    pts = _cloud(rng, 200, EDGE_INTERVAL)
+    k = 90
+    r = ctx.render_beads(pts, EDGE_INTERVAL, sigma, view_offsets=[0, k, k, len(pts)], f32=True, u16=True)
+    assert len(r["f32"]) == 3 and len(r["u16"]) == 3
+    assert not r["f32"][1].view(np.uint32).any() and not r["u16"][1].any()
+    for v, part in ((0, pts[:k]), (2, pts[k:])):
+        single = ctx.render_beads(part, EDGE_INTERVAL, sigma, f32=True, u16=True)
+        assert single["f32"][0].any()
+        assert np.array_equal(r["f32"][v].view(np.uint32), single["f32"][0].view(np.uint32))
+        assert np.array_equal(r["u16"][v], single["u16"][0])
+
+
+def test_beads_that_all_lie_outside_the_interval_give_zero_images(ctx):
+    """A non-empty list of which the cull keeps nothing: counts that scan to zero pairs, so the pad starts at slot 0."""
+    rng = np.random.default_rng(32)
+    mx = np.array(EDGE_INTERVAL[1], dtype=np.float64)
+    far = mx + 5.0 + rng.random((150, 3)) * 30.0                          # beyond max on every axis
+    near = np.array([[-1e-9, 10.0, 10.0], [20.0, 33.0 + 1e-9, 10.0], [20.0, 10.0, -0.5], [np.nan, 10.0, 10.0]])
+    r = ctx.render_beads(np.concatenate([far, near, -far]), EDGE_INTERVAL, (1.0, 1.0, 3.0), f32=True, u16=True)
+    assert _all_zero(r)
+
+
 def test_large_dense_case_on_the_device(mvs, ctx):
     """10^6 beads, 2048 x 2048 x 512, 4 angles, float and uint16 images resident on the device."""
     nx, ny, nz = 2048, 2048, 512
