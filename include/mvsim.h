@@ -730,6 +730,79 @@ int mvsim_register_beads(mvsim_ctx* ctx, const void* pos_a, int64_t stride_a, in
                          const mvsim_match_params* params, mvsim_registration* result, mvsim_match* candidates_or_null,
                          unsigned char* mask_or_null);
 
+/* ---- view fusion: affine resampling into one frame, blended average or aligned views ----------------------------------------------
+ * The consumer of mvsim_register_beads: V views, each with a forward matrix view -> output frame, are resampled into a caller-chosen
+ * output interval and either averaged under smooth border weights (the fused volume) or handed back one by one with their weight
+ * volumes (the aligned views, which mvsim_normalize_weights_dev and mvsim_deconvolve_dev take as they are).  The reference has no
+ * fusion; the recipe is this one, and every arithmetic step is stated so that a literal restatement reproduces the result bit for bit.
+ * Volumes are x fastest with dim = {Nx, Ny, Nz}.  A source is float, or uint16_t widened with one (float)v on load (MVSIM_SRC_F32 /
+ * MVSIM_SRC_U16; one type for all views of a call).  All arithmetic below is fp64, every + - * / an operation of its own (no fused
+ * multiply-add), every product chain and every sum evaluated as parenthesised.
+ * 1. Inverse.  View v has the forward matrix m = [A | t], 3 x 4 row-major (what mvsim_registration.m holds for A -> B).  With
+ *    m00 .. m22 = A, det, idet = 1.0 / det and the nine i_rc = (...) * idet are exactly the formulas of step 5 of the detector, and
+ *        it_r = -((i_r0 * t_x + i_r1 * t_y) + i_r2 * t_z)
+ *    If any of the 12 entries is non-finite, or det is zero or non-finite, the view contributes nothing anywhere (in aligned mode its
+ *    outputs are all zero) and its status word is MVSIM_FUSE_SINGULAR; otherwise the status word is 0.
+ * 2. Position.  For output voxel l: o_d = (double)(out_min_d + l_d) (out_min may be negative), and
+ *        p_r = ((it_r + i_r2 * o_z) + i_r1 * o_y) + i_r0 * o_x
+ * 3. Inside.  View v covers the voxel when 0.0 <= p_d && p_d <= (double)(N_d - 1) for all three axes; a NaN is outside.
+ * 4. Sample.  f_d = floor(p_d), u_d = p_d - f_d, lo_d = (int64)f_d, hi_d = min(lo_d + 1, N_d - 1).  The eight voxels v_abc (a, b, c in
+ *    {0 = lo, 1 = hi} along x, y, z) are widened to double; along x: c_bc = v_0bc + u_x * (v_1bc - v_0bc); along y: c_c = c_0c + u_y *
+ *    (c_1c - c_0c); along z: s = c_0 + u_z * (c_1 - c_0); s_f = (float)s.
+ * 5. Border weight.  g_d = (double)(N_d - 1) - p_d;  e_d = p_d < g_d ? p_d : g_d;  r_d = 1.0 unless e_d < blend_d, and then
+ *    q = e_d / blend_d, r_d = (q * q) * (3.0 - 2.0 * q) (a smoothstep: it restates exactly, the usual cosine does not).
+ *    w = (r_x * r_y) * r_z.  blend_d = 0 gives r_d = 1 everywhere inside.
+ * 6. Fused volume.  num = den = +0.0; over the views that cover the voxel, in ascending v: num = num + w * (double)s_f, den = den + w.
+ *    out = den > 0.0 ? (float)(num / den) : background; the optional second output is (float)den.  Non-finite samples propagate as
+ *    the arithmetic gives (0 * inf is NaN).
+ * 7. Aligned views.  Per view: aligned_v[l] = inside ? s_f : 0.0f, weight_v[l] = inside ? (float)w : 0.0f.
+ * A block may skip a view whose box its brick of output provably misses; the skip never changes a bit. */
+#define MVSIM_FUSE_SINGULAR 1
+typedef struct mvsim_fuse_params {
+    double  blend[3];          /* default 8, 8, 8 voxels (a convention); >= 0 and finite */
+    float   background;        /* default 0: where no view has weight */
+    int32_t src_type;          /* default MVSIM_SRC_F32 */
+} mvsim_fuse_params;           /* 32 bytes */
+typedef struct mvsim_fuse_view {
+    const void*   src;         /* the view's voxels (DEVICE for the _dev calls, HOST for the others) */
+    int64_t       dim[3];
+    const double* m_dev;       /* non-null: 12 doubles in DEVICE memory (e.g. &result_dev->m[0]), m is ignored; _dev calls only */
+    double        m[12];       /* 3 x 4 row-major, view -> output frame */
+} mvsim_fuse_view;             /* 136 bytes */
+void mvsim_fuse_params_default(mvsim_fuse_params* p);
+/* Host only, no context: step 1.  *singular = 1 and inv untouched, or *singular = 0 and inv = [i | it] as 3 x 4 row-major. */
+int mvsim_fuse_invert(const double m[12], double inv[12], int* singular);
+/* Host only: the output interval that holds every view (intersection = 0) or that every view covers (intersection = 1), as bounding
+ * boxes.  m: 12 doubles per view, dims: 3 extents per view.  The 8 corners {0, N_d - 1} of every view go forward, each coordinate as
+ * ((m_r0 * x + m_r1 * y) + m_r2 * z) + m_r3; a view's box is floor of the minima .. ceil of the maxima; out_dim = max - min + 1.
+ * MVSIM_EINVAL: an empty intersection, a non-finite corner, n_views outside [1, MVSIM_MAX_VIEWS], an extent < 1. */
+int mvsim_fusion_bounds(const double* m, const int64_t* dims, int n_views, int intersection, int64_t out_min[3], int64_t out_dim[3]);
+/* Host only: the matrix that brings a view's PSF into the output frame as a small volume of out_kdim: PSF voxel k goes to
+ * A (k - c) + c' with c_d = kdim_d / 2, c'_d = out_kdim_d / 2 (integer divisions: the centre mvsim_convolve uses), so
+ * out = [A | c' - A c], t_r = (double)c'_r - ((A_r0 * c_x + A_r1 * c_y) + A_r2 * c_z).  mvsim_align_views with blend = 0 on the PSF
+ * volume, out_min = 0 and out_dim = out_kdim then resamples it. */
+int mvsim_fusion_psf_matrix(const double m[12], const int64_t kdim[3], const int64_t out_kdim[3], double out[12]);
+/* Host only: {x, y, z extent of the brick of output a block owns, most blocks a launch has}. */
+int mvsim_fusion_geometry(int64_t out[4]);
+/* Steps 1-6 on the device.  views: HOST array of n_views records whose src (and m_dev) are DEVICE pointers; fused_dev and
+ * sum_weights_dev_or_null: prod(out_dim) floats; status_dev_or_null: n_views int32 in DEVICE memory.  Asynchronous on the context's
+ * stream, nothing is read back: a prepare kernel inverts the matrices, host-given and device-given, into a context workspace that
+ * mvsim_release_caches frees, so detection -> registration -> fusion chain without a synchronisation.
+ * MVSIM_EINVAL, before the context is touched: a null pointer, n_views outside [1, MVSIM_MAX_VIEWS], an extent < 1, an out_dim entry
+ * < 1, a blend that is negative or not finite, a src_type outside the two, an output that overlaps a source. */
+int mvsim_fuse_views_dev(mvsim_ctx* ctx, const mvsim_fuse_view* views, int n_views, const int64_t out_min[3], const int64_t out_dim[3],
+                         const mvsim_fuse_params* params, float* fused_dev, float* sum_weights_dev_or_null, int32_t* status_dev_or_null);
+/* Steps 1-5 and 7.  aligned_dev: HOST array of n_views DEVICE pointers, entries may be NULL; weights_dev_or_null: the same, or NULL
+ * for no weight volume at all. */
+int mvsim_align_views_dev(mvsim_ctx* ctx, const mvsim_fuse_view* views, int n_views, const int64_t out_min[3], const int64_t out_dim[3],
+                          const mvsim_fuse_params* params, float* const* aligned_dev, float* const* weights_dev_or_null,
+                          int32_t* status_dev_or_null);
+/* The same two with HOST buffers and host matrices only (m_dev must be NULL); synchronous. */
+int mvsim_fuse_views(mvsim_ctx* ctx, const mvsim_fuse_view* views, int n_views, const int64_t out_min[3], const int64_t out_dim[3],
+                     const mvsim_fuse_params* params, float* fused, float* sum_weights_or_null, int32_t* status_or_null);
+int mvsim_align_views(mvsim_ctx* ctx, const mvsim_fuse_view* views, int n_views, const int64_t out_min[3], const int64_t out_dim[3],
+                      const mvsim_fuse_params* params, float* const* aligned, float* const* weights_or_null, int32_t* status_or_null);
+
 /* ---- extractSlices over Intervals of volumes that stay on the device (SimulateTileStitching.java:131-189) ---------------
  * Views.zeroMin(Views.interval(con, min, max)) run through extractSlices: output voxel (x, y, k) of the contiguous tile
  * tx x ty x mvsim_extract_nz(tz, inc), t_d = max_d - min_d + 1, is f(in[(min_x + x) + Nx ((min_y + y) + Ny (min_z + k inc))]).

@@ -918,6 +918,106 @@ JNIEXPORT jlong JNICALL JNI_FN(registerBeads)(JNIEnv* env, jclass, jlong h, jobj
     return static_cast<jlong>(r.n_candidates);
 }
 
+// ---- view fusion (mvsim_fuse_views, mvsim_align_views) ---------------------------------------------------------------------------
+namespace {
+// The views of a fusion call: direct Float- or (u16) ShortBuffers of the extents in dims (3 longs per view) with one 3 x 4 matrix each
+// in a direct DoubleBuffer of 12 V doubles.  ok == false after an exception.  Every length, null and capacity is checked here.
+struct FuseArgs {
+    mvsim_fuse_view v[MVSIM_MAX_VIEWS];
+    int64_t out_min[3], out_dim[3];
+    mvsim_fuse_params p;
+    int32_t* status = nullptr;
+    jsize n = 0;
+    bool ok = false;
+    FuseArgs(JNIEnv* env, jobjectArray views, jboolean u16, jlongArray dims, jobject m12, jlongArray omin, jlongArray odim, jdouble bx, jdouble by,
+             jdouble bz, jfloat background, jobject status_buf)
+    {
+        const char* iae = "java/lang/IllegalArgumentException";
+        if (!views || !dims || !m12 || !omin || !odim) { throw_new(env, iae, "fuse: null argument"); return; }
+        n = env->GetArrayLength(views);
+        if (n < 1 || n > MVSIM_MAX_VIEWS) { throw_new(env, iae, "fuse: 1..32 views"); return; }
+        if (env->GetArrayLength(dims) != 3 * n) { throw_new(env, iae, "fuse: three extents per view"); return; }
+        if (env->GetArrayLength(omin) < 3) { throw_new(env, iae, "fuse: outMin: long[3] expected"); return; }
+        Dim od(env, odim);
+        if (!od.ok) return;
+        jlong mn[3], nd[3 * MVSIM_MAX_VIEWS];
+        env->GetLongArrayRegion(omin, 0, 3, mn);
+        if (env->ExceptionCheck()) return;
+        env->GetLongArrayRegion(dims, 0, 3 * n, nd);
+        if (env->ExceptionCheck()) return;
+        const double* m = static_cast<const double*>(any_ptr(env, m12, 12 * static_cast<int64_t>(n), "fuse: matrix buffer missing or smaller than 12 doubles per view"));
+        if (!m) return;
+        for (int a = 0; a < 3; ++a) { out_min[a] = mn[a]; out_dim[a] = od.d[a]; }
+        for (jsize k = 0; k < n; ++k) {
+            for (int a = 0; a < 3; ++a) {
+                if (nd[3 * k + a] < 1 || nd[3 * k + a] > 0x7fffffff) { throw_new(env, iae, "fuse: view extents must be in 1 .. 2^31-1"); return; }
+                v[k].dim[a] = nd[3 * k + a];
+            }
+            jobject b = env->GetObjectArrayElement(views, k);
+            if (env->ExceptionCheck()) return;
+            v[k].src = any_ptr(env, b, v[k].dim[0] * v[k].dim[1] * v[k].dim[2], "fuse: view buffer missing or smaller than its dimensions");
+            if (!v[k].src) return;
+            v[k].m_dev = nullptr;
+            std::memcpy(v[k].m, m + 12 * k, sizeof(v[k].m));
+        }
+        if (status_buf) {
+            status = static_cast<int32_t*>(any_ptr(env, status_buf, n, "fuse: status buffer smaller than one int per view"));
+            if (!status) return;
+        }
+        mvsim_fuse_params_default(&p);
+        p.blend[0] = bx; p.blend[1] = by; p.blend[2] = bz;
+        p.background = background;
+        p.src_type = u16 ? MVSIM_SRC_U16 : MVSIM_SRC_F32;
+        ok = true;
+    }
+    int64_t out_n() const { return out_dim[0] * out_dim[1] * out_dim[2]; }
+};
+}  // namespace
+
+// mvsim_fuse_views: the blended average of the views in the interval outMin, outDim.  fused: a direct FloatBuffer of prod(outDim) floats;
+// sumWeights (or null): the same; status (or null): a direct IntBuffer of one int per view (MVSIM_FUSE_SINGULAR).
+JNIEXPORT void JNICALL JNI_FN(fuseViews)(JNIEnv* env, jclass, jlong h, jobjectArray views, jboolean u16, jlongArray dims, jobject m12,
+                                         jlongArray out_min, jlongArray out_dim, jdouble blend_x, jdouble blend_y, jdouble blend_z,
+                                         jfloat background, jobject fused, jobject sum_weights, jobject status)
+{
+    FuseArgs a(env, views, u16, dims, m12, out_min, out_dim, blend_x, blend_y, blend_z, background, status);
+    if (!a.ok) return;
+    float* out = fptr(env, fused, a.out_n(), "fuseViews: output buffer missing or smaller than the interval");
+    if (!out) return;
+    float* sw = fptr(env, sum_weights, a.out_n(), "fuseViews: sum-of-weights buffer smaller than the interval", true);
+    if (sum_weights && !sw) return;
+    throw_for(env, mvsim_fuse_views(ctx_of(h), a.v, static_cast<int>(a.n), a.out_min, a.out_dim, &a.p, out, sw, a.status));
+}
+
+// mvsim_align_views: one resampled volume and one weight volume per view.  aligned: direct FloatBuffers of prod(outDim) floats, entries
+// may be null; weights: null, or the same.
+JNIEXPORT void JNICALL JNI_FN(alignViews)(JNIEnv* env, jclass, jlong h, jobjectArray views, jboolean u16, jlongArray dims, jobject m12,
+                                          jlongArray out_min, jlongArray out_dim, jdouble blend_x, jdouble blend_y, jdouble blend_z,
+                                          jobjectArray aligned, jobjectArray weights, jobject status)
+{
+    FuseArgs a(env, views, u16, dims, m12, out_min, out_dim, blend_x, blend_y, blend_z, 0.0f, status);
+    if (!a.ok) return;
+    if (!aligned || env->GetArrayLength(aligned) != a.n || (weights && env->GetArrayLength(weights) != a.n)) {
+        throw_new(env, "java/lang/IllegalArgumentException", "alignViews: one output entry (and, with weights, one weight entry) per view");
+        return;
+    }
+    float *al[MVSIM_MAX_VIEWS], *wt[MVSIM_MAX_VIEWS];
+    for (jsize k = 0; k < a.n; ++k) {
+        jobject b = env->GetObjectArrayElement(aligned, k);
+        if (env->ExceptionCheck()) return;
+        al[k] = fptr(env, b, a.out_n(), "alignViews: output buffer smaller than the interval", true);
+        if (b && !al[k]) return;
+        wt[k] = nullptr;
+        if (weights) {
+            b = env->GetObjectArrayElement(weights, k);
+            if (env->ExceptionCheck()) return;
+            wt[k] = fptr(env, b, a.out_n(), "alignViews: weight buffer smaller than the interval", true);
+            if (b && !wt[k]) return;
+        }
+    }
+    throw_for(env, mvsim_align_views(ctx_of(h), a.v, static_cast<int>(a.n), a.out_min, a.out_dim, &a.p, al, weights ? wt : nullptr, a.status));
+}
+
 // ---- mvsim_group_* -------------------------------------------------------------------------------------------------
 JNIEXPORT jlong JNICALL JNI_FN(groupCreate)(JNIEnv* env, jclass, jint ndev)
 {

@@ -134,6 +134,25 @@ final class MvsimNative
 			double ratio, double maxEpsilon, double minInlierRatio, long seed, int hypotheses, int maxRefits, int minInliers,
 			java.nio.ByteBuffer result, java.nio.ByteBuffer candidates, java.nio.ByteBuffer mask );
 
+	/**
+	 * View fusion (mvsim_fuse_views; include/mvsim.h states the recipe): every view is resampled through its 3 x 4 matrix view to output
+	 * frame into the interval outMin, outDim and averaged under smooth border weights.  views are direct FloatBuffers (or, u16, direct
+	 * ShortBuffers) of the extents in dims (3 longs per view); m12 a direct DoubleBuffer of 12 doubles per view; fused a direct
+	 * FloatBuffer of prod(outDim) floats; sumWeights (or null) the same; status (or null) a direct IntBuffer of one int per view
+	 * (1: the matrix is singular or not finite, the view is absent).  The shim checks every length first.
+	 */
+	static native void fuseViews( long ctx, java.nio.Buffer[] views, boolean u16, long[] dims, java.nio.DoubleBuffer m12, long[] outMin,
+			long[] outDim, double blendX, double blendY, double blendZ, float background, FloatBuffer fused, FloatBuffer sumWeights,
+			java.nio.IntBuffer status );
+
+	/**
+	 * Aligned views (mvsim_align_views): one resampled volume and one weight volume per view, what normalizeWeights and deconvolve
+	 * take.  aligned: direct FloatBuffers of prod(outDim) floats, entries may be null; weights: null, or the same.
+	 */
+	static native void alignViews( long ctx, java.nio.Buffer[] views, boolean u16, long[] dims, java.nio.DoubleBuffer m12, long[] outMin,
+			long[] outDim, double blendX, double blendY, double blendZ, FloatBuffer[] aligned, FloatBuffer[] weights,
+			java.nio.IntBuffer status );
+
 	/** Fused loop body of SimulateMultiViewDataset.main (:570-585); rot/att/con may be null (then they never leave HBM). */
 	static native double simulateView( long ctx, FloatBuffer gt, long[] dim, FloatBuffer psf, long[] kdim,
 			int axis, int degrees, double delta, float minValue, float targetAverage, int inc, float snr, long seed, int stream,

@@ -129,6 +129,19 @@ class Registration(C.Structure):
                 ("flags", C.c_int32)]
 
 
+class FuseParams(C.Structure):
+    """mvsim_fuse_params: the settings of the view fusion (mvsim_fuse_params_default fills them)."""
+    _fields_ = [("blend", C.c_double * 3), ("background", C.c_float), ("src_type", C.c_int32)]
+
+
+class FuseView(C.Structure):
+    """mvsim_fuse_view: one view of a fusion -- its voxels, its extents and its matrix view -> output frame (host, or 12 doubles in
+    device memory)."""
+    _fields_ = [("src", C.c_void_p), ("dim", C.c_int64 * 3), ("m_dev", C.c_void_p), ("m", C.c_double * 12)]
+
+
+MVSIM_MAX_VIEWS = 32
+MVSIM_FUSE_SINGULAR = 1
 MVSIM_REG_MAX_POINTS, MVSIM_REG_FIT_CHUNK = 65536, 256
 MVSIM_REG_FEW_CANDIDATES, MVSIM_REG_NO_MODEL, MVSIM_REG_CAPPED, MVSIM_REG_FEW_INLIERS = 1, 2, 4, 8
 MVSIM_SRC_F32, MVSIM_SRC_U16 = 0, 1
@@ -341,6 +354,15 @@ SIGNATURES = {
     "mvsim_register_beads_dev": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(MatchParams),
                                            _vp, _vp, _vp]),
     "mvsim_register_beads": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int64, C.POINTER(MatchParams), _vp, _vp, _vp]),
+    "mvsim_fuse_params_default": (None, [C.POINTER(FuseParams)]),
+    "mvsim_fuse_invert": (C.c_int, [_dp, _dp, C.POINTER(C.c_int)]),
+    "mvsim_fusion_bounds": (C.c_int, [_dp, _i64p, C.c_int, C.c_int, _i64p, _i64p]),
+    "mvsim_fusion_psf_matrix": (C.c_int, [_dp, _i64p, _i64p, _dp]),
+    "mvsim_fusion_geometry": (C.c_int, [_i64p]),
+    "mvsim_fuse_views_dev": (C.c_int, [_vp, C.POINTER(FuseView), C.c_int, _i64p, _i64p, C.POINTER(FuseParams), _vp, _vp, _vp]),
+    "mvsim_align_views_dev": (C.c_int, [_vp, C.POINTER(FuseView), C.c_int, _i64p, _i64p, C.POINTER(FuseParams), C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    "mvsim_fuse_views": (C.c_int, [_vp, C.POINTER(FuseView), C.c_int, _i64p, _i64p, C.POINTER(FuseParams), _vp, _vp, _vp]),
+    "mvsim_align_views": (C.c_int, [_vp, C.POINTER(FuseView), C.c_int, _i64p, _i64p, C.POINTER(FuseParams), C.POINTER(_vp), C.POINTER(_vp), _vp]),
 }
 
 _lib = None

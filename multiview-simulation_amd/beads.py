@@ -204,6 +204,18 @@ class SimulateBeads:
         m = self.matrices()
         return register_rendered(_ctx(), self.points, m[view_a], m[view_b], self.intervalRender, self.sigma, detector, matcher, u16)
 
+    def fuse(self, views=None, reference: int = 0, detector=None, matcher=None, u16: bool = False, params=None):
+        """Render ``views`` (default: all), detect their beads, register each against view ``reference`` (an index into ``views``) and
+        fuse them into the reference's interval, all on the device.  Returns (fused, registrations, fused_with_true_matrices):
+        ``registrations[v]`` is the record of view v -> reference, None at the reference itself."""
+        from .fusion import fuse_rendered
+        if self.points is None:
+            self.points = self.randomPoints(self.numPoints, self.rangeSimulation, self.rnd)
+        m = self.matrices()
+        picked = list(range(len(m))) if views is None else [int(v) for v in views]
+        return fuse_rendered(_ctx(), self.points, [m[v] for v in picked], self.intervalRender, self.sigma, reference, detector, matcher, u16,
+                             params)
+
     @staticmethod
     def randomPoints(numPoints: int, range_, rnd) -> np.ndarray:
         """:151-166 -- (numPoints, 3) doubles.  A JavaRandom is replayed natively and advanced; any other object with
@@ -361,6 +373,13 @@ class SimulateBeads2:
         from .registration import register_rendered
         return register_rendered(_ctx(), self.points, self.transform(*view_a).m, self.transform(*view_b).m, self.intervalRender, self.sigma,
                                  detector, matcher, u16)
+
+    def fuse(self, views, reference: int = 0, detector=None, matcher=None, u16: bool = False, params=None):
+        """``views``: (tp, angle, channel, tile, illumination) keys.  Rendered, detected, registered against ``views[reference]`` and
+        fused into its interval on the device.  Returns (fused, registrations, fused_with_true_matrices) as SimulateBeads.fuse does."""
+        from .fusion import fuse_rendered
+        return fuse_rendered(_ctx(), self.points, [self.transform(*v).m for v in views], self.intervalRender, self.sigma, reference, detector,
+                             matcher, u16, params)
 
     def getImage(self, tp: int, angle: int, channel: int, tile: int, illumination: int) -> np.ndarray:
         """LegacySimulatedBeadsImgLoader2.getImage (:65-85): uint16, written by the kernel directly."""

@@ -272,6 +272,7 @@ struct mvsim_ctx {
     mvsim::DevBuf decon_stat;               // ... per-block partials, per-view sums and the statistics of every step of a call
     mvsim::DevBuf detect_buf[6];            // bead detector (api_detect.cpp): the two half-blurred volumes, D, the peak list, block counts + offsets + ballots, scan temp
     mvsim::DevBuf register_buf[4];          // bead registration (api_register.cpp): the stages' lists of one whole call, split partials, per-point bests, RANSAC pairs + key + mask
+    mvsim::DevBuf fuse_buf;                 // view fusion (api_fuse.cpp): the views' inverted matrices, sources and outputs of the current call
     int64_t       weight_dim[3] = {0, 0, 0};
     mvsim::DevBuf host_gt, host_rot, host_att, host_con;   // device twins of the host-buffer simulate_view (grow-only)
     mvsim::DevBuf partials;                 // doubles: block partial sums + [sum, corr]
@@ -370,7 +371,7 @@ template <class F> inline void mvsim_ctx::each_workspace(F&& f)
     for (mvsim::DevBuf* b : {&vol_a, &vol_b, &vol_c, &out_buf, &psf_dev, &stencil_psf, &fft_real, &fft_spec_img, &fft_spec_psf, &fft_work,
                              &pqueue, &view_tab, &interval_tab, &sphere_list, &weight_img, &plane_flags, &host_gt, &host_rot, &host_att, &host_con, &cfft_f, &cfft_g,
                              &cfft_g1, &cfft_g2, &partials_z, &async_gt[0], &async_gt[1], &async_acq[0], &async_acq[1], &async_counts[0].dev,
-                             &async_counts[1].dev, &sync_counts.dev, &decon_work[0], &decon_work[1], &decon_psf, &decon_stat})
+                             &async_counts[1].dev, &sync_counts.dev, &decon_work[0], &decon_work[1], &decon_psf, &decon_stat, &fuse_buf})
         f(*b, 0);
     f(partials, WS_KEPT);
     f(partials_e, WS_KEPT);
