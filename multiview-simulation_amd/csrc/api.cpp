@@ -70,6 +70,7 @@ int parse_option(Options& o, const char* name, const char* value)
         return MVSIM_OK;
     }
     if (n == "skip_empty") return flag(&o.skip_empty);
+    if (n == "skip_rows") return flag(&o.skip_rows);
     if (n == "fft_pad") {
         long long a = 0, b = 0, c = 0;
         if (v == "auto" || v.empty()) { o.fft_pad[0] = o.fft_pad[1] = o.fft_pad[2] = 0; return MVSIM_OK; }

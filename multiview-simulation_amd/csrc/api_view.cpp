@@ -55,9 +55,10 @@ static int view_enqueue(mvsim_ctx* ctx, const float* gt, const int64_t dim[3], c
     // ... and when the FFT passes follow, their x transform rides in the same kernel: `att` leaves the chip only if asked for
     bool x_done = false;
     const int* plane_nz = nullptr;
+    const unsigned int* row_bits = nullptr;
     ev_begin(ctx, ST_ROTATE);
     if (pick_method(p->conv_method, kdim) == 1)
-        MVSIM_TRY(rotate_attenuate_fftx(ctx, gt, rot, o->att, dim, kdim, inv, p->delta, &x_done, &plane_nz));
+        MVSIM_TRY(rotate_attenuate_fftx(ctx, gt, rot, o->att, dim, kdim, inv, p->delta, &x_done, &plane_nz, 0, -1, &row_bits));
     fused = x_done;
     if (!x_done) {
         if (!att) { MVSIM_TRY(ctx->vol_b.reserve(vbytes)); att = ctx->vol_b.as<float>(); }
@@ -90,6 +91,7 @@ static int view_enqueue(mvsim_ctx* ctx, const float* gt, const int64_t dim[3], c
     tail.corr_n = n; tail.min_value = p->min_value; tail.target_average = p->target_average;
     tail.x_done = x_done;
     tail.plane_nz = x_done ? plane_nz : nullptr;
+    tail.row_bits = x_done ? row_bits : nullptr;
     if (method == 1 && ctx->opt.fuse_tail && (!noise || ctx->opt.poisson_queue == 1)) {
         const size_t qb = noise ? fused_tail_queue_bytes(dim, kdim, p->inc, materialise, ctx->opt) : 0;
         if (!noise || qb > 0) {
@@ -169,8 +171,9 @@ static std::string view_graph_key(mvsim_ctx* ctx, const float* gt, const int64_t
     add(&o->rot, sizeof(o->rot)); add(&o->att, sizeof(o->att)); add(&o->con, sizeof(o->con)); add(&o->acq, sizeof(o->acq));
     add(&ctx->stream, sizeof(ctx->stream));
     const Options& q = ctx->opt;
-    const int oo[14] = {q.zpass, q.rocfft ? 1 : 0, q.fused_rotate, q.poisson_queue, q.early_sum ? 1 : 0, q.fuse_tail ? 1 : 0, q.psf_overlap ? 1 : 0,
-                        q.attenuate_scan ? 1 : 0, q.fused_fftx, q.zconv_strided ? 1 : 0, q.skip_empty ? 1 : 0, q.exp, q.poisson_queue_share, ctx->queue_share_learned};
+    const int oo[15] = {q.zpass, q.rocfft ? 1 : 0, q.fused_rotate, q.poisson_queue, q.early_sum ? 1 : 0, q.fuse_tail ? 1 : 0, q.psf_overlap ? 1 : 0,
+                        q.attenuate_scan ? 1 : 0, q.fused_fftx, q.zconv_strided ? 1 : 0, q.skip_empty ? 1 : 0, q.exp, q.poisson_queue_share, ctx->queue_share_learned,
+                        q.skip_rows ? 1 : 0};
     add(oo, sizeof(oo));
     add(q.fft_pad, sizeof(q.fft_pad));
     return k;

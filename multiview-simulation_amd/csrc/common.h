@@ -215,6 +215,8 @@ struct Options {
                                        // the pieces that have arrived among themselves (mvsim_comm_broadcast_plan; comm.cpp: bcast_pipelined)
     int64_t fft_pad[3] = {0, 0, 0};    // explicit padded sizes on the rocFFT path (0: choose)
     bool    skip_empty = true;         // convolution passes skip planes the fused rotate kernel found empty (exact; option for A/B runs)
+    bool    skip_rows = true;          // ... and, where those flags are in use, the rotate kernel does not store the rows without a non-zero
+                                       // voxel and pass B does not read them (row_bits.h; exact; option for A/B runs)
     int64_t beads_pair_cap = (int64_t)1 << 28;   // bead renderer and volume injection: (brick, item) pairs one chunk may bin; larger calls run in chunks (beads.hip, aberrations.hip)
     int64_t reject_batch = 0;          // rejection sampler: trials per launch (0 = auto: 4 per wanted sample, 4096 .. 2^20) (procedural.hip)
     int     dog_pass = 0;              // the DoG kernels a call launches (detect.hip): 0 both, 1 the xy kernel alone, 2 the z kernel alone -- for
@@ -593,13 +595,17 @@ struct ConvTail {
     // in (with x_done): per-plane flags the fused rotate kernel has set (1 = the attenuated plane holds a non-zero voxel; device
     // array of dim[2] ints): passes B .. E skip the planes whose inputs are all empty -- exact, their spectra are zero
     const int* plane_nz = nullptr;
+    // in (with x_done): the row-bit record of the fused rotate kernel (row_bits.h; device array, dim[2] records of row_bits_words(Py)
+    // words).  Non-null means that kernel has NOT written the rows whose bit is clear: pass B must read the bits, whatever else the
+    // convolution decides
+    const unsigned int* row_bits = nullptr;
 };
 // bytes of queue workspace the fused tail needs for this geometry (0: the geometry has no fused tail)
 size_t fused_tail_queue_bytes(const int64_t dim[3], const int64_t kdim[3], int inc, bool con_wanted, const Options& opt);
 int comm_allreduce_f64_on_stream(mvsim_ctx* cc, double* value_dev, hipStream_t s);      // comm.cpp
 int rotate_attenuate_fftx(mvsim_ctx* ctx, const float* gt, float* rot_or_null, float* att_or_null, const int64_t dim[3],
                           const int64_t kdim[3], const Affine& inv, double delta, bool* done, const int** plane_nz = nullptr,
-                          int z_first = 0, int nzl = -1);
+                          int z_first = 0, int nzl = -1, const unsigned int** row_bits = nullptr);
 int fft_convolve(mvsim_ctx* ctx, const float* img_dev, const int64_t dim[3], const float* psf_dev,
                  const int64_t kdim[3], float* out_dev, ConvTail* tail);
 void fft_release(mvsim_ctx* ctx);

@@ -415,6 +415,10 @@ struct RotFftArgs {
     Affine a;
     double delta;
     int*   plane_nz;         // [nz], zeroed by the caller: set to 1 for every plane that holds a non-zero attenuated voxel (null: not wanted)
+    // the row-bit record (row_bits.h; null: not wanted): plane zl's at rowbits + zl * row_bits_words(py).  With it, rows without a
+    // non-zero attenuated voxel are NOT stored -- their reader asks the bits; without it they are stored as zeros
+    unsigned int* rowbits;
+    int           ky;        // taps along y: the mirrored halo of the record
 };
 
 // half lengths the fused kernel is instantiated for (rows of up to 1024 voxels with PSFs of up to 64 taps); the plans --

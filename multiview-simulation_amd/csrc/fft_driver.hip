@@ -322,11 +322,13 @@ bool custom_fft_batchable(const mvsim_ctx* ctx, const int64_t dim[3], const int6
 // z_first / nzl: the planes of the rotated volume to compute (a z slab of a tiled view: its own planes and the halo the PSF reaches;
 // nzl < 0: all of them).  F then holds those planes from index 0, as pass A leaves them for custom_fft_convolve_slab.
 int rotate_attenuate_fftx(mvsim_ctx* ctx, const float* gt, float* rot_or_null, float* att_or_null, const int64_t dim[3],
-                          const int64_t kdim[3], const Affine& inv, double delta, bool* done, const int** plane_nz, int z_first, int nzl)
+                          const int64_t kdim[3], const Affine& inv, double delta, bool* done, const int** plane_nz, int z_first, int nzl,
+                          const unsigned int** row_bits)
 {
     using namespace fft;
     *done = false;
     if (plane_nz) *plane_nz = nullptr;
+    if (row_bits) *row_bits = nullptr;
     if (ctx->opt.fused_fftx == 0) return MVSIM_OK;
     if (!affine_is_x_rotation(inv)) return MVSIM_OK;
     ConvPlan pl;
@@ -371,9 +373,19 @@ int rotate_attenuate_fftx(mvsim_ctx* ctx, const float* gt, float* rot_or_null, f
         else ctx->views_since_flags = 0;
     }
     if (want_flags) {
-        MVSIM_TRY(ctx->plane_flags.reserve((size_t)(3 * nz + 1024) * sizeof(int)));   // flags, the dilated flags, the flag bit string
+        // Beside the flags, the row-bit records (row_bits.h; option skip_rows): the kernel then stores no row without a non-zero voxel
+        // and pass B -- k_fft_lines<FWD> of py points on this view's whole spectrum, nothing else -- reads the bits.  Not where pass B
+        // takes the split long-line form, which does not read them.
+        const bool want_rows = row_bits && ctx->opt.skip_rows && pl.zdirect && row_bits_len_ok(py) && !(py % 2 == 0 && lines_split_exists(py / 2));
+        const size_t flag_bytes = ((size_t)(3 * nz + 1024) * sizeof(int) + 255) & ~(size_t)255;   // flags, the dilated flags, the flag bit string
+        MVSIM_TRY(ctx->plane_flags.reserve(flag_bytes + (want_rows ? row_bits_bytes(py, nz) : 0)));
         a.plane_nz = ctx->plane_flags.as<int>();
         *plane_nz = a.plane_nz;
+        if (want_rows) {
+            a.rowbits = reinterpret_cast<unsigned int*>(ctx->plane_flags.as<char>() + flag_bytes);
+            a.ky = pl.k[1];
+            *row_bits = a.rowbits;
+        }
     }
     MVSIM_TRY(launch_rot_fftx(ctx, M, a, rot_or_null != nullptr || att_or_null != nullptr, ctx->opt.fused_fftx >= 2));
     *done = true;
@@ -401,6 +413,7 @@ struct ConvRun {
     double* scal;
     const int *pnz, *pnz_dil;       // planes the fused rotate kernel found empty (null: no flags): raw, dilated by the taps' reach,
     const unsigned int* pnz_bits;   // and as the z pass's bit string
+    const unsigned int* rowbits;    // the rotate kernel's row-bit record (null: it wrote every row): pass B's
 };
 
 // compact PSF intermediates: G1 [kz][ky][hxp] (x transformed), G2 [kz][py][hxp] (x,y transformed), G the full spectrum (FFT z pass only)
@@ -523,6 +536,9 @@ static int pass_b(mvsim_ctx* ctx, const ConvRun& r)
         b.outer_skip_len = std::max(0, pl.pz - (kz - 1 - kz / 2) - b.outer_skip_lo);
     }
     if (r.pnz) { b.nzflags = r.pnz; b.nz_stride = 1; }
+    // the rotate kernel of this view produced the row-bit record, i.e. left the rows whose bit is clear unwritten: read the bits
+    // (with or without the plane flags -- an empty plane's bits are all clear)
+    if (r.rowbits) { b.rowbits = r.rowbits; b.rowbits_stride = row_bits_words(pl.py); }
     ev_begin(ctx, ST_PASS_B);
     MVSIM_TRY(launch_lines(ctx, pl.py, FWD, false, b, hxp / pl.tile_y, pl.zdirect ? r.slab.nz_in * r.V : pl.pz - b.outer_skip_len));
     ev_end(ctx, ST_PASS_B);
@@ -743,6 +759,10 @@ int custom_fft_convolve_slab(mvsim_ctx* ctx, const float* img, const int64_t dim
     ev_begin(ctx, ST_CONVOLVE);
     if (x_done) {
         if (!pl.ymirror || r.V != 1) { set_error("x_done without the geometry of the fused x transform"); return MVSIM_EINVAL; }
+        if (tail->row_bits) {
+            if (r.is_slab || !pl.zdirect) { set_error("row bits on a view pass B cannot read them for"); return MVSIM_EINVAL; }
+            r.rowbits = tail->row_bits;
+        }
     } else {
         MVSIM_TRY(pass_a(ctx, r, img));
     }

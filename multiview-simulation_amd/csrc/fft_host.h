@@ -34,6 +34,8 @@ struct LinesArgs {
                                     // of the padded image are the rows themselves, read twice instead of transformed twice
     // planes known to be empty (null: none): a block whose outer index names an empty plane has nothing to read and -- because every
     // reader of its output asks the same flags -- nothing to write.  Outer index k = plane k * nz_stride of the flag array
+    // (Pass B behind the fused rotate kernel: that kernel may have left the rows without a non-zero voxel UNWRITTEN -- stale bytes of an
+    // earlier view.  Whoever reads its output must ask `rowbits` below as well as these flags.)
     const int*    nzflags;
     int           nz_stride;
     // blocked OUTER addressing (0: linear): outer index by sits at (by >> ZBS) * oblk + (by & (ZB - 1)) * outer -- the z-blocked
@@ -48,6 +50,11 @@ struct LinesArgs {
     const double2* wy;
     double*       sum_partial;
     int           pair_tiles;       // 8-column tiles: the two tiles of a 128-byte line on one XCD (see k_fft_lines; exp bit 4 clears it)
+    // FWD, not SPARSE (pass B): the row-bit record of the fused rotate kernel (row_bits.h; null: every row was written).  Outer index
+    // `by` finds its plane's bits at rowbits + by * rowbits_stride; position n of the line is loaded iff bit n is set and is +0
+    // otherwise -- the rotate kernel has not written that row.  Lengths with row_bits_len_ok only (launch_lines checks).
+    const unsigned int* rowbits;
+    int           rowbits_stride;
 };
 
 #ifndef MVSIM_ZBS
@@ -63,6 +70,15 @@ __device__ __forceinline__ int mirror_index(int i, int n)
     i %= p;
     if (i < 0) i += p;
     return i < n ? i : p - i;
+}
+
+// A tile row that is not wanted, loaded all the same from an address that is certainly mapped and cleared to +0 bits: an AND, not a
+// select -- a select whose operand is a load is turned back into a branch around the load (zconv.hip; k_fft_lines' masked form)
+__device__ __forceinline__ float4 keep4(float4 t, bool keep)
+{
+    const unsigned int m = keep ? 0xFFFFFFFFu : 0u;
+    return make_float4(__uint_as_float(__float_as_uint(t.x) & m), __uint_as_float(__float_as_uint(t.y) & m),
+                       __uint_as_float(__float_as_uint(t.z) & m), __uint_as_float(__float_as_uint(t.w) & m));
 }
 
 __device__ __forceinline__ long long line_off(int n, long long es, long long blk)

@@ -29,6 +29,12 @@ __device__ unsigned long long g_line_stamps[2][STAMP_BLOCKS][8];
 #define MVSIM_STAMP(k) do { } while (0)
 #endif
 
+// Pass B's rows whose row bit is clear (k_fft_lines): 0 = a branch around the load, 1 = the load from the tile's base under a mask
+// (keep4).  Both built and measured at 512^3 (profiles/row_bits_ab.txt); the product build keeps the branch.
+#ifndef MVSIM_ROWBITS_MASKED
+#define MVSIM_ROWBITS_MASKED 0
+#endif
+
 // where outer index `by` (a plane, or a row of the z-blocked layout seen from a pass along z: oblk != 0, see LinesArgs::src_oblk) starts
 __device__ __forceinline__ long long outer_off(int by, long long outer, long long oblk)
 {
@@ -73,7 +79,33 @@ void k_fft_lines(LinesArgs p)
     }
     MVSIM_STAMP(0);
     const int by = tile_o >= p.outer_skip_lo ? tile_o + p.outer_skip_len : tile_o;
-    if (p.nzflags) {
+    // Pass B behind the fused rotate kernel: the plane's row-bit record (row_bits.h), block-uniform loads requested in front of the
+    // plane flag so that one wait covers both -- no second trip to memory in front of the tile loads.  Row n = r0 + it * ROWS: with
+    // ROWS a multiple of 32 the words of iteration `it` are static and the bit is r0's; shorter tiles ask per row (below).
+    // null: every row was written -- the block takes the loop every other instance has, and no scalar load stands in front of its
+    // tile loads unless there are plane flags: a volume without empty rows pays one branch per block.  Only this instance has any of it.
+    constexpr bool ROWBITS = MODE == FWD && !SPARSE && row_bits_len_ok(L);
+    constexpr int RB_WPI = ROWS >= 32 ? ROWS / 32 : 1;            // words of the record per load iteration
+    constexpr int RB_N = (ROWBITS && ROWS >= 32) ? NIT * RB_WPI : 1;
+    unsigned int rb[RB_N];
+    const unsigned int* rec = nullptr;
+    if constexpr (ROWBITS) {
+        const int* const nzf = p.nzflags;
+        const unsigned int* const rbp = p.rowbits;
+        if (rbp) {
+            // No branch between the two loads -- behind one the compiler waits for the flag before it asks for the record: without
+            // flags the record's first word stands in and is not looked at.
+            rec = rbp + (long long)by * p.rowbits_stride;
+            const int flag = *(nzf ? nzf + by * p.nz_stride : reinterpret_cast<const int*>(rbp));
+            if constexpr (ROWS >= 32) {
+#pragma unroll
+                for (int i = 0; i < RB_N; ++i) rb[i] = i < row_bits_words(L) ? rec[i] : 0u;
+            }
+            if (nzf && flag == 0) return;                         // an empty plane: as below
+        } else if (nzf) {
+            if (nzf[by * p.nz_stride] == 0) return;
+        }
+    } else if (p.nzflags) {
         // block-uniform (one scalar load): nothing of an empty plane is read, transformed or stored -- its readers skip it on the
         // same flags.  Pass B: flags of the input planes; pass D: the dilated flags (a plane of the z pass's output is empty iff
         // every plane its Kz taps reach is), outer index k = plane k * nz_stride
@@ -94,6 +126,39 @@ void k_fft_lines(LinesArgs p)
         }
     }
     float4 v[NIT];
+    bool under_bits = false;                                      // (block-uniform; constant false in every other instance)
+    if constexpr (ROWBITS) {
+        if (rec) {
+            // The tile under the row bits: a row is loaded iff its bit is set and is +0 bits otherwise -- it was never written, and its
+            // (stale) line is not brought in.  The record's gap bits and the bits from Py on are clear: no other test.
+            under_bits = true;
+#pragma unroll
+            for (int it = 0; it < NIT; ++it) {
+                const int n = r0 + it * ROWS;
+                bool keep;
+                if constexpr (ROWS >= 32) {
+                    unsigned int w = rb[it * RB_WPI];
+                    if constexpr (RB_WPI > 1) {
+                        const int sel = __builtin_amdgcn_readfirstlane(r0 >> 5);           // wave-uniform: a wave's rows share a word
+#pragma unroll
+                        for (int k = 1; k < RB_WPI; ++k) w = sel == k ? rb[it * RB_WPI + k] : w;
+                    }
+                    keep = (w >> (r0 & 31)) & 1u;
+                } else {
+                    keep = n < L && ((rec[n >> 5] >> (n & 31)) & 1u);
+                }
+                const int sn = keep ? (p.src_mirror ? map_src(p.lmap, n) : n) : 0;
+#if MVSIM_ROWBITS_MASKED
+                // (the z pass's form: every load unconditional, an unwanted row from the tile's base -- certainly mapped -- and cleared)
+                v[it] = keep4(*reinterpret_cast<const float4*>(sbase + line_off(sn, p.src_es, p.src_blk)), keep);
+#else
+                v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (keep) v[it] = *reinterpret_cast<const float4*>(sbase + line_off(sn, p.src_es, p.src_blk));
+#endif
+            }
+        }
+    }
+    if (!under_bits) {
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int n = r0 + it * ROWS;
@@ -109,6 +174,7 @@ void k_fft_lines(LinesArgs p)
                 v[it] = *reinterpret_cast<const float4*>(sbase + line_off(sn, p.src_es, p.src_blk));
             }
         }
+    }
     }
     MVSIM_STAMP(1);
     for (int i = tid; i < L; i += T) tw[i] = p.tw[i];
@@ -424,7 +490,13 @@ int launch_lines(mvsim_ctx* s, int L, int mode, bool sparse, const LinesArgs& a0
     a.pair_tiles = (s->opt.exp & 4) ? 0 : 1;              // exp bit 4: 8-column tiles in plain grid order (A/B, tools/ab_env.sh)
     // lines of one block per CU: the image's y passes as two half-length transforms (k_fft_lines_split) unless exp bit 8 asks for the
     // one-block form; the PSF's sparse passes and the z-pass forms keep k_fft_lines
-    const LinesSplitFn split = L % 2 ? nullptr : lines_split_fn(L / 2);
+    // the row-bit record is read by k_fft_lines<FWD, not sparse> alone: whoever set it must get that kernel or an error, never a
+    // kernel that reads the unwritten rows
+    if (a.rowbits && (mode != FWD || sparse || !row_bits_len_ok(L) || a.rowbits_stride != row_bits_words(L))) {
+        set_error("custom FFT: row bits on a pass that does not read them (length %d, mode %d)", L, mode);
+        return MVSIM_EINVAL;
+    }
+    const LinesSplitFn split = (L % 2 || a.rowbits) ? nullptr : lines_split_fn(L / 2);
     if ((mode == FWD || mode == INV) && !sparse && !a.dst_tile_major && !(s->opt.exp & 8) && split && tiles % 2 == 0 &&
         (!a.src_mirror || (a.lmap.mode == 0 && a.lmap.b < a.lmap.n && a.lmap.a - a.lmap.n < a.lmap.n))) {
         const float2* tw2 = nullptr;

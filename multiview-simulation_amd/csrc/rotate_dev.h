@@ -12,6 +12,8 @@
 
 #include <math.h>
 
+#include "row_bits.h"
+
 #if defined(__HIPCC__)
 #define MVSIM_ROT_FN __host__ __device__ __forceinline__
 #else
@@ -163,6 +165,18 @@ __device__ __forceinline__ void write_plane_flag(unsigned int* blk_any, unsigned
     if (lane == 0 && plane_any != 0u) atomicOr(blk_any, 1u);
     __syncthreads();
     if (tid == 0) *flag = (int)*blk_any;
+}
+
+// The plane's row-bit record (row_bits.h) from the block's Ny data bits in LDS (`data`: ROW_BITS_MAX_WORDS words; whoever owned a
+// stored row has ORed its bit in, and the block has met at a barrier since).  ONE wave calls: 64 padded positions per ballot, two
+// words per trip, ordinary vector stores; the whole record on every launch, an empty plane's included.
+__device__ __forceinline__ void write_row_bits(const unsigned int* data, unsigned int* __restrict__ rec, int ny, int ky, int py, int lane)
+{
+    const int words = fft::row_bits_words(py);
+    for (int w0 = 0; w0 < words; w0 += 2) {
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(fft::row_bits_padded_bit(data, 32 * w0 + lane, ny, ky, py));
+        if (lane < 2 && w0 + lane < words) rec[w0 + lane] = (unsigned int)(m >> (32 * lane));
+    }
 }
 #endif
 

@@ -32,11 +32,12 @@ constexpr int UF = 8;
 // Dynamic LDS of both kernels, G batches per transform round (the role-split kernel: G = 1):
 // [2][G * U][M + 1] round buffers, [M] plan twiddles, [M + 1] post-processing twiddles (each rounded up to 2 float2: the
 // geometry table behind them is 16-byte aligned), the geometry and class tables of a chunk (rotate_dev.h), the row masks
-// [2][G][16 waves] (bit u set = the wave's 64 columns of row u of that batch hold a non-zero value), the plane flag's word
+// [2][G][16 waves] (bit u set = the wave's 64 columns of row u of that batch hold a non-zero value), the plane flag's word (of 4),
+// the plane's Ny data bits of the row-bit record (row_bits.h: ROW_BITS_MAX_WORDS words, bit y = row y was stored)
 constexpr size_t rot_fftx_lds_bytes(int M, int G)
 {
     return (size_t)(2 * G * UF * (M + 1) + M + (M & 1) + (M + 1) + ((M + 1) & 1)) * sizeof(float2) + (size_t)geo_chunk_f(G) * sizeof(RowGeo) +
-           (size_t)(geo_chunk_f(G) / UF) * sizeof(int) + (size_t)(2 * G * 16 + 4) * sizeof(unsigned int);
+           (size_t)(geo_chunk_f(G) / UF) * sizeof(int) + (size_t)(2 * G * 16 + 4 + ROW_BITS_MAX_WORDS) * sizeof(unsigned int);
 }
 
 // Plane order.  Consecutive block ids go to different XCDs (round-robin dispatch, for speed only) and planes z, z + 1 read
@@ -225,14 +226,17 @@ __device__ __forceinline__ void rot_post_store(const float2* wbuf, const float2*
 // Row y of the plane, owned by the calling wave: transform, post-process to the half spectrum, store.  A row without a single
 // non-zero voxel (everything outside the specimen: well over half the rows of a sphere phantom) has the zero spectrum: no
 // transform, sixteen-byte zero stores.  Exact, not an approximation.
+// With the row-bit record (p.rowbits; `dbits`: the block's data bits in LDS) a stored row sets its bit and a zero row stores NOTHING:
+// pass B reads the bits instead of the zeros.
 template <class PLAN>
 __device__ __forceinline__ void spectrum_row_store(const RotFftArgs& p, int zl, int y, bool nonzero, float2* wbuf, const float2* tw,
-                                                   const float2* twx_l, int lane)
+                                                   const float2* twx_l, int lane, unsigned int* dbits)
 {
     if (nonzero) {
         PLAN::template run<1>(wbuf, tw, lane);
         rot_post_store<PLAN::len>(wbuf, twx_l, spectrum_row(p, zl, y), p.hxp, lane);
-    } else {
+        if (p.rowbits && lane == 0) atomicOr(dbits + (y >> 5), 1u << (y & 31));
+    } else if (!p.rowbits) {
         float4* __restrict__ drow = reinterpret_cast<float4*>(spectrum_row(p, zl, y));
         for (int i = lane; i < p.hxp / 2; i += 64) drow[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
@@ -252,11 +256,13 @@ __global__ __launch_bounds__(1024) void k_rotate_attenuate_fftx(RotFftArgs p)
     RowGeo* geo = reinterpret_cast<RowGeo*>(twx_l + (M + 1) + ((M + 1) & 1));
     int* bclass = reinterpret_cast<int*>(geo + GEO_CHUNK_F);
     unsigned int* wmask = reinterpret_cast<unsigned int*>(bclass + GEO_CHUNK_F / U);
+    unsigned int* dbits = wmask + 2 * G * 16 + 4;                 // the rows of the plane that were stored, bit y
     const int ny = p.ny, steps = p.steps;
     const int x = threadIdx.x;
     const int lane = x & 63, wave = __builtin_amdgcn_readfirstlane(x >> 6), nwaves = (int)blockDim.x >> 6;
     const int zl = rot_fftx_plane();
     if (zl >= p.nzl) return;                                      // whole block: uniform
+    if (x < ROW_BITS_MAX_WORDS) dbits[x] = 0u;                    // (in front of the chunk loop's first barrier)
     const double l2 = (double)(p.z_first + zl);
     const WalkLane L = walk_lane(p, x, zl, 2 * M);
     const char* __restrict__ in_b = reinterpret_cast<const char*>(p.in);
@@ -286,7 +292,7 @@ __global__ __launch_bounds__(1024) void k_rotate_attenuate_fftx(RotFftArgs p)
                 any = 0u;
 #endif
                 spectrum_row_store<PLAN>(p, zl, ysub[sub] - u, (__builtin_amdgcn_readfirstlane(any) >> u) & 1u,
-                                         rowbuf + (((size_t)buf * G + sub) * U + u) * LP, tw, twx_l, lane);
+                                         rowbuf + (((size_t)buf * G + sub) * U + u) * LP, tw, twx_l, lane, dbits);
             }
         }
         buf ^= 1;
@@ -313,7 +319,7 @@ __global__ __launch_bounds__(1024) void k_rotate_attenuate_fftx(RotFftArgs p)
             const int nrows = min(U, cnt - r0);
             if (cls == 0) {
                 if (WRITE_OUT) store_zero_batch<U>(p, L, y0);
-                for (int j = wave; j < U; j += nwaves) spectrum_row_store<PLAN>(p, zl, y0 - j, false, nullptr, tw, twx_l, lane);   // zero rows, zero spectra
+                for (int j = wave; j < U; j += nwaves) spectrum_row_store<PLAN>(p, zl, y0 - j, false, nullptr, tw, twx_l, lane, dbits);   // zero rows, zero spectra
                 continue;
             }
             float val[U];
@@ -341,12 +347,18 @@ __global__ __launch_bounds__(1024) void k_rotate_attenuate_fftx(RotFftArgs p)
         }
         if (fill > 0) flush_round();                              // before the geometry table (and with it nothing the round needs) moves on
     }
+    // The row-bit record: every stored row's bit is in LDS once the block has met -- at an LDS-only barrier that every wave reaches
+    // whatever its plane holds (p.rowbits is a kernel argument); one wave expands the Ny bits and stores the record
+    if (p.rowbits) {
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if (wave == 0) write_row_bits(dbits, p.rowbits + (long long)zl * row_bits_words(p.py), ny, p.ky, p.py, lane);
+    }
     // Planes that stay empty (a specimen in empty space: a third of the planes of the sphere phantom) need no convolution passes at
     // all: their spectrum is exactly zero.  The passes skip what these flags call empty (custom_fft_convolve_slab, ConvTail::plane_nz).
     if (p.plane_nz) write_plane_flag(wmask + 2 * G * 16, plane_any, x, lane, p.plane_nz + zl);
     for (int yy = ny - 1 - steps; yy >= 0; --yy) {
         store_unvisited_row<WRITE_OUT>(p, L, yy, l2);
-        if ((ny - 1 - steps - yy) % nwaves == wave) spectrum_row_store<PLAN>(p, zl, yy, false, nullptr, tw, twx_l, lane);
+        if ((ny - 1 - steps - yy) % nwaves == wave) spectrum_row_store<PLAN>(p, zl, yy, false, nullptr, tw, twx_l, lane, dbits);
     }
 }
 
@@ -384,6 +396,7 @@ __global__ __launch_bounds__((8 + T) * 64, (8 + T) / 2) void k_rotate_attenuate_
     RowGeo* geo = reinterpret_cast<RowGeo*>(twx_l + (M + 1) + ((M + 1) & 1));
     int* bclass = reinterpret_cast<int*>(geo + GEO_CHUNK_F);
     unsigned int* wmask = reinterpret_cast<unsigned int*>(bclass + GEO_CHUNK_F / U);
+    unsigned int* dbits = wmask + 2 * 16 + 4;                     // the rows of the plane that were stored, bit y
     const int ny = p.ny, steps = p.steps;
     const int x = threadIdx.x;
     const int lane = x & 63, wave = __builtin_amdgcn_readfirstlane(x >> 6);
@@ -392,6 +405,7 @@ __global__ __launch_bounds__((8 + T) * 64, (8 + T) / 2) void k_rotate_attenuate_
     const int tr = wave - nwalk;                                  // which transformer (walkers: negative)
     const int zl = rot_fftx_plane();
     if (zl >= p.nzl) return;                                      // whole block: uniform
+    if (x < ROW_BITS_MAX_WORDS) dbits[x] = 0u;                    // (in front of the barriers around the table fill)
     const double l2 = (double)(p.z_first + zl);
     const WalkLane L = walk_lane(p, x, zl, 2 * M);                // (transformer lanes: x >= 64 nwalk >= nx, never active)
     const char* __restrict__ in_b = reinterpret_cast<const char*>(p.in);
@@ -421,7 +435,7 @@ __global__ __launch_bounds__((8 + T) * 64, (8 + T) / 2) void k_rotate_attenuate_
         while (rot_rounds_next(rounds, cls_of, b)) {
             const int y0 = ny - 1 - b.r0;
             if (b.cls == 0) {
-                for (int j = tr; j < U; j += T) spectrum_row_store<PLAN>(p, zl, y0 - j, false, nullptr, tw, twx_l, lane);
+                for (int j = tr; j < U; j += T) spectrum_row_store<PLAN>(p, zl, y0 - j, false, nullptr, tw, twx_l, lane, dbits);
                 continue;
             }
             round_barrier();                                  // round b.buf is complete
@@ -434,7 +448,7 @@ __global__ __launch_bounds__((8 + T) * 64, (8 + T) / 2) void k_rotate_attenuate_
             // this wave's RW adjacent rows
 #pragma unroll 1
             for (int u = tr * RW; u < (tr + 1) * RW && u < b.nrows; ++u)
-                spectrum_row_store<PLAN>(p, zl, y0 - u, (any >> u) & 1u, rowbuf + ((size_t)b.buf * U + u) * LP, tw, twx_l, lane);
+                spectrum_row_store<PLAN>(p, zl, y0 - u, (any >> u) & 1u, rowbuf + ((size_t)b.buf * U + u) * LP, tw, twx_l, lane, dbits);
         }
     } else {
         // ------------------------------------------------------------------ walker: one batch, one round buffer, one barrier
@@ -469,11 +483,19 @@ __global__ __launch_bounds__((8 + T) * 64, (8 + T) / 2) void k_rotate_attenuate_
             round_barrier();                                  // hands buffer b.buf to the transformers
         }
     }
+    // The row-bit record: the transformers have ORed the bits of the rows they stored into LDS.  The block meets ONCE MORE, at an
+    // LDS-only barrier outside the enumeration of rot_rounds_next, which every wave of both roles reaches whatever its plane holds
+    // (p.rowbits is a kernel argument: the number of barriers stays a function of block-uniform data only); one wave expands the Ny
+    // bits and stores the record
+    if (p.rowbits) {
+        round_barrier();
+        if (wave == 0) write_row_bits(dbits, p.rowbits + (long long)zl * row_bits_words(p.py), ny, p.ky, p.py, lane);
+    }
     if (p.plane_nz) write_plane_flag(wmask + 2 * 16, plane_any, x, lane, p.plane_nz + zl);   // the walkers know; every wave meets at the barriers
     // the rows the reference never visits: zero spectra are the transformers'
     for (int yy = ny - 1 - steps; yy >= 0; --yy) {
         store_unvisited_row<WRITE_OUT>(p, L, yy, l2);
-        if (!walker && (ny - 1 - steps - yy) % T == tr) spectrum_row_store<PLAN>(p, zl, yy, false, nullptr, tw, twx_l, lane);
+        if (!walker && (ny - 1 - steps - yy) % T == tr) spectrum_row_store<PLAN>(p, zl, yy, false, nullptr, tw, twx_l, lane, dbits);
     }
 }
 

@@ -68,13 +68,7 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 // with the zeros of the other path, pays for that with a register copy -- and a wait for the tile's FIRST row before the second is
 // requested (and again before the sum's weights): two extra trips to memory in a block that lives for 12 us.  A row that is not wanted
 // (padding, past the end, an empty plane -- nobody wrote it) reads the tile's column in the first plane instead (a cache hit) and is cleared
-// with this mask; an AND, not a select -- a select whose operand is a load is turned back into the branch.
-__device__ __forceinline__ float4 zconv_keep4(float4 t, bool keep)
-{
-    const unsigned int m = keep ? 0xFFFFFFFFu : 0u;
-    return make_float4(__uint_as_float(__float_as_uint(t.x) & m), __uint_as_float(__float_as_uint(t.y) & m),
-                       __uint_as_float(__float_as_uint(t.z) & m), __uint_as_float(__float_as_uint(t.w) & m));
-}
+// with the mask of keep4 (fft_host.h).
 
 constexpr int TNIT = 64 / ZRPI;                       // kzp <= 64 rows of taps
 
@@ -165,13 +159,13 @@ __global__ __launch_bounds__(ZT, ZBLOCKS_PER_CU) void k_zconv(ZConvArgs p)
         int z = p.z_out0 + zc0 + (r - padf) - hl;
         if ((unsigned)z >= (unsigned)p.nz_global) z = mirror_index(z, p.nz_global);
         const long long zo = want ? (long long)(z - p.z_in0) * p.zs : 0ll;
-        v[it] = zconv_keep4(*reinterpret_cast<const float4*>(p.src + zo + scol + c2), want);
+        v[it] = keep4(*reinterpret_cast<const float4*>(p.src + zo + scol + c2), want);
     }
 #pragma unroll
     for (int it = 0; it < TNIT; ++it) {
         const int r = (tid / ZLPR) + it * ZRPI;
         const bool want = r < p.kz;
-        tv[it] = zconv_keep4(*reinterpret_cast<const float4*>(p.taps + (long long)(want ? r : 0) * p.zs + tcol + c2), want);
+        tv[it] = keep4(*reinterpret_cast<const float4*>(p.taps + (long long)(want ? r : 0) * p.zs + tcol + c2), want);
     }
     // the sum's weights travel with the tile (requested in the epilogue they cost a block 1-4 k cycles of exposed latency: clock stamps)
     double2 wxa = make_double2(0.0, 0.0), wyb = make_double2(0.0, 0.0);
@@ -359,13 +353,13 @@ __global__ __launch_bounds__(ZT, ZBLOCKS_PER_CU) void k_zconv_strided(ZConvArgs 
         int z = p.z_out0 + zc0 + (r - padf) - hl;
         if ((unsigned)z >= (unsigned)p.nz_global) z = mirror_index(z, p.nz_global);
         const long long zo = want ? (long long)(z - p.z_in0) * p.zs : 0ll;
-        v[it] = zconv_keep4(*reinterpret_cast<const float4*>(p.src + zo + scol + c2), want);
+        v[it] = keep4(*reinterpret_cast<const float4*>(p.src + zo + scol + c2), want);
     }
 #pragma unroll
     for (int it = 0; it < TNIT; ++it) {
         const int r = (tid / ZLPR) + it * ZRPI;
         const bool want = r < p.kz;
-        tv[it] = zconv_keep4(*reinterpret_cast<const float4*>(p.taps + (long long)(want ? r : 0) * p.zs + tcol + c2), want);
+        tv[it] = keep4(*reinterpret_cast<const float4*>(p.taps + (long long)(want ? r : 0) * p.zs + tcol + c2), want);
     }
     // the sum's weights travel with the tile (requested in the epilogue they cost a block 1-4 k cycles of exposed latency: clock stamps)
     double2 wxa = make_double2(0.0, 0.0), wyb = make_double2(0.0, 0.0);
