@@ -803,6 +803,114 @@ int mvsim_fuse_views(mvsim_ctx* ctx, const mvsim_fuse_view* views, int n_views, 
 int mvsim_align_views(mvsim_ctx* ctx, const mvsim_fuse_view* views, int n_views, const int64_t out_min[3], const int64_t out_dim[3],
                       const mvsim_fuse_params* params, float* const* aligned, float* const* weights_or_null, int32_t* status_or_null);
 
+/* ---- PSF extraction: the beads of one view averaged into that view's PSF, in the output frame ------------------------------------
+ * The link between mvsim_detect_beads / mvsim_register_beads and mvsim_deconvolve: a device-resident view, its detection list and
+ * (optionally) its registration matrix go in, one normalised PSF volume comes out, already in the frame the matrix maps to, so that
+ * mvsim_deconvolve_dev takes it as it is.  The reference has no counterpart; the recipe is this one, and every arithmetic step is stated
+ * so that a literal restatement reproduces the result bit for bit.
+ * Volumes are x fastest with dim = {Nx, Ny, Nz}; the source is float, or uint16_t widened with one (float)v on load.  A point list is
+ * as in the registration: 3 doubles at a byte stride >= 24 that is a multiple of 8, n = min(max(*n_dev, 0), capacity) read from DEVICE
+ * memory by the kernels, capacity <= MVSIM_PSF_MAX_POINTS.  All arithmetic is fp64 unless it says float, every + - * / an operation of
+ * its own (no fused multiply-add), every sum and product evaluated as parenthesised.
+ * 1. Inverse.  The forward matrix m = [A | t] (3 x 4 row-major, view -> output frame; NULL: the identity matrix, taken through the
+ *    same arithmetic) is given on the host or as 12 doubles in device memory.  Only A is used: the nine i_rc are those of step 1 of
+ *    the fusion applied to [A | 0].  If an entry of A is non-finite, or det is zero or non-finite: the flag is MVSIM_PSF_SINGULAR,
+ *    n_listed = n, every other count, minimum and sum are 0, the PSF is all +0.0f, the status bytes are not written, nothing else runs.
+ * 2. Offsets.  The PSF has odd extents kdim_d, 1 <= kdim_d <= MVSIM_PSF_MAX_DIM, centre c_d = kdim_d / 2.  For tap k:
+ *        j_d = (double)(k_d - c_d),   delta_r = ((i_r2 * j_z) + i_r1 * j_y) + i_r0 * j_x
+ *    and the sample position of tap k for a bead at pos is p_r = pos_r + delta_r: with the identity, pos + j exactly.
+ * 3. Selection.  Every listed bead i < n gets one status byte, the first rule that applies:
+ *      MVSIM_PSF_NONFINITE  a coordinate is not finite
+ *      MVSIM_PSF_MASKED     a use-mask is given and use[i] == 0
+ *      MVSIM_PSF_OUTSIDE    one of the eight corner taps (k_d in {0, kdim_d - 1}) has a p_d that fails
+ *                           0.0 <= p_d && p_d <= (double)(N_d - 1)
+ *      MVSIM_PSF_CROWDED    min_separation is not all zero and another finite listed point j != i, masked or not, has
+ *                           fabs(pos_j,d - pos_i,d) < min_separation_d on all three axes (strict: an exact duplicate crowds both)
+ *      MVSIM_PSF_USED       otherwise
+ * 4. Sample, for a used bead and any tap: q_d = p_d > 0.0 ? p_d : 0.0, then q_d = q_d < (double)(N_d - 1) ? q_d : (double)(N_d - 1)
+ *    (between inside corners a tap leaves the box only by rounding), then step 4 of the fusion on q verbatim: floor, u, lo,
+ *    hi = min(lo + 1, N - 1), along x, then y, then z, rounded to float once: s_f.
+ * 5. Sum per tap over the used beads, as step 4 of the registration takes its sums: chunks of MVSIM_PSF_CHUNK (256) consecutive list
+ *    indices, unused beads skipped; a chunk's sum starts from +0.0 and adds (double)s_f ascending, the total starts from +0.0 and adds
+ *    the sums of the ceil(n / 256) chunks ascending.
+ * 6. Finish.  Taps are indexed t = k_x + kdim_x * (k_y + kdim_y * k_z).  mean_t = total_t / (double)n_used.  b = +inf, then ascending
+ *    t: if mean_t < b then b = mean_t (a NaN is never smaller).  v_t = mean_t - b with subtract_min, else v_t = mean_t.  S is the sum
+ *    of v_t, chunked by 256 consecutive tap indices exactly as in step 5.  With normalize and S > 0.0 and S finite:
+ *    psf_t = (float)(v_t / S); otherwise psf_t = (float)v_t, and MVSIM_PSF_FLAT is set when normalize was asked for.
+ *    n_used == 0: the flag is MVSIM_PSF_NO_BEADS, the PSF is all +0.0f, minimum and sum are 0.
+ * The workspace of a call is ceil(capacity / 256) * prod(kdim) doubles of per-chunk partial sums, prod(kdim) doubles of totals and
+ * capacity status bytes, in the context (mvsim_release_caches frees them). */
+#define MVSIM_PSF_MAX_POINTS MVSIM_REG_MAX_POINTS
+#define MVSIM_PSF_MAX_DIM    63
+#define MVSIM_PSF_CHUNK      256
+#define MVSIM_PSF_USED       0
+#define MVSIM_PSF_NONFINITE  1
+#define MVSIM_PSF_MASKED     2
+#define MVSIM_PSF_OUTSIDE    3
+#define MVSIM_PSF_CROWDED    4
+#define MVSIM_PSF_SINGULAR   1
+#define MVSIM_PSF_NO_BEADS   2
+#define MVSIM_PSF_FLAT       4
+typedef struct mvsim_psf_params {
+    int64_t kdim[3];           /* default 15, 15, 15; odd, 1 .. MVSIM_PSF_MAX_DIM */
+    double  min_separation[3]; /* default 15, 15, 15 voxels; >= 0 and finite; all zero: no crowding rule */
+    int32_t src_type;          /* default MVSIM_SRC_F32 */
+    int32_t subtract_min;      /* default 1 */
+    int32_t normalize;         /* default 1 */
+    int32_t pad;
+} mvsim_psf_params;            /* 64 bytes */
+typedef struct mvsim_psf_result {
+    double  minimum, sum;      /* b and S of step 6 */
+    int64_t n_listed, n_used, n_nonfinite, n_masked, n_outside, n_crowded;
+    int32_t flags, pad;        /* MVSIM_PSF_SINGULAR | NO_BEADS | FLAT */
+} mvsim_psf_result;            /* 72 bytes */
+void mvsim_psf_params_default(mvsim_psf_params* p);
+/* Host only, no context: steps 1 and 2.  offsets receives 3 doubles (delta_x, delta_y, delta_z) per tap, taps indexed as in step 6;
+ * *singular = 1 leaves offsets untouched.  m_or_null: 12 doubles. */
+int mvsim_psf_offsets(const double* m_or_null, const int64_t kdim[3], double* offsets, int* singular);
+/* Host only: steps 1 and 3 over a host list of n >= 0 points.  status receives n bytes; result the counts, flags 0 or
+ * MVSIM_PSF_SINGULAR, minimum = sum = 0.  Of params, kdim and min_separation are used. */
+int mvsim_psf_select(const void* pos, int64_t stride, int64_t n, const unsigned char* use_or_null, const double* m_or_null,
+                     const int64_t dim[3], const mvsim_psf_params* params, unsigned char* status, mvsim_psf_result* result);
+/* Host only: step 6 over prod(kdim) host totals.  result goes in as the selection left it (n_used and flags are read) and comes out
+ * complete; psf receives prod(kdim) floats. */
+int mvsim_psf_finish(const double* totals, const mvsim_psf_params* params, float* psf, mvsim_psf_result* result);
+/* Host only: {MVSIM_PSF_CHUNK, taps per block of the gather kernel, beads staged per tile of the crowding kernel, most blocks a
+ * launch has}. */
+int mvsim_psf_geometry(int64_t out[4]);
+/* The stages on their own, asynchronous on the context's stream.  Selection: status_dev receives capacity bytes (n of them written),
+ * result_dev one record as mvsim_psf_select leaves it.  m_or_null (host) and m_dev_or_null (DEVICE, e.g. &result_dev->m[0] of a
+ * registration) exclude each other. */
+int mvsim_psf_select_dev(mvsim_ctx* ctx, const void* pos_dev, int64_t stride, const int64_t* n_dev, int64_t capacity,
+                         const unsigned char* use_dev_or_null, const double* m_or_null, const double* m_dev_or_null, const int64_t dim[3],
+                         const mvsim_psf_params* params, unsigned char* status_dev, mvsim_psf_result* result_dev);
+/* Steps 4 and 5 for the beads whose status byte is 0: totals_dev receives prod(kdim) doubles (all +0.0 when the matrix is singular,
+ * and then the status bytes are not read). */
+int mvsim_psf_gather_dev(mvsim_ctx* ctx, const void* img_dev, const int64_t dim[3], const void* pos_dev, int64_t stride,
+                         const int64_t* n_dev, int64_t capacity, const unsigned char* status_dev, const double* m_or_null,
+                         const double* m_dev_or_null, const mvsim_psf_params* params, double* totals_dev);
+/* Step 6: result_dev goes in as the selection left it and comes out complete; psf_dev receives prod(kdim) floats. */
+int mvsim_psf_finish_dev(mvsim_ctx* ctx, const double* totals_dev, const mvsim_psf_params* params, float* psf_dev,
+                         mvsim_psf_result* result_dev);
+/* The inliers of a registration as a use-mask: use_dev (n_points_capacity bytes) is zeroed, then byte a (side 0) or byte b (side 1)
+ * of every candidate i < min(max(*n_candidates_dev, 0), capacity) whose mask byte is 1 -- of every candidate with a NULL mask -- is
+ * set to 1; an index outside [0, n_points_capacity) is ignored. */
+int mvsim_psf_use_from_matches_dev(mvsim_ctx* ctx, const mvsim_match* candidates_dev, const int64_t* n_candidates_dev, int64_t capacity,
+                                   const unsigned char* mask_dev_or_null, int side, int64_t n_points_capacity, unsigned char* use_dev);
+/* The whole recipe.  psf_dev: prod(kdim) floats; result_dev: one record; status_dev_or_null: capacity bytes.  Asynchronous on the
+ * context's stream, nothing is read back.
+ * MVSIM_EINVAL, before the context is touched: a null pointer where one is required, an extent < 1, a kdim entry even, < 1 or above
+ * MVSIM_PSF_MAX_DIM, a stride below 24 or no multiple of 8, a capacity <= 0 or above MVSIM_PSF_MAX_POINTS, a min_separation that is
+ * negative or not finite, an unknown src_type, both m and m_dev given, a psf_dev that overlaps the image. */
+int mvsim_extract_psf_dev(mvsim_ctx* ctx, const void* img_dev, const int64_t dim[3], const void* pos_dev, int64_t stride,
+                          const int64_t* n_dev, int64_t capacity, const unsigned char* use_dev_or_null, const double* m_or_null,
+                          const double* m_dev_or_null, const mvsim_psf_params* params, float* psf_dev, mvsim_psf_result* result_dev,
+                          unsigned char* status_dev_or_null);
+/* The same with HOST buffers and a host matrix; synchronous.  n >= 0 points, at most MVSIM_PSF_MAX_POINTS; status_or_null: n bytes. */
+int mvsim_extract_psf(mvsim_ctx* ctx, const void* img, const int64_t dim[3], const void* pos, int64_t stride, int64_t n,
+                      const unsigned char* use_or_null, const double* m_or_null, const mvsim_psf_params* params, float* psf,
+                      mvsim_psf_result* result, unsigned char* status_or_null);
+
 /* ---- extractSlices over Intervals of volumes that stay on the device (SimulateTileStitching.java:131-189) ---------------
  * Views.zeroMin(Views.interval(con, min, max)) run through extractSlices: output voxel (x, y, k) of the contiguous tile
  * tx x ty x mvsim_extract_nz(tz, inc), t_d = max_d - min_d + 1, is f(in[(min_x + x) + Nx ((min_y + y) + Ny (min_z + k inc))]).

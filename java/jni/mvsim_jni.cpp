@@ -1018,6 +1018,65 @@ JNIEXPORT void JNICALL JNI_FN(alignViews)(JNIEnv* env, jclass, jlong h, jobjectA
     throw_for(env, mvsim_align_views(ctx_of(h), a.v, static_cast<int>(a.n), a.out_min, a.out_dim, &a.p, al, weights ? wt : nullptr, a.status));
 }
 
+// ---- PSF extraction (mvsim_extract_psf) ---------------------------------------------------------------------------------------------
+// The PSF of one view from its beads.  img: a direct Float- or (u16) ShortBuffer of prod(dim) voxels; pos: a direct DoubleBuffer of 3 n
+// doubles; use (or null): a direct ByteBuffer of n bytes; m12 (or null: the identity): a direct DoubleBuffer of 12 doubles, view -> output
+// frame; psf: a direct FloatBuffer of prod(kdim) floats; result: a direct ByteBuffer of at least 72 bytes that receives one
+// mvsim_psf_result {double minimum, sum; long nListed, nUsed, nNonfinite, nMasked, nOutside, nCrowded; int flags, pad} in native byte
+// order; status (or null): a direct ByteBuffer of max(n, 1) bytes.  Returns the number of beads used.  Every length, null and capacity is
+// checked before the C ABI sees a pointer.
+JNIEXPORT jlong JNICALL JNI_FN(extractPsf)(JNIEnv* env, jclass, jlong h, jobject img, jboolean u16, jlongArray dim, jobject pos, jlong n,
+                                           jobject use, jobject m12, jlongArray kdim, jdouble sep_x, jdouble sep_y, jdouble sep_z,
+                                           jboolean subtract_min, jboolean normalize, jobject psf, jobject result, jobject status)
+{
+    const char* iae = "java/lang/IllegalArgumentException";
+    if (n < 0 || n > MVSIM_PSF_MAX_POINTS) { throw_new(env, iae, "extractPsf: the list length must be in 0 .. 65536"); return 0; }
+    Dim d(env, dim);
+    if (!d.ok) return 0;
+    Dim k(env, kdim);
+    if (!k.ok) return 0;
+    for (int a = 0; a < 3; ++a) {
+        if (d.d[a] > 0x7fffffff) { throw_new(env, iae, "extractPsf: image extents must be in 1 .. 2^31-1"); return 0; }
+        if (k.d[a] > MVSIM_PSF_MAX_DIM || (k.d[a] & 1) == 0) { throw_new(env, iae, "extractPsf: PSF extents must be odd and in 1 .. 63"); return 0; }
+    }
+    const void* src = any_ptr(env, img, d.n(), "extractPsf: image buffer missing or smaller than its dimensions");
+    if (!src) return 0;
+    const void* p = any_ptr(env, pos, 3 * n, "extractPsf: position buffer missing or smaller than 3 n doubles");
+    if (!p) return 0;
+    const void* u = nullptr;
+    if (use) {
+        u = any_ptr(env, use, n, "extractPsf: use buffer smaller than n bytes");
+        if (!u) return 0;
+    }
+    const void* m = nullptr;
+    if (m12) {
+        m = any_ptr(env, m12, 12, "extractPsf: matrix buffer smaller than 12 doubles");
+        if (!m) return 0;
+    }
+    float* out = fptr(env, psf, k.n(), "extractPsf: PSF buffer missing or smaller than its dimensions");
+    if (!out) return 0;
+    void* res = any_ptr(env, result, static_cast<jlong>(sizeof(mvsim_psf_result)), "extractPsf: result buffer missing or smaller than 72 bytes");
+    if (!res) return 0;
+    void* st = nullptr;
+    if (status) {
+        st = any_ptr(env, status, n > 0 ? n : 1, "extractPsf: status buffer smaller than max(n, 1) bytes");
+        if (!st) return 0;
+    }
+    mvsim_psf_params q;
+    mvsim_psf_params_default(&q);
+    for (int a = 0; a < 3; ++a) q.kdim[a] = k.d[a];
+    q.min_separation[0] = sep_x; q.min_separation[1] = sep_y; q.min_separation[2] = sep_z;
+    q.src_type = u16 ? MVSIM_SRC_U16 : MVSIM_SRC_F32;
+    q.subtract_min = subtract_min ? 1 : 0;
+    q.normalize = normalize ? 1 : 0;
+    mvsim_psf_result r;
+    const int rc = mvsim_extract_psf(ctx_of(h), src, d.d, p, 24, n, static_cast<const unsigned char*>(u), static_cast<const double*>(m), &q, out, &r,
+                                     static_cast<unsigned char*>(st));
+    if (rc != MVSIM_OK) { throw_for(env, rc); return 0; }
+    std::memcpy(res, &r, sizeof(r));
+    return static_cast<jlong>(r.n_used);
+}
+
 // ---- mvsim_group_* -------------------------------------------------------------------------------------------------
 JNIEXPORT jlong JNICALL JNI_FN(groupCreate)(JNIEnv* env, jclass, jint ndev)
 {

@@ -153,6 +153,16 @@ final class MvsimNative
 			long[] outDim, double blendX, double blendY, double blendZ, FloatBuffer[] aligned, FloatBuffer[] weights,
 			java.nio.IntBuffer status );
 
+	/**
+	 * mvsim_extract_psf: the PSF of one view from its beads (include/mvsim.h states the recipe).  img: a direct Float- or (u16)
+	 * ShortBuffer of prod(dim) voxels; pos: 3 n doubles; use (or null): n bytes; m12 (or null: the identity): 12 doubles, view to
+	 * output frame; psf: prod(kdim) floats; result: at least 72 bytes for one mvsim_psf_result in native byte order; status (or
+	 * null): max(n, 1) bytes.  Returns the number of beads used.
+	 */
+	static native long extractPsf( long ctx, java.nio.Buffer img, boolean u16, long[] dim, java.nio.DoubleBuffer pos, long n,
+			java.nio.ByteBuffer use, java.nio.DoubleBuffer m12, long[] kdim, double sepX, double sepY, double sepZ, boolean subtractMin,
+			boolean normalize, FloatBuffer psf, java.nio.ByteBuffer result, java.nio.ByteBuffer status );
+
 	/** Fused loop body of SimulateMultiViewDataset.main (:570-585); rot/att/con may be null (then they never leave HBM). */
 	static native double simulateView( long ctx, FloatBuffer gt, long[] dim, FloatBuffer psf, long[] kdim,
 			int axis, int degrees, double delta, float minValue, float targetAverage, int inc, float snr, long seed, int stream,

@@ -33,12 +33,15 @@ from .registration import BeadRegistration, ContextRegistration, descriptor_subs
 from ._lib import FuseParams, FuseView  # noqa: F401
 from .fusion import (ContextFusion, ViewFusion, fuse_invert, fuse_params, fusion_bounds, fusion_geometry, psf_matrix,  # noqa: F401
                      transform_psf)
+from ._lib import PsfParams, PsfResult  # noqa: F401
+from .psf import (ContextPsf, PsfExtraction, gaussian_psf, psf_finish, psf_geometry, psf_offsets, psf_params, psf_rendered,  # noqa: F401
+                  psf_select)
 from .phantoms import ContextPhantoms
 
 __all__ = ["AffineTransform3D", "BeadRegistration", "Context", "DeconParams", "DifferenceOfGaussian", "DogParams", "MatchParams", "MultiViewDeconvolution", "Group", "Hessian", "HypersphereCollectionRealRandomAccessible", "JavaRandom", "Lightsheet",
            "PerlinNoiseRealRandomAccessible", "PointRejectionSampling", "RayTracingTest", "Raytrace", "RefractiveIndexMap", "ClearingMap", "SimpleCalculatedRealRandomAccessible", "SimulateBeads",
            "SimulateBeads2", "SimulateMultiViewAberrations", "SimulateMultiViewDataset", "Tools", "VolumeInjection", "broadcast_plan", "default_context", "MvsimError", "MvsimNoDeviceError", "ViewParams", "shard_views",
-           "version", "ViewFusion", "FuseParams"]
+           "version", "ViewFusion", "FuseParams", "PsfExtraction", "PsfParams"]
 
 
 def broadcast_plan(nranks: int, rank: int, root: int, count: int, pieces: int = 8):
@@ -154,7 +157,7 @@ def _ptr(a: np.ndarray) -> C.c_void_p:
     return C.c_void_p(a.ctypes.data)
 
 
-class Context(ContextAberrations, ContextPhantoms, ContextDeconvolution, ContextDetection, ContextRegistration, ContextFusion):
+class Context(ContextAberrations, ContextPhantoms, ContextDeconvolution, ContextDetection, ContextRegistration, ContextFusion, ContextPsf):
     """One ``mvsim_ctx``: bound to one GPU, not thread-safe.  (The refraction simulator's entry points -- refract3d,
     project_to_camera, hessian_at, volume_inject, ... -- are in aberrations.ContextAberrations, the procedural phantom's --
     perlin_at, spheres_raster, rejection_sample, ... -- in phantoms.ContextPhantoms, the multi-view deconvolution's --
@@ -162,7 +165,7 @@ class Context(ContextAberrations, ContextPhantoms, ContextDeconvolution, Context
     detect_beads, detect_beads_dev, dog_dev, find_peaks_dev, localise_peaks_dev -- in detection.ContextDetection, the bead
     registration's -- register_beads, register_beads_dev, knn_dev, bead_descriptors_dev, match_descriptors_dev, ransac_affine_dev -- in
     registration.ContextRegistration, the view fusion's -- fuse_views, fuse_views_dev, align_views, align_views_dev -- in
-    fusion.ContextFusion.)"""
+    fusion.ContextFusion, the PSF extraction's -- extract_psf, extract_psf_dev, psf_use_from_matches_dev -- in psf.ContextPsf.)"""
 
     def __init__(self, device: int | None = None):
         self._h = C.c_void_p()

@@ -140,7 +140,22 @@ class FuseView(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dim", C.c_int64 * 3), ("m_dev", C.c_void_p), ("m", C.c_double * 12)]
 
 
+class PsfParams(C.Structure):
+    """mvsim_psf_params: the settings of the PSF extraction (mvsim_psf_params_default fills them)."""
+    _fields_ = [("kdim", C.c_int64 * 3), ("min_separation", C.c_double * 3), ("src_type", C.c_int32), ("subtract_min", C.c_int32),
+                ("normalize", C.c_int32), ("pad", C.c_int32)]
+
+
+class PsfResult(C.Structure):
+    """mvsim_psf_result: what the PSF extraction reports beside the PSF."""
+    _fields_ = [("minimum", C.c_double), ("sum", C.c_double), ("n_listed", C.c_int64), ("n_used", C.c_int64), ("n_nonfinite", C.c_int64),
+                ("n_masked", C.c_int64), ("n_outside", C.c_int64), ("n_crowded", C.c_int64), ("flags", C.c_int32), ("pad", C.c_int32)]
+
+
 MVSIM_MAX_VIEWS = 32
+MVSIM_PSF_MAX_POINTS, MVSIM_PSF_MAX_DIM, MVSIM_PSF_CHUNK = 65536, 63, 256
+MVSIM_PSF_USED, MVSIM_PSF_NONFINITE, MVSIM_PSF_MASKED, MVSIM_PSF_OUTSIDE, MVSIM_PSF_CROWDED = 0, 1, 2, 3, 4
+MVSIM_PSF_SINGULAR, MVSIM_PSF_NO_BEADS, MVSIM_PSF_FLAT = 1, 2, 4
 MVSIM_FUSE_SINGULAR = 1
 MVSIM_REG_MAX_POINTS, MVSIM_REG_FIT_CHUNK = 65536, 256
 MVSIM_REG_FEW_CANDIDATES, MVSIM_REG_NO_MODEL, MVSIM_REG_CAPPED, MVSIM_REG_FEW_INLIERS = 1, 2, 4, 8
@@ -363,6 +378,17 @@ SIGNATURES = {
     "mvsim_align_views_dev": (C.c_int, [_vp, C.POINTER(FuseView), C.c_int, _i64p, _i64p, C.POINTER(FuseParams), C.POINTER(_vp), C.POINTER(_vp), _vp]),
     "mvsim_fuse_views": (C.c_int, [_vp, C.POINTER(FuseView), C.c_int, _i64p, _i64p, C.POINTER(FuseParams), _vp, _vp, _vp]),
     "mvsim_align_views": (C.c_int, [_vp, C.POINTER(FuseView), C.c_int, _i64p, _i64p, C.POINTER(FuseParams), C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    "mvsim_psf_params_default": (None, [C.POINTER(PsfParams)]),
+    "mvsim_psf_offsets": (C.c_int, [_vp, _i64p, _vp, C.POINTER(C.c_int)]),
+    "mvsim_psf_select": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp, _i64p, C.POINTER(PsfParams), _vp, C.POINTER(PsfResult)]),
+    "mvsim_psf_finish": (C.c_int, [_vp, C.POINTER(PsfParams), _vp, C.POINTER(PsfResult)]),
+    "mvsim_psf_geometry": (C.c_int, [_i64p]),
+    "mvsim_psf_select_dev": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, _i64p, C.POINTER(PsfParams), _vp, _vp]),
+    "mvsim_psf_gather_dev": (C.c_int, [_vp, _vp, _i64p, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, C.POINTER(PsfParams), _vp]),
+    "mvsim_psf_finish_dev": (C.c_int, [_vp, _vp, C.POINTER(PsfParams), _vp, _vp]),
+    "mvsim_psf_use_from_matches_dev": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_int, C.c_int64, _vp]),
+    "mvsim_extract_psf_dev": (C.c_int, [_vp, _vp, _i64p, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, C.POINTER(PsfParams), _vp, _vp, _vp]),
+    "mvsim_extract_psf": (C.c_int, [_vp, _vp, _i64p, _vp, C.c_int64, C.c_int64, _vp, _vp, C.POINTER(PsfParams), _vp, C.POINTER(PsfResult), _vp]),
 }
 
 _lib = None

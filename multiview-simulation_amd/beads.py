@@ -216,6 +216,14 @@ class SimulateBeads:
         return fuse_rendered(_ctx(), self.points, [m[v] for v in picked], self.intervalRender, self.sigma, reference, detector, matcher, u16,
                              params)
 
+    def extract_psf(self, view: int = 0, detector=None, u16: bool = False, params=None):
+        """Render view ``view``, detect its beads and extract its PSF in the view's own frame, all on the device.  Returns
+        (psf, record, analytic): ``analytic`` is the renderer's Gaussian under the same minimum subtraction and normalisation."""
+        from .psf import psf_rendered
+        if self.points is None:
+            self.points = self.randomPoints(self.numPoints, self.rangeSimulation, self.rnd)
+        return psf_rendered(_ctx(), self.points, self.intervalRender, self.sigma, self.matrices()[view], detector, u16, params)
+
     @staticmethod
     def randomPoints(numPoints: int, range_, rnd) -> np.ndarray:
         """:151-166 -- (numPoints, 3) doubles.  A JavaRandom is replayed natively and advanced; any other object with
@@ -380,6 +388,12 @@ class SimulateBeads2:
         from .fusion import fuse_rendered
         return fuse_rendered(_ctx(), self.points, [self.transform(*v).m for v in views], self.intervalRender, self.sigma, reference, detector,
                              matcher, u16, params)
+
+    def extract_psf(self, tp: int, angle: int, channel: int, tile: int, illumination: int, detector=None, u16: bool = False, params=None):
+        """The PSF of one view from its rendered and detected beads, on the device: (psf, record, analytic) as SimulateBeads.extract_psf."""
+        from .psf import psf_rendered
+        return psf_rendered(_ctx(), self.points, self.intervalRender, self.sigma, self.transform(tp, angle, channel, tile, illumination).m,
+                            detector, u16, params)
 
     def getImage(self, tp: int, angle: int, channel: int, tile: int, illumination: int) -> np.ndarray:
         """LegacySimulatedBeadsImgLoader2.getImage (:65-85): uint16, written by the kernel directly."""

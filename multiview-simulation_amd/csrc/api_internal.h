@@ -1,7 +1,7 @@
 // What the translation units of the C ABI share: api.cpp (context, options, memory, stage operators on device buffers, queries),
 // api_view.cpp (the per-view pipeline on device buffers), api_host.cpp (host-buffer entry points), api_sims.cpp (phantom, bead and
 // refraction-simulator wrappers), api_decon.cpp (the multi-view deconvolution), api_detect.cpp (the bead detector), api_register.cpp (the bead
-// registration), api_fuse.cpp (the view fusion).  Host orchestration only.
+// registration), api_fuse.cpp (the view fusion), api_psf.cpp (the PSF extraction).  Host orchestration only.
 #pragma once
 
 #include "common.h"

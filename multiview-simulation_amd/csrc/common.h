@@ -275,6 +275,7 @@ struct mvsim_ctx {
     mvsim::DevBuf detect_buf[6];            // bead detector (api_detect.cpp): the two half-blurred volumes, D, the peak list, block counts + offsets + ballots, scan temp
     mvsim::DevBuf register_buf[4];          // bead registration (api_register.cpp): the stages' lists of one whole call, split partials, per-point bests, RANSAC pairs + key + mask
     mvsim::DevBuf fuse_buf;                 // view fusion (api_fuse.cpp): the views' inverted matrices, sources and outputs of the current call
+    mvsim::DevBuf psfx_buf[3];              // PSF extraction (api_psf.cpp): per-chunk partial sums, per-tap totals, status bytes
     int64_t       weight_dim[3] = {0, 0, 0};
     mvsim::DevBuf host_gt, host_rot, host_att, host_con;   // device twins of the host-buffer simulate_view (grow-only)
     mvsim::DevBuf partials;                 // doubles: block partial sums + [sum, corr]
@@ -379,6 +380,7 @@ template <class F> inline void mvsim_ctx::each_workspace(F&& f)
     f(partials_e, WS_KEPT);
     for (mvsim::DevBuf& b : detect_buf) f(b, 0);
     for (mvsim::DevBuf& b : register_buf) f(b, 0);
+    for (mvsim::DevBuf& b : psfx_buf) f(b, 0);
     for (mvsim::DevBuf& b : beads_buf) f(b, WS_NO_EPOCH);
     for (mvsim::DevBuf& b : proc_buf) f(b, WS_NO_EPOCH);
     for (mvsim::DevBuf& b : walk_buf) f(b, WS_NO_EPOCH);
