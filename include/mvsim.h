@@ -1099,6 +1099,12 @@ int mvsim_fused_tail_geometry(mvsim_ctx* ctx, const int64_t dim[3], const int64_
  * read them), planes of the z pass's output that are empty (passes D and E skip them)}.  Read from a page-locked word the device
  * writes, without synchronising: call after the view has completed.  All zero when no view has carried flags yet. */
 int mvsim_get_plane_stats(mvsim_ctx* ctx, int64_t stats[3]);
+/* Whether the tail of the last view this context enqueued ran in sparse mode (option "skip_tail", default 1; exact): out = {1 if the
+ * convolution's last pass stored nothing into the planes of its output that are known to be empty and phase 1 of the Poisson sampler read
+ * nothing there, else 0; the plane stride of the flags the two shared (0 outside the mode)}.  The mode needs a flagged view (see
+ * mvsim_get_plane_stats), the convolved volume not requested, and a sampled view on the work queue; together with the third figure of
+ * mvsim_get_plane_stats it says how many planes were left out.  Recorded on the host when the work is enqueued. */
+int mvsim_get_tail_path(mvsim_ctx* ctx, int64_t out[2]);
 /* The work queue of the Poisson sampler (Tools.java:73-86 is one sample per voxel; here the voxels whose sample needs the divergent fp64
  * code wait in per-block segments for a second kernel): stats = {bytes of queue workspace the context holds, items one segment holds,
  * bright items (lambda >= 10) and inversion items (lambda < 10) the context's last sampled view queued -- the first view of a stacked

@@ -686,6 +686,12 @@ class Context(ContextAberrations, ContextPhantoms, ContextDeconvolution, Context
         _lib.check(self._L.mvsim_get_plane_stats(self._h, st))
         return int(st[0]), int(st[1]), int(st[2])
 
+    def tail_path(self):
+        """mvsim_get_tail_path: (1 if the last view's tail ran in sparse mode -- option skip_tail --, the flag stride)."""
+        st = (C.c_int64 * 2)()
+        _lib.check(self._L.mvsim_get_tail_path(self._h, st))
+        return int(st[0]), int(st[1])
+
     def queue_stats(self):
         """The Poisson work queue of the last sampled view: dict(bytes, segment_items, bright, inversion, refused, fullest_block) --
         mvsim_get_queue_stats."""

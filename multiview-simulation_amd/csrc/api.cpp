@@ -71,6 +71,7 @@ int parse_option(Options& o, const char* name, const char* value)
     }
     if (n == "skip_empty") return flag(&o.skip_empty);
     if (n == "skip_rows") return flag(&o.skip_rows);
+    if (n == "skip_tail") return flag(&o.skip_tail);
     if (n == "fft_pad") {
         long long a = 0, b = 0, c = 0;
         if (v == "auto" || v.empty()) { o.fft_pad[0] = o.fft_pad[1] = o.fft_pad[2] = 0; return MVSIM_OK; }
@@ -271,6 +272,15 @@ int extract_stage_plan(mvsim_ctx* ctx, const ExtractGeom& g, const ExtractOps& o
     return MVSIM_OK;
 }
 
+// Will the launch behind a view's convolution be one of the two queue samplers, whichever planes the convolution leaves?  (The caller's
+// half of the sparse tail's condition -- extract_plan.h: tail_queue_sampler -- from the sizes and the context's queue setting alone.)
+bool extract_stage_queued(mvsim_ctx* ctx, const int64_t dim[3], int inc, bool noise)
+{
+    QueueMode qm;
+    if (queue_mode_next(ctx, &qm) != MVSIM_OK) return false;
+    return tail_queue_sampler(dim, inc, noise, qm);
+}
+
 int extract_stage_run(mvsim_ctx* ctx, const ExtractPlan& pl, ExtractOps& ops)
 {
     if (ops.nviews == 0) ops.queue_ws = ops.noise ? ctx->pqueue.p : nullptr;
@@ -279,6 +289,7 @@ int extract_stage_run(mvsim_ctx* ctx, const ExtractPlan& pl, ExtractOps& ops)
     ev_end(ctx, ST_EXTRACT);
     const int64_t path[5] = {pl.kernel, pl.checked ? 1 : 0, pl.blocks, pl.segcap, ops.nviews > 0 ? ops.nviews : 1};
     std::memcpy(ctx->extract_path, path, sizeof(path));
+    ctx->tail_path[0] = ops.empty_flags ? 1 : 0; ctx->tail_path[1] = ops.empty_flags ? ops.empty_stride : 0;
     return MVSIM_OK;
 }
 
@@ -933,6 +944,13 @@ int mvsim_get_extract_path(mvsim_ctx* ctx, int64_t path[5])
 {
     MVSIM_CHECK_ARG(ctx != nullptr && path != nullptr, "null pointer");
     std::memcpy(path, ctx->extract_path, sizeof(ctx->extract_path));
+    return MVSIM_OK;
+}
+
+int mvsim_get_tail_path(mvsim_ctx* ctx, int64_t out[2])
+{
+    MVSIM_CHECK_ARG(ctx != nullptr && out != nullptr, "null pointer");
+    out[0] = ctx->tail_path[0]; out[1] = ctx->tail_path[1];
     return MVSIM_OK;
 }
 

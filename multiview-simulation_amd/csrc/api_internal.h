@@ -20,6 +20,8 @@ int set_device(mvsim_ctx* ctx, bool keep_tail = false);
 // where the plan is needed first: stacked views (the queue regions of their table; views_aligned16 = every view's buffers), view_enqueue.
 int extract_stage_plan(mvsim_ctx* ctx, const ExtractGeom& g, const ExtractOps& ops, ExtractPlan* pl, bool views_aligned16 = false);
 int extract_stage_run(mvsim_ctx* ctx, const ExtractPlan& pl, ExtractOps& ops);
+// known before the convolution is enqueued: the launch behind it will be one of the two queue samplers (extract_plan.h: tail_queue_sampler)
+bool extract_stage_queued(mvsim_ctx* ctx, const int64_t dim[3], int inc, bool noise);
 int extract_stage(mvsim_ctx* ctx, const ExtractGeom& g, ExtractOps& ops);
 // extractSlices over intervals of device volumes (api.cpp): the jobs checked against everything mvsim_extract_intervals* refuses but the
 // outputs (geoms: one per job), and the launches of checked jobs into DEVICE outputs, asynchronous on ctx->stream

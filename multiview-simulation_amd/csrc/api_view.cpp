@@ -92,6 +92,10 @@ static int view_enqueue(mvsim_ctx* ctx, const float* gt, const int64_t dim[3], c
     tail.x_done = x_done;
     tail.plane_nz = x_done ? plane_nz : nullptr;
     tail.row_bits = x_done ? row_bits : nullptr;
+    // the sparse tail, the caller's half (extract_plan.h): `con` is the context's workspace, which nothing but this view's sampler reads,
+    // and that sampler will be one of the two that take the flags -- settled here, on the host, before pass E is enqueued
+    tail.want_sparse = tail.plane_nz != nullptr &&
+                       tail_sparse_caller(ctx->opt.skip_tail, materialise, extract_stage_queued(ctx, dim, p->inc, noise));
     if (method == 1 && ctx->opt.fuse_tail && (!noise || ctx->opt.poisson_queue == 1)) {
         const size_t qb = noise ? fused_tail_queue_bytes(dim, kdim, p->inc, materialise, ctx->opt) : 0;
         if (!noise || qb > 0) {
@@ -107,8 +111,10 @@ static int view_enqueue(mvsim_ctx* ctx, const float* gt, const int64_t dim[3], c
     if (tail.fused) {                  // pass E adjusted, extracted and sampled (phase 1); the resolver is enqueued behind it
         const int64_t fused[5] = {EXTRACT_FUSED_TAIL, 0, tail.fused_blocks, noise ? (int64_t)tail.fused_segcap : 0, 1};
         std::memcpy(ctx->extract_path, fused, sizeof(fused));
+        ctx->tail_path[0] = ctx->tail_path[1] = 0;
         return MVSIM_OK;
     }
+    if (tail.sparse && (materialise || method != 1)) { set_error("sparse tail behind a view that did not ask for it"); return MVSIM_EINVAL; }
 
     ev_begin(ctx, ST_ADJUST);
     if (method == 2) MVSIM_TRY(launch_sum(ctx->stream, con, n, partial, scal));   // FFT path sums in its crop epilogue
@@ -121,6 +127,10 @@ static int view_enqueue(mvsim_ctx* ctx, const float* gt, const int64_t dim[3], c
     ops.in = con; ops.out = o->acq; ops.scal = scal;
     ops.min_value = p->min_value; ops.noise = noise; ops.mul = mvsim_poisson_mul((double)p->snr); ops.seed = p->seed; ops.stream = p->stream;
     ops.adjust = !materialise;             // a materialised volume is adjusted already
+    // a sparse tail: `con` has holes where these flags are clear, and launch_extract refuses every form but the two that read them.
+    // The flag words belong to this view until the next view's rotate kernel rewrites them; that kernel is enqueued behind this
+    // tail -- same stream, or joined (below: a sparse tail never stays pending on the tail stream)
+    if (tail.sparse) { ops.empty_flags = tail.sparse_flags; ops.empty_stride = tail.sparse_stride; }
     // compact: `con` holds the acquired planes only (read in order, the RNG counted in source planes).  The queue grows here, before the tail forks
     ExtractPlan xpl;
     MVSIM_TRY(extract_stage_plan(ctx, tail.zstride > 1 ? ExtractGeom::compact(dim, p->inc) : ExtractGeom::strided(dim, p->inc), ops, &xpl));
@@ -129,6 +139,9 @@ static int view_enqueue(mvsim_ctx* ctx, const float* gt, const int64_t dim[3], c
     // (not beside the fused rotate + attenuate + x transform of the next view: that kernel is bound by vector issue like the
     // sampler itself, and the two together measured slower than one after the other -- 17.6 against 17.2 ms per 8 views)
     if (x_done) overlap_ok = false;
+    // (a sparse tail implies x_done today.  Should the line above ever go: the pending tail would be reading ctx->plane_flags while the
+    // next view's rotate kernel rewrites them, and join_tail's ranges do not cover that workspace)
+    if (tail.sparse) overlap_ok = false;
     hipStream_t tail_on = ctx->stream;
     if (overlap_ok) {
         if (!ctx->tail_stream) {
@@ -171,9 +184,9 @@ static std::string view_graph_key(mvsim_ctx* ctx, const float* gt, const int64_t
     add(&o->rot, sizeof(o->rot)); add(&o->att, sizeof(o->att)); add(&o->con, sizeof(o->con)); add(&o->acq, sizeof(o->acq));
     add(&ctx->stream, sizeof(ctx->stream));
     const Options& q = ctx->opt;
-    const int oo[15] = {q.zpass, q.rocfft ? 1 : 0, q.fused_rotate, q.poisson_queue, q.early_sum ? 1 : 0, q.fuse_tail ? 1 : 0, q.psf_overlap ? 1 : 0,
+    const int oo[16] = {q.zpass, q.rocfft ? 1 : 0, q.fused_rotate, q.poisson_queue, q.early_sum ? 1 : 0, q.fuse_tail ? 1 : 0, q.psf_overlap ? 1 : 0,
                         q.attenuate_scan ? 1 : 0, q.fused_fftx, q.zconv_strided ? 1 : 0, q.skip_empty ? 1 : 0, q.exp, q.poisson_queue_share, ctx->queue_share_learned,
-                        q.skip_rows ? 1 : 0};
+                        q.skip_rows ? 1 : 0, q.skip_tail ? 1 : 0};
     add(oo, sizeof(oo));
     add(q.fft_pad, sizeof(q.fft_pad));
     return k;

@@ -217,6 +217,8 @@ struct Options {
     bool    skip_empty = true;         // convolution passes skip planes the fused rotate kernel found empty (exact; option for A/B runs)
     bool    skip_rows = true;          // ... and, where those flags are in use, the rotate kernel does not store the rows without a non-zero
                                        // voxel and pass B does not read them (row_bits.h; exact; option for A/B runs)
+    bool    skip_tail = true;          // ... and pass E does not store, nor phase 1 of the queue samplers read, the planes whose dilated flag is
+                                       // clear (extract_plan.h: tail_sparse_ok; exact; option for A/B runs)
     int64_t beads_pair_cap = (int64_t)1 << 28;   // bead renderer and volume injection: (brick, item) pairs one chunk may bin; larger calls run in chunks (beads.hip, aberrations.hip)
     int64_t reject_batch = 0;          // rejection sampler: trials per launch (0 = auto: 4 per wanted sample, 4096 .. 2^20) (procedural.hip)
     int     dog_pass = 0;              // the DoG kernels a call launches (detect.hip): 0 both, 1 the xy kernel alone, 2 the z kernel alone -- for
@@ -267,6 +269,7 @@ struct mvsim_ctx {
     unsigned int* queue_hint = nullptr;     // page-locked word the device raises: sixteenths of a block's voxels the fullest refused queue segment needed
     int           queue_share_learned = 0;  // ... as the host has seen it so far (auto share: queue_mode_next)
     int64_t       extract_path[5] = {-1, 0, 0, 0, 0};   // the sampler form of the last extract this context enqueued (mvsim_get_extract_path)
+    int64_t       tail_path[2] = {0, 0};    // {the last view's tail ran in sparse mode, its flag stride} (mvsim_get_tail_path)
     int           views_since_flags = 0;    // views run WITHOUT flags since (a volume without empty planes pays nothing for the bookkeeping)
     mvsim::DevBuf weight_img;               // computeWeightImage of the last volume size (mvsim_simulate_iteration_dev)
     mvsim::DevBuf decon_work[2];            // multi-view deconvolution (api_decon.cpp): the blurred estimate / ratio, and the correlation
@@ -429,6 +432,11 @@ struct ExtractOps {               // the operands of one launch_extract
     double        mul = 0.0;
     uint64_t      seed = 0;       // the RNG key and stream of the launch
     uint32_t      stream = 0;
+    // sparse tail (ConvTail::sparse): pass E has NOT written the planes of `in` whose flag is clear -- plane j of the buffer is flag
+    // empty_flags[j * empty_stride], so output plane k reads flag k * ExtractGeom::inc * empty_stride (extract_plan.h:
+    // tail_flag_of_output) -- and phase 1 must not read them.  Only the two queue samplers take it; launch_extract refuses every other form
+    const int*    empty_flags = nullptr;
+    int           empty_stride = 0;
 };
 int launch_extract(hipStream_t s, const ExtractPlan& pl, const ExtractOps& o);
 int launch_resolve(hipStream_t s, const ExtractPlan& pl, const ExtractOps& o);   // the sampler's second launch alone (the fused tail)
@@ -601,6 +609,16 @@ struct ConvTail {
     // words).  Non-null means that kernel has NOT written the rows whose bit is clear: pass B must read the bits, whatever else the
     // convolution decides
     const unsigned int* row_bits = nullptr;
+    // in: the caller's half of the sparse-tail condition (extract_plan.h: tail_sparse_ok) -- option skip_tail, `out` is the context's
+    // own workspace, and the launch behind the convolution will be one of the two queue samplers whichever stride is applied.
+    // out: sparse = pass E has left the planes k of `out` with sparse_flags[k * sparse_stride] == 0 UNWRITTEN (stale bytes of
+    // earlier views): nothing but a sampler launch of this view that carries the flags (ExtractOps::empty_flags) may read `out`.
+    // The flag words are the dilated flags of ctx->plane_flags, which the NEXT view's rotate kernel rewrites: the sampler has to be
+    // enqueued in front of it, on the same stream or joined (view_enqueue: a sparse tail never stays pending)
+    bool       want_sparse = false;
+    bool       sparse = false;
+    const int* sparse_flags = nullptr;
+    int        sparse_stride = 0;
 };
 // bytes of queue workspace the fused tail needs for this geometry (0: the geometry has no fused tail)
 size_t fused_tail_queue_bytes(const int64_t dim[3], const int64_t kdim[3], int inc, bool con_wanted, const Options& opt);

@@ -196,6 +196,107 @@ __global__ __launch_bounds__(256) void k_extract_noise2_any(const float* __restr
     p1_frame_close<true>(qcount, &qctr, qovf, segcap);
 }
 
+// Phase 1 behind a sparse tail (ExtractOps::empty_flags; extract_plan.h): the two kernels above for a buffer whose empty planes pass E has
+// not stored.  Kernels of their own -- the mode is not an argument of the unflagged ones, whose code stays what it was -- for single
+// views that are adjusted on the fly (the buffer is the context's workspace), planes of at least 256 voxels and fewer than 2^32 outputs
+// (every queue launch).  flags[j * fstride] is the flag of plane j of `in`.
+//
+// k_extract4_noise2_sparse: a slot is 64 consecutive float4 groups, of plane k from lane 0 and of plane k + 1 from lane `first` on
+// (first >= 64: one plane; a plane holds at least 64 groups, so never a third).  Where the slot starts -- plane k, group rem of it --
+// is carried from trip to trip in scalar registers: the grid stride is dq planes and dr groups.  The two flags of the NEXT trip are
+// requested (wave-uniform scalar loads) before this trip's voxels, so that no load of voxels waits behind a load of flags.
+//   * the slot lies in one empty plane of regime 0 or 1: poisson_phase1_empty -- no read, no adjust, no regime test per voxel;
+//   * else the ordinary phase 1, where a lane of an empty plane does not read: its four voxels are the plane's one value.
+template <bool CHECKED>
+__global__ __launch_bounds__(256) void k_extract4_noise2_sparse(const float* __restrict__ in, float* __restrict__ out,
+                                                                long long plane4, long long nzo, int inc, int idx_inc,
+                                                                const double* __restrict__ scal, float min_value, double mul,
+                                                                uint32_t k0, uint32_t k1, uint32_t stream,
+                                                                unsigned long long index_offset, PItem* __restrict__ queue,
+                                                                unsigned int* __restrict__ qcount, unsigned int segcap,
+                                                                const int* __restrict__ flags, int fstride)
+{
+    __shared__ unsigned long long qctr;
+    __shared__ unsigned int qovf[2];
+    __shared__ P1Scratch scratch[4];
+    p1_frame_open(&qctr, qovf);
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const P1Args pa = p1_frame_args(mul, k0, k1, stream, queue, segcap, &qctr, qovf);
+    const double corr = scal[1];
+    const P1Empty pe = p1_empty_of(corr, min_value, pa);
+    const float4* __restrict__ in4 = reinterpret_cast<const float4*>(in);
+    float4* __restrict__ out4 = reinterpret_cast<float4*>(out);
+    const unsigned int p4 = (unsigned int)plane4, total4 = (unsigned int)(plane4 * nzo), step = gridDim.x * 256u;   // (outputs < 2^32)
+    const unsigned int klast = (unsigned int)nzo - 1u;
+    const long long fstep = (long long)inc * fstride;                  // flag index per output plane
+    const unsigned long long sskip = (unsigned long long)(inc - 1) * p4, iskip = (unsigned long long)(idx_inc - 1) * p4;   // planes between two read / counted ones
+    unsigned int o0 = blockIdx.x * 256u + (unsigned int)wave * 64u;
+    TailSlot sl = tail_slot_at(o0, p4);
+    const unsigned int dq = step / p4, dr = step - dq * p4;
+    int fa = 1, fb = 1;
+    if (o0 < total4) { fa = flags[(long long)sl.k * fstep]; fb = flags[(long long)(sl.k < klast ? sl.k + 1u : klast) * fstep]; }
+    while (o0 < total4) {
+        const TailSlot sn = tail_slot_next(sl, dq, dr, p4);
+        const unsigned int o0n = o0 + step;
+        int fan = 1, fbn = 1;
+        if (o0n < total4) { fan = flags[(long long)sn.k * fstep]; fbn = flags[(long long)(sn.k < klast ? sn.k + 1u : klast) * fstep]; }
+        const unsigned int o = o0 + (unsigned int)lane;
+        const bool valid = o < total4;
+        float ov[4];
+        if (tail_slot_first(sl, p4) >= 64u && fa == 0 && pe.cls != 2) {  // wave-uniform
+            const unsigned long long idx4 = (unsigned long long)(sl.k * (unsigned int)idx_inc) * p4 + (sl.rem + (unsigned int)lane);
+            poisson_phase1_empty<CHECKED>(pe, valid ? 15u : 0u, index_offset + 4ull * idx4, 4ull * (unsigned long long)o, pa, ov);
+        } else {
+            // the lane's group in the buffer and on the RNG counter: the slot's first group (scalar) + lane, and past the plane boundary
+            // the planes in between (tail_lane's k * inc * p4 + within, without a 64-bit multiplication per lane)
+            const bool second = (unsigned int)lane >= tail_slot_first(sl, p4);
+            const bool empty = (second ? fb : fa) == 0;
+            const unsigned long long sbase = (unsigned long long)(sl.k * (unsigned int)inc) * p4 + sl.rem;
+            const unsigned long long ibase = (unsigned long long)(sl.k * (unsigned int)idx_inc) * p4 + sl.rem;
+            const unsigned long long src4 = sbase + (unsigned int)lane + (second ? sskip : 0ull);
+            const unsigned long long idx4 = ibase + (unsigned int)lane + (second ? iskip : 0ull);
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (valid) {
+                if (empty) {
+                    v = make_float4(pe.v, pe.v, pe.v, pe.v);
+                } else {
+                    v = in4[src4];
+                    v.x = adjust_one(v.x, corr, min_value);
+                    v.y = adjust_one(v.y, corr, min_value);
+                    v.z = adjust_one(v.z, corr, min_value);
+                    v.w = adjust_one(v.w, corr, min_value);
+                }
+            }
+            const float vv[4] = {v.x, v.y, v.z, v.w};
+            poisson_phase1<CHECKED>(vv, valid, index_offset + 4ull * idx4, 4ull * (unsigned long long)o, pa, &scratch[wave], lane, ov);
+        }
+        if (valid) out4[o] = make_float4(ov[0], ov[1], ov[2], ov[3]);
+        o0 = o0n; sl = sn; fa = fan; fb = fbn;
+    }
+    p1_frame_close<true>(qcount, &qctr, qovf, segcap);
+}
+
+template <bool CHECKED>
+__global__ __launch_bounds__(256) void k_extract_noise2_any_sparse(const float* __restrict__ in, float* __restrict__ out,
+                                                                   long long plane, long long nzo, int inc, int idx_inc,
+                                                                   const double* __restrict__ scal, float min_value, double mul,
+                                                                   uint32_t k0, uint32_t k1, uint32_t stream,
+                                                                   unsigned long long index_offset, PItem* __restrict__ queue,
+                                                                   unsigned int* __restrict__ qcount, unsigned int segcap,
+                                                                   long long slots_per_plane, const int* __restrict__ flags, int fstride)
+{
+    __shared__ unsigned long long qctr;
+    __shared__ unsigned int qovf[2];
+    __shared__ P1Scratch scratch[4];
+    p1_frame_open(&qctr, qovf);
+    const P1Args pa = p1_frame_args(mul, k0, k1, stream, queue, segcap, &qctr, qovf);
+    const double corr = scal[1];
+    const FetchContiguous<true> fetch{in, inc, corr, min_value};
+    group_walk_phase1_sparse<CHECKED>(fetch, p1_empty_of(corr, min_value, pa), flags, (long long)inc * fstride, out, plane, nzo, idx_inc,
+                                      index_offset, slots_per_plane, pa, scratch);
+    p1_frame_close<true>(qcount, &qctr, qovf, segcap);
+}
+
 // One block per queue segment (same grid as k_extract4_noise2; the grid-stride walk of that kernel spreads the
 // bright voxels evenly over the segments).
 __global__ __launch_bounds__(256) void k_poisson_resolve(ResolveJob job, const ExtractView* __restrict__ vt)
@@ -281,7 +382,27 @@ int launch_extract(hipStream_t s, const ExtractPlan& pl, const ExtractOps& o)
     const float* in = o.in ? o.in + g.in_offset : nullptr;
     const uint32_t k0 = (uint32_t)o.seed, k1 = (uint32_t)(o.seed >> 32);
     const unsigned long long offset = g.index_offset;
-    if (pl.kernel == EXTRACT_K_NOISE2 || pl.kernel == EXTRACT_K_NOISE2_ANY) {
+    const bool queued = pl.kernel == EXTRACT_K_NOISE2 || pl.kernel == EXTRACT_K_NOISE2_ANY;
+    if (o.empty_flags && !(queued && o.adjust && o.nviews == 0 && g.in_offset == 0 && g.plane >= TAIL_SPARSE_MIN_PLANE && o.empty_stride >= 1)) {
+        // the buffer has holes only a flagged queue sampler knows about: no other form may read it
+        set_error("extract: a sparse tail needs one of the two queue samplers on a single adjusted view");
+        return MVSIM_EINVAL;
+    }
+    if (queued && o.empty_flags) {
+        const QueueLayout::Region q = pl.layout.region(o.queue_ws);
+        PItem* queue = reinterpret_cast<PItem*>(q.items);
+        dispatch1(pl.checked, [&](auto C) {
+            if (pl.kernel == EXTRACT_K_NOISE2)
+                hipLaunchKernelGGL((k_extract4_noise2_sparse<decltype(C)::value>), grid, block, 0, s, in, o.out, g.plane / 4, g.nzo, g.inc, g.index_inc,
+                                   o.scal, o.min_value, o.mul, k0, k1, o.stream, offset, queue, q.counts, pl.segcap, o.empty_flags, o.empty_stride);
+            else
+                hipLaunchKernelGGL((k_extract_noise2_any_sparse<decltype(C)::value>), grid, block, 0, s, in, o.out, g.plane, g.nzo, g.inc, g.index_inc,
+                                   o.scal, o.min_value, o.mul, k0, k1, o.stream, offset, queue, q.counts, pl.segcap, pl.slots_per_plane,
+                                   o.empty_flags, o.empty_stride);
+        });
+        return launch_resolve(s, pl, o);
+    }
+    if (queued) {
         const QueueLayout::Region q = pl.layout.region(o.queue_ws);
         PItem* queue = reinterpret_cast<PItem*>(q.items);
         dispatch2(o.adjust, pl.checked, [&](auto A, auto C) {

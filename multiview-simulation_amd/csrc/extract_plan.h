@@ -173,4 +173,54 @@ inline ExtractPlan extract_plan(const ExtractGeom& g, bool aligned16, bool noise
     return p;
 }
 
+// ---- The sparse tail (option skip_tail).  Behind a flagged view (the fused rotate kernel's plane flags, dilated by the reach of the
+// PSF's z taps) a plane of the convolved volume whose flag is clear is exactly zero: pass E does not store it and phase 1 of the queue
+// samplers does not read it -- every voxel of it has the one value adjust_one(+0, corr, min_value).  The buffer between the two then
+// has holes, so the mode is taken only where the one reader of the buffer is known, BEFORE pass E is enqueued, to be a flagged sampler.
+// The caller's half (view_enqueue): the option, the convolved volume not requested -- the buffer is the context's own workspace --, and
+// the launch behind the convolution one of the two queue samplers ...
+inline bool tail_sparse_caller(bool skip_tail, bool con_requested, bool queue_sampler) { return skip_tail && !con_requested && queue_sampler; }
+// ... the driver's half: the view carries dilated flags (x_done, a whole single view, skip_empty, not the inline z pass) and pass E
+// does not run the fused tail
+inline bool tail_sparse_ok(bool caller_half, bool has_flags, bool fused_tail) { return caller_half && has_flags && !fused_tail; }
+
+// phase 1 tells a slot's planes apart by ONE plane boundary (the vector form: 64 float4 groups per slot), so a plane holds at least a slot
+constexpr long long TAIL_SPARSE_MIN_PLANE = 256;
+// "one of the two queue samplers" for an acquisition of every inc-th plane of `dim`, whichever of the two geometries the convolution
+// leaves (compact planes or all of them) and whatever the buffers' alignment: known from the sizes and the context's queue setting alone
+inline bool tail_queue_sampler(const int64_t dim[3], int inc, bool noise, QueueMode mode)
+{
+    if (!noise || (long long)dim[0] * dim[1] < TAIL_SPARSE_MIN_PLANE) return false;
+    for (int compact = 0; compact < 2; ++compact)
+        for (int aligned = 0; aligned < 2; ++aligned) {
+            const int k = extract_plan(compact ? ExtractGeom::compact(dim, inc) : ExtractGeom::strided(dim, inc), aligned != 0, true, mode).kernel;
+            if (k != EXTRACT_K_NOISE2 && k != EXTRACT_K_NOISE2_ANY) return false;
+        }
+    return true;
+}
+
+// Which flag stands for which plane.  Pass E produces the planes j = 0 .. nk-1 of the buffer; plane j is source plane j * zstride, the
+// index of its dilated flag (zstride: ConvTail::sparse_stride).  Output plane k of the sampler reads buffer plane k * g.inc (whole
+// views: in_offset = 0), hence flag k * g.inc * zstride: source plane k * inc for both ExtractGeom::strided (g.inc = inc, zstride = 1)
+// and ::compact (g.inc = 1, zstride = inc).
+inline long long tail_flag_of_buffer_plane(long long j, int zstride) { return j * zstride; }
+inline long long tail_flag_of_output(const ExtractGeom& g, long long k, int zstride) { return tail_flag_of_buffer_plane(k * g.inc, zstride); }
+
+// The vector form's walk behind a sparse tail (k_extract4_noise2_sparse; constexpr: host and device).  A wave slot is 64 consecutive
+// float4 groups of the output from group o0 on; p4 groups make a plane (p4 >= 64, outputs < 2^32).  The slot starts in plane k at
+// group rem of it and the grid stride is dq planes and dr groups, so the next slot follows without a division.
+struct TailSlot { unsigned int k, rem; };
+constexpr TailSlot tail_slot_at(unsigned int o0, unsigned int p4) { return TailSlot{o0 / p4, o0 - (o0 / p4) * p4}; }
+constexpr TailSlot tail_slot_next(TailSlot s, unsigned int dq, unsigned int dr, unsigned int p4)
+{
+    return s.rem + dr >= p4 ? TailSlot{s.k + dq + 1u, s.rem + dr - p4} : TailSlot{s.k + dq, s.rem + dr};
+}
+// groups of plane k from lane 0 on (>= 64: the slot lies in one plane); from that lane on the groups are of plane k + 1 -- never of a third
+constexpr unsigned int tail_slot_first(TailSlot s, unsigned int p4) { return p4 - s.rem; }
+struct TailLane { unsigned int k, within; bool second; };   // a lane's group: its plane, its place in it, whether it is past the boundary
+constexpr TailLane tail_lane(TailSlot s, unsigned int lane, unsigned int p4)
+{
+    return lane >= tail_slot_first(s, p4) ? TailLane{s.k + 1u, lane - tail_slot_first(s, p4), true} : TailLane{s.k, s.rem + lane, false};
+}
+
 }  // namespace mvsim

@@ -782,9 +782,15 @@ int custom_fft_convolve_slab(mvsim_ctx* ctx, const float* img, const int64_t dim
     // both half spectra carry the factor 2 left in by pass A (see k_fft_x_r2c): 2 * 2 = 4
     const float scale = (float)(0.25 / ((double)pl.px * (double)pl.py * ((pl.zdirect && !r.zinline) ? 1.0 : (double)pl.pz)));
     int nblk = 0;
+    // The sparse tail (option skip_tail; extract_plan.h: tail_sparse_ok): this view carries plane flags, and the caller vouches that
+    // `out` is a workspace nobody but its flagged queue sampler reads -- pass E then stores nothing into the planes k whose dilated
+    // flag k * zstride is clear.  Handed over through the tail: the flags the sampler reads are the words pass E read.
+    // (r.pnz_dil already says: x_done, a whole single view, skip_empty, not the inline z pass, not the fused tail)
+    const bool sparse = tail_sparse_ok(tail && tail->want_sparse, r.pnz_dil != nullptr, fuse) && r.V == 1 && !r.is_slab;
+    if (tail) { tail->sparse = sparse; tail->sparse_flags = sparse ? r.pnz_dil : nullptr; tail->sparse_stride = sparse ? r.zstride : 0; }
     MVSIM_TRY(launch_c2r(ctx, pl.M, Fz, out, r.tw_m, r.tw_px, pl.hxp, pl.py * r.zstride, pl.n[0], pl.n[1], (long long)pl.n[1] * r.nk, scale,
                          pl.early ? nullptr : ctx->partials_e.as<double>(), &nblk, fuse ? &fz : nullptr,
-                         C2REmpty{r.pnz_dil, r.zstride}));
+                         C2REmpty{r.pnz_dil, r.zstride, sparse ? 1 : 0}));
     if (fuse && nblk != fp.blocks) { set_error("fused tail: block count mismatch"); return MVSIM_EINVAL; }
     if (!pl.early) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, s, ctx->partials_e.as<double>(), (long long)nblk, r.scal, 1.0,
                                       r.corr_n, r.corr_min, r.corr_target);

@@ -104,10 +104,12 @@ struct C2RFuse {
 };
 
 // planes of pass E's input known to be empty (pass D has not written them): plane k of this pass is plane k * stride of the
-// dilated flag array (null: none)
+// dilated flag array (null: none).  sparse: the mode bit of the sparse tail (ConvTail::sparse) -- the rows of those planes are not
+// stored either (k_fft_x_c2r_sparse); 0: they are stored as zeros
 struct C2REmpty {
     const int* flags;
     int        stride;
+    int        sparse;
 };
 
 // ---------------------------------------------------------------------------------- direct z pass (zconv.hip)

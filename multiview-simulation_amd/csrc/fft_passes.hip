@@ -660,6 +660,15 @@ __global__ __launch_bounds__(CfgX<PLAN::len>::T) void k_fft_x_r2c(const float* _
 // z pass), stores the adjusted row only if the caller wants the volume, and turns the rows of acquired planes into the
 // acquisition: a copy (no noise) or phase 1 of the Poisson sampler (poisson_phase1; the rest is queued for
 // k_poisson_resolve).  Saves the 8 N bytes of the convolved volume's round trip and a launch.
+// SPARSE (the sparse tail, C2REmpty::sparse; never with FUSE): a row of an empty plane is not stored at all -- the sampler behind this
+// pass carries the same flags and does not read it (ConvTail::sparse) -- and a block whose rows all lie in empty planes returns before
+// it has requested anything but the flags.  The mode is a template argument by way of the plan's type, k_fft_x_c2r<SparseTail<PLAN>, false>:
+// the instances without it keep their symbols and, line for line, their code (a third template parameter renames every instance, and a
+// body shared through a device function changed the schedule of all of them).
+template <class P> struct SparseTail : P {};
+template <class P> struct is_sparse_tail { static constexpr bool value = false; };
+template <class P> struct is_sparse_tail<SparseTail<P>> { static constexpr bool value = true; };
+
 template <class PLAN, bool FUSE>
 __global__ __launch_bounds__(CfgX<PLAN::len>::T) void k_fft_x_c2r(const float2* __restrict__ srcc,
                                                                  float* __restrict__ out,
@@ -668,6 +677,8 @@ __global__ __launch_bounds__(CfgX<PLAN::len>::T) void k_fft_x_c2r(const float2* 
                                                                  int nx, int ny, long long rows, float scale,
                                                                  double* __restrict__ partial, C2RFuse f, C2REmpty em)
 {
+    constexpr bool SPARSE = is_sparse_tail<PLAN>::value;
+    static_assert(!(FUSE && SPARSE), "the fused tail stores no convolved volume");
     constexpr int M = PLAN::len;
     using C = CfgX<M>;
     constexpr int NR = C::NL, LP = C::LP, T = C::T, LW = C::LW, NW = C::NW;
@@ -675,6 +686,18 @@ __global__ __launch_bounds__(CfgX<PLAN::len>::T) void k_fft_x_c2r(const float2* 
     float2* tw = lds + NR * LP;
     double* red = reinterpret_cast<double*>(lds + NR * LP + M);              // NW doubles
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (SPARSE) {
+        // The block's rows lie in planes zb0 .. zb1 (rows = Ny * planes < 2^31).  Up to two planes, both empty (block-uniform, two
+        // scalar loads): nothing to store, and nothing waits at the barrier below because nobody gets there.  Blocks of more than two
+        // planes (Ny < the block's rows / 2) decide wave by wave, further down.
+        const unsigned rb0 = blockIdx.x * (unsigned)NR;
+        const unsigned rb1 = (rb0 + (unsigned)NR < (unsigned)rows ? rb0 + (unsigned)NR : (unsigned)rows) - 1u;
+        const int zb0 = (int)(rb0 / (unsigned)ny), zb1 = (int)(rb1 / (unsigned)ny);
+        if (zb1 - zb0 <= 1 && (em.flags[zb0 * em.stride] | em.flags[zb1 * em.stride]) == 0) {
+            if (partial != nullptr && tid == 0) partial[blockIdx.x] = 0.0;   // (a sum taken here: this block's share of it)
+            return;
+        }
+    }
     float2* wbuf = lds + wave * LW * LP;
     // FUSE: behind the 32 doubles of `red`: the append counter (64 bits) and the two refusal counters, then one P1Scratch per wave
     unsigned long long* qctr = reinterpret_cast<unsigned long long*>(red + 32);
@@ -721,6 +744,13 @@ __global__ __launch_bounds__(CfgX<PLAN::len>::T) void k_fft_x_c2r(const float2* 
 #pragma unroll
     for (int j = 0; j < LW; ++j)
         if (rowflag[j] == 0) offs[j] = -1;
+    // SPARSE: ... and not stored either (bit j: row j of this wave lies in an empty plane; wave-uniform)
+    static_assert(LW <= 32, "one bit per row of a wave");
+    unsigned int unstored = 0u;
+    if (SPARSE) {
+#pragma unroll
+        for (int j = 0; j < LW; ++j) unstored |= (rowflag[j] == 0 ? 1u : 0u) << j;
+    }
     // every row of this wave lies in an empty plane (wave-uniform): nothing to read or transform, its outputs are zeros
     bool wave_empty = !FUSE && em.flags != nullptr;
 #pragma unroll
@@ -844,6 +874,7 @@ __global__ __launch_bounds__(CfgX<PLAN::len>::T) void k_fft_x_c2r(const float2* 
     for (int j = 0; j < LW; ++j) {
         const long long row = row0 + j;
         if (row >= rows) break;
+        if (SPARSE && ((unstored >> j) & 1u) != 0u) continue;
         float* __restrict__ o = out + row * nx;
         if (wave_empty) {
             if (vec_out) for (int q = lane; 4 * q < nx; q += 64) *reinterpret_cast<float4*>(o + 4 * q) = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -877,6 +908,7 @@ __global__ __launch_bounds__(CfgX<PLAN::len>::T) void k_fft_x_c2r(const float2* 
         partial[blockIdx.x] = sum;
     }
 }
+
 template <class PLAN>
 static int launch_r2c_t(mvsim_ctx* ctx, const float* src, const SrcMap& map, float2* dst, const float2* tw,
                         const float2* twx, int hxp, long long rows)
@@ -905,6 +937,11 @@ static int launch_c2r_t(mvsim_ctx* ctx, const float2* srcc, float* out, const fl
         MVSIM_TRY(set_lds(ctx, k_fft_x_c2r<PLAN, true>, lds));
         hipLaunchKernelGGL((k_fft_x_c2r<PLAN, true>), dim3((unsigned)blocks), dim3(C::T), lds, s, srcc, out, tw, twx, hxp, py, nx, ny,
                            rows, scale, partial, *fuse, em);
+    } else if (em.sparse) {
+        if (!em.flags) { set_error("pass E: sparse mode without plane flags"); return MVSIM_EINVAL; }
+        MVSIM_TRY(set_lds(ctx, k_fft_x_c2r<SparseTail<PLAN>, false>, C::LDS));
+        hipLaunchKernelGGL((k_fft_x_c2r<SparseTail<PLAN>, false>), dim3((unsigned)blocks), dim3(C::T), C::LDS, s, srcc, out, tw, twx, hxp, py, nx, ny,
+                           rows, scale, partial, C2RFuse{}, em);
     } else {
         MVSIM_TRY(set_lds(ctx, k_fft_x_c2r<PLAN, false>, C::LDS));
         hipLaunchKernelGGL((k_fft_x_c2r<PLAN, false>), dim3((unsigned)blocks), dim3(C::T), C::LDS, s, srcc, out, tw, twx, hxp, py, nx, ny,

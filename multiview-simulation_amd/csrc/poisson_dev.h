@@ -116,6 +116,13 @@ __device__ __forceinline__ int p1_class(float v, const P1Args& a)
     return ((double)v * a.mul >= 10.0) ? 2 : 1;
 }
 
+// The "count is 0" shortcut of an inversion voxel as an integer threshold on its random word (poisson_phase1 says why it is safe)
+__device__ __forceinline__ uint32_t p1_zero_threshold(float v, const P1Args& a)
+{
+    const float tf = (1.0f - v * a.mulf) - 2.0e-6f;
+    return (uint32_t)(fmaxf(tf, 0.f) * 4294967296.0f);
+}
+
 // The squeeze of PTRS attempt 0 (ptrs_setup + ptrs_fast, outcome 0) in single precision.  Returns true only when the
 // fp64 recipe is CERTAIN to accept at the squeeze with the same k:
 //   b, a:  v_sqrt_f32 / constants / two roundings          -> relative error <= 4e-7 (b), 1e-6 (a)
@@ -178,8 +185,7 @@ __device__ __forceinline__ void poisson_phase1(const float vv[4], bool valid, un
                 // count = 0  <=>  u = (w + 0.5) 2^-32 < exp(-lambda).  Sufficient, in integers: w < thr with
                 // thr = floor((1 - lf - 2e-6) 2^32): lf is lambda to 1.2e-7 and the two fp32 subtractions round by <= 1.2e-7,
                 // so w < thr implies u < 1 - lambda - 1.7e-6 < exp(-lambda).  (lf >= 1: thr = 0, never fires.)
-                const float tf = (1.0f - vv[c] * a.mulf) - 2.0e-6f;
-                const uint32_t thr = (uint32_t)(fmaxf(tf, 0.f) * 4294967296.0f);
+                const uint32_t thr = p1_zero_threshold(vv[c], a);
 #ifndef MVSIM_EXP_NOSMALLPUSH
                 if (!(w[c] < thr)) {
                     unsigned int pos;
@@ -266,6 +272,46 @@ __device__ __forceinline__ void poisson_phase1(const float vv[4], bool valid, un
     p1_wave_order();                                        // the scratch is reused by the wave's next slot
 }
 
+// ---- The sparse tail (extract_plan.h; option skip_tail): a plane of the convolved volume whose dilated flag is clear is exactly zero
+// and pass E has not stored it.  Every voxel of it has ONE value, adjust_one(+0, corr, min_value) -- the sign of a stored zero would
+// not have survived `+ min_value` either, and where it would (min_value = -0) the voxel is in regime 0 under both signs -- so its
+// regime and the threshold of the "count is 0" shortcut are computed once per wave, with the functions every other voxel goes through.
+struct P1Empty {                  // wave-uniform
+    float    v;                   // the value of every voxel of an empty plane
+    int      cls;                 // its regime (p1_class)
+    uint32_t thr;                 // its p1_zero_threshold (regime 1)
+};
+
+__device__ __forceinline__ P1Empty p1_empty_of(double corr, float min_value, const P1Args& a)
+{
+    P1Empty e;
+    e.v = adjust_one(+0.f, corr, min_value);
+    e.cls = p1_class(e.v, a);
+    e.thr = p1_zero_threshold(e.v, a);
+    return e;
+}
+
+// Phase 1 of one lane's group in a wave slot that lies wholly in an empty plane, regimes 0 and 1 (regime 2, a caller with a large
+// min_value: poisson_phase1 on the constant values).  `has`: bit c = component c of the group is a voxel of the plane.  What is left of
+// poisson_phase1 for such a slot: the group's Philox block, four compares, the appends of the misses, and no bright pair to look for.
+template <bool CHECKED>
+__device__ __forceinline__ void poisson_phase1_empty(const P1Empty& e, unsigned int has, unsigned long long index4, unsigned long long out4,
+                                                     const P1Args& a, float ov[4])
+{
+#pragma unroll
+    for (int c = 0; c < 4; ++c) ov[c] = 0.f;
+    if (e.cls != 1 || has == 0u) return;
+    const Philox4 r = group_block(index4, a.stream, a.k0, a.k1);
+    const uint32_t w[4] = {group_word(r, 0u), group_word(r, 1u), group_word(r, 2u), group_word(r, 3u)};
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+        if (((has >> c) & 1u) != 0u && !(w[c] < e.thr)) {
+            unsigned int pos;
+            if (p1_slot<CHECKED>(a, true, pos)) p1_push(a.seg + pos, out4 + (unsigned long long)c, e.v, w[c], 0u);
+            else ov[c] = -e.v;
+        }
+}
+
 // ---- The block frame around phase 1 (the three queue kernels and pass E).  The append counter and the two refusal words are LDS of the
 // kernel (pass E: of its dynamic LDS), so the frame takes pointers.
 // Thread 0 zeroes the words; a block barrier has to follow before the first append (pass E: the one behind its twiddle table).
@@ -318,16 +364,23 @@ struct GroupSlot {
     __device__ __forceinline__ long long out0(long long plane) const { return k * plane + i0; }
 };
 
-__device__ __forceinline__ GroupSlot group_slot(long long sl, int lane, long long slots_per_plane, long long plane, long long idx_inc,
-                                                unsigned long long index_offset)
+// slot jb of acquired plane k
+__device__ __forceinline__ GroupSlot group_slot_of_plane(long long k, long long jb, int lane, long long plane, long long idx_inc,
+                                                         unsigned long long index_offset)
 {
     GroupSlot s;
-    s.k = sl / slots_per_plane;
-    const long long jb = sl - s.k * slots_per_plane;
+    s.k = k;
     const unsigned long long ibase = index_offset + (unsigned long long)(s.k * idx_inc) * (unsigned long long)plane;   // RNG index of the plane's voxel 0
     s.g = (ibase >> 2) + (unsigned long long)(jb * 64 + lane);
     s.i0 = (long long)(4ull * s.g - ibase);
     return s;
+}
+
+__device__ __forceinline__ GroupSlot group_slot(long long sl, int lane, long long slots_per_plane, long long plane, long long idx_inc,
+                                                unsigned long long index_offset)
+{
+    const long long k = sl / slots_per_plane;
+    return group_slot_of_plane(k, sl - k * slots_per_plane, lane, plane, idx_inc, index_offset);
 }
 
 // How the walk reads the voxels of a slot: fetch(s, plane, vv) fills vv[c] for the components inside the plane, zeros elsewhere.
@@ -395,6 +448,50 @@ __device__ __forceinline__ void group_walk_phase1(const FETCH& fetch, float* __r
 #pragma unroll
         for (int c = 0; c < 4; ++c)
             if (s.has(c, plane)) out[s.out0(plane) + c] = ov[c];
+    }
+}
+
+// The same walk behind a sparse tail (k_extract_noise2_any_sparse): a slot's 64 groups are of ONE plane, so the plane's flag decides for
+// the whole wave.  flags[k * fstep] is the flag of acquired plane k; the next trip's flag is requested (a wave-uniform scalar load) while
+// this trip is processed, so that no tile load ever waits behind a flag.  An empty plane is not read: regimes 0 and 1 of its one value
+// take poisson_phase1_empty, regime 2 the ordinary phase 1 on the constant.  The slot's plane is carried from trip to trip (the grid
+// stride is so many planes and so many slots further on) instead of divided out per lane.
+template <bool CHECKED, class FETCH>
+__device__ __forceinline__ void group_walk_phase1_sparse(const FETCH& fetch, const P1Empty& pe, const int* __restrict__ flags, long long fstep,
+                                                         float* __restrict__ out, long long plane, long long nzo, long long idx_inc,
+                                                         unsigned long long index_offset, long long slots_per_plane, const P1Args& pa,
+                                                         P1Scratch* scratch)
+{
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long long slots = slots_per_plane * nzo, stride = (long long)gridDim.x * 4;
+    long long sl = (long long)blockIdx.x * 4 + wave;
+    long long k = sl / slots_per_plane, jb = sl - k * slots_per_plane;
+    const long long dk = stride / slots_per_plane, dj = stride - dk * slots_per_plane;
+    int flag = sl < slots ? flags[k * fstep] : 1;
+    while (sl < slots) {
+        long long kn = k + dk, jn = jb + dj;
+        if (jn >= slots_per_plane) { jn -= slots_per_plane; kn += 1; }
+        const long long sln = sl + stride;
+        const int flag_next = sln < slots ? flags[kn * fstep] : 1;
+        const GroupSlot s = group_slot_of_plane(k, jb, lane, plane, idx_inc, index_offset);
+        const unsigned int has = (s.has(0, plane) ? 1u : 0u) | (s.has(1, plane) ? 2u : 0u) | (s.has(2, plane) ? 4u : 0u) | (s.has(3, plane) ? 8u : 0u);
+        float ov[4];
+        if (flag == 0 && pe.cls != 2) {                   // wave-uniform
+            poisson_phase1_empty<CHECKED>(pe, has, 4ull * s.g, (unsigned long long)s.out0(plane), pa, ov);
+        } else {
+            float vv[4];
+            if (flag == 0) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) vv[c] = ((has >> c) & 1u) != 0u ? pe.v : 0.f;
+            } else {
+                fetch(s, plane, vv);
+            }
+            poisson_phase1<CHECKED>(vv, has != 0u, 4ull * s.g, (unsigned long long)s.out0(plane), pa, &scratch[wave], lane, ov);
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (((has >> c) & 1u) != 0u) out[s.out0(plane) + c] = ov[c];
+        sl = sln; k = kn; jb = jn; flag = flag_next;
     }
 }
 
