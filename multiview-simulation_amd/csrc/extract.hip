@@ -203,11 +203,29 @@ __global__ __launch_bounds__(256) void k_extract_noise2_any(const float* __restr
 //
 // k_extract4_noise2_sparse: a slot is 64 consecutive float4 groups, of plane k from lane 0 and of plane k + 1 from lane `first` on
 // (first >= 64: one plane; a plane holds at least 64 groups, so never a third).  Where the slot starts -- plane k, group rem of it --
-// is carried from trip to trip in scalar registers: the grid stride is dq planes and dr groups.  The two flags of the NEXT trip are
-// requested (wave-uniform scalar loads) before this trip's voxels, so that no load of voxels waits behind a load of flags.
+// is carried from trip to trip in scalar registers: the grid stride is dq planes and dr groups.  The flags of the wave's next 32 trips
+// are ONE per-lane load and a ballot (tail_mask_ask: before the first voxel load, and again every 32 trips): a trip shifts the mask and
+// tests a bit -- no flag load, no flag register and no clamp in the loop.
+//   ALIGNED (planes of a multiple of 64 groups; the launcher picks the instance from the plan): a slot lies in ONE plane and no slot is
+//     cut by the end of the output -- no second plane, no per-lane flag, no `valid` mask; the lane's address is a scalar base + lane.
+//   else the per-lane form: the lanes from `first` on ask the mask's second half, a lane of an empty plane does not read -- its four
+//     voxels are the plane's one value -- and lanes past the end of the output are masked out.
 //   * the slot lies in one empty plane of regime 0 or 1: poisson_phase1_empty -- no read, no adjust, no regime test per voxel;
-//   * else the ordinary phase 1, where a lane of an empty plane does not read: its four voxels are the plane's one value.
-template <bool CHECKED>
+//   * else the ordinary phase 1 (regime 2, a caller with a large min_value: on the constant, still without a read).
+// What the trip loop carries in scalar registers: the slot's first group, its plane and place in it, the mask, the trip count.  The
+// products with inc / index_inc are formed per trip on the scalar unit.  profiles/tail_walk_isa.txt: the aligned instance spills as
+// many scalars as the unflagged kernel and reloads none of them on the path a trip takes.
+template <bool ALIGNED>
+__device__ __forceinline__ unsigned long long tail_mask_load(const int* __restrict__ flags, long long fstep, unsigned int o0, unsigned int lane,
+                                                             unsigned int step, unsigned int p4, unsigned int total4, unsigned int klast)
+{
+    const TailAsk a = tail_mask_ask(o0, lane, step, p4, total4, klast);
+    int f = 0;
+    if (a.ask && !(ALIGNED && lane >= TAIL_MASK_TRIPS)) f = flags[(long long)a.k * fstep];
+    return __ballot(f != 0);
+}
+
+template <bool CHECKED, bool ALIGNED>
 __global__ __launch_bounds__(256) void k_extract4_noise2_sparse(const float* __restrict__ in, float* __restrict__ out,
                                                                 long long plane4, long long nzo, int inc, int idx_inc,
                                                                 const double* __restrict__ scal, float min_value, double mul,
@@ -220,7 +238,8 @@ __global__ __launch_bounds__(256) void k_extract4_noise2_sparse(const float* __r
     __shared__ unsigned int qovf[2];
     __shared__ P1Scratch scratch[4];
     p1_frame_open(&qctr, qovf);
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned int lane = threadIdx.x & 63u;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const P1Args pa = p1_frame_args(mul, k0, k1, stream, queue, segcap, &qctr, qovf);
     const double corr = scal[1];
     const P1Empty pe = p1_empty_of(corr, min_value, pa);
@@ -229,49 +248,65 @@ __global__ __launch_bounds__(256) void k_extract4_noise2_sparse(const float* __r
     const unsigned int p4 = (unsigned int)plane4, total4 = (unsigned int)(plane4 * nzo), step = gridDim.x * 256u;   // (outputs < 2^32)
     const unsigned int klast = (unsigned int)nzo - 1u;
     const long long fstep = (long long)inc * fstride;                  // flag index per output plane
-    const unsigned long long sskip = (unsigned long long)(inc - 1) * p4, iskip = (unsigned long long)(idx_inc - 1) * p4;   // planes between two read / counted ones
     unsigned int o0 = blockIdx.x * 256u + (unsigned int)wave * 64u;
     TailSlot sl = tail_slot_at(o0, p4);
     const unsigned int dq = step / p4, dr = step - dq * p4;
-    int fa = 1, fb = 1;
-    if (o0 < total4) { fa = flags[(long long)sl.k * fstep]; fb = flags[(long long)(sl.k < klast ? sl.k + 1u : klast) * fstep]; }
-    while (o0 < total4) {
-        const TailSlot sn = tail_slot_next(sl, dq, dr, p4);
-        const unsigned int o0n = o0 + step;
-        int fan = 1, fbn = 1;
-        if (o0n < total4) { fan = flags[(long long)sn.k * fstep]; fbn = flags[(long long)(sn.k < klast ? sn.k + 1u : klast) * fstep]; }
-        const unsigned int o = o0 + (unsigned int)lane;
-        const bool valid = o < total4;
+    unsigned long long mask = 0ull;
+    for (unsigned int trip = 0u; o0 < total4; ++trip) {
+        if (tail_mask_refill(trip)) mask = tail_mask_load<ALIGNED>(flags, fstep, o0, lane, step, p4, total4, klast);   // wave-uniform
+        const bool fa = tail_mask_first(mask);
+        // the slot's first group in the buffer and on the RNG counter (scalar; the lane adds itself)
+        const unsigned long long sbase = (unsigned long long)(sl.k * (unsigned int)inc) * p4 + sl.rem;
+        const unsigned long long ibase = (unsigned long long)(sl.k * (unsigned int)idx_inc) * p4 + sl.rem;
         float ov[4];
-        if (tail_slot_first(sl, p4) >= 64u && fa == 0 && pe.cls != 2) {  // wave-uniform
-            const unsigned long long idx4 = (unsigned long long)(sl.k * (unsigned int)idx_inc) * p4 + (sl.rem + (unsigned int)lane);
-            poisson_phase1_empty<CHECKED>(pe, valid ? 15u : 0u, index_offset + 4ull * idx4, 4ull * (unsigned long long)o, pa, ov);
-        } else {
-            // the lane's group in the buffer and on the RNG counter: the slot's first group (scalar) + lane, and past the plane boundary
-            // the planes in between (tail_lane's k * inc * p4 + within, without a 64-bit multiplication per lane)
-            const bool second = (unsigned int)lane >= tail_slot_first(sl, p4);
-            const bool empty = (second ? fb : fa) == 0;
-            const unsigned long long sbase = (unsigned long long)(sl.k * (unsigned int)inc) * p4 + sl.rem;
-            const unsigned long long ibase = (unsigned long long)(sl.k * (unsigned int)idx_inc) * p4 + sl.rem;
-            const unsigned long long src4 = sbase + (unsigned int)lane + (second ? sskip : 0ull);
-            const unsigned long long idx4 = ibase + (unsigned int)lane + (second ? iskip : 0ull);
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (valid) {
-                if (empty) {
-                    v = make_float4(pe.v, pe.v, pe.v, pe.v);
-                } else {
-                    v = in4[src4];
+        if (ALIGNED) {
+            const unsigned long long index4 = index_offset + 4ull * (ibase + lane), o4 = 4ull * (unsigned long long)(o0 + lane);
+            if (!fa && pe.cls != 2) {                                        // wave-uniform
+                poisson_phase1_empty<CHECKED>(pe, 15u, index4, o4, pa, ov);
+            } else {
+                float4 v = make_float4(pe.v, pe.v, pe.v, pe.v);
+                if (fa) {                                                    // wave-uniform: the whole slot reads, or none of it
+                    v = (in4 + sbase)[lane];
                     v.x = adjust_one(v.x, corr, min_value);
                     v.y = adjust_one(v.y, corr, min_value);
                     v.z = adjust_one(v.z, corr, min_value);
                     v.w = adjust_one(v.w, corr, min_value);
                 }
+                const float vv[4] = {v.x, v.y, v.z, v.w};
+                poisson_phase1<CHECKED>(vv, true, index4, o4, pa, &scratch[wave], (int)lane, ov);
             }
-            const float vv[4] = {v.x, v.y, v.z, v.w};
-            poisson_phase1<CHECKED>(vv, valid, index_offset + 4ull * idx4, 4ull * (unsigned long long)o, pa, &scratch[wave], lane, ov);
+            (out4 + o0)[lane] = make_float4(ov[0], ov[1], ov[2], ov[3]);
+        } else {
+            const unsigned int o = o0 + lane;
+            const bool valid = o < total4;
+            if (tail_slot_first(sl, p4) >= 64u && !fa && pe.cls != 2) {      // wave-uniform
+                poisson_phase1_empty<CHECKED>(pe, valid ? 15u : 0u, index_offset + 4ull * (ibase + lane), 4ull * (unsigned long long)o, pa, ov);
+            } else {
+                // past the plane boundary the planes in between come on top (tail_lane's k * inc * p4 + within, without a 64-bit
+                // multiplication per lane)
+                const bool second = lane >= tail_slot_first(sl, p4);
+                const bool empty = !(second ? tail_mask_second(mask) : fa);
+                const unsigned long long sskip = (unsigned long long)(unsigned int)(inc - 1) * p4, iskip = (unsigned long long)(unsigned int)(idx_inc - 1) * p4;
+                const unsigned long long src4 = sbase + lane + (second ? sskip : 0ull);
+                const unsigned long long idx4 = ibase + lane + (second ? iskip : 0ull);
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (valid) {
+                    if (empty) {
+                        v = make_float4(pe.v, pe.v, pe.v, pe.v);
+                    } else {
+                        v = in4[src4];
+                        v.x = adjust_one(v.x, corr, min_value);
+                        v.y = adjust_one(v.y, corr, min_value);
+                        v.z = adjust_one(v.z, corr, min_value);
+                        v.w = adjust_one(v.w, corr, min_value);
+                    }
+                }
+                const float vv[4] = {v.x, v.y, v.z, v.w};
+                poisson_phase1<CHECKED>(vv, valid, index_offset + 4ull * idx4, 4ull * (unsigned long long)o, pa, &scratch[wave], (int)lane, ov);
+            }
+            if (valid) out4[o] = make_float4(ov[0], ov[1], ov[2], ov[3]);
         }
-        if (valid) out4[o] = make_float4(ov[0], ov[1], ov[2], ov[3]);
-        o0 = o0n; sl = sn; fa = fan; fb = fbn;
+        o0 += step; sl = tail_slot_next(sl, dq, dr, p4); mask = tail_mask_next(mask);
     }
     p1_frame_close<true>(qcount, &qctr, qovf, segcap);
 }
@@ -391,9 +426,9 @@ int launch_extract(hipStream_t s, const ExtractPlan& pl, const ExtractOps& o)
     if (queued && o.empty_flags) {
         const QueueLayout::Region q = pl.layout.region(o.queue_ws);
         PItem* queue = reinterpret_cast<PItem*>(q.items);
-        dispatch1(pl.checked, [&](auto C) {
+        dispatch2(pl.checked, tail_walk_aligned((unsigned int)(g.plane / 4)), [&](auto C, auto A) {
             if (pl.kernel == EXTRACT_K_NOISE2)
-                hipLaunchKernelGGL((k_extract4_noise2_sparse<decltype(C)::value>), grid, block, 0, s, in, o.out, g.plane / 4, g.nzo, g.inc, g.index_inc,
+                hipLaunchKernelGGL((k_extract4_noise2_sparse<decltype(C)::value, decltype(A)::value>), grid, block, 0, s, in, o.out, g.plane / 4, g.nzo, g.inc, g.index_inc,
                                    o.scal, o.min_value, o.mul, k0, k1, o.stream, offset, queue, q.counts, pl.segcap, o.empty_flags, o.empty_stride);
             else
                 hipLaunchKernelGGL((k_extract_noise2_any_sparse<decltype(C)::value>), grid, block, 0, s, in, o.out, g.plane, g.nzo, g.inc, g.index_inc,

@@ -222,5 +222,29 @@ constexpr TailLane tail_lane(TailSlot s, unsigned int lane, unsigned int p4)
 {
     return lane >= tail_slot_first(s, p4) ? TailLane{s.k + 1u, lane - tail_slot_first(s, p4), true} : TailLane{s.k, s.rem + lane, false};
 }
+// p4 a multiple of 64 (every power-of-two plane, the flagship's): a wave's slots start on multiples of 64 groups, so none straddles a
+// plane and none is cut by the end of the output -- the kernel instance without a second plane, per-lane flags or a `valid` lane mask
+constexpr bool tail_walk_aligned(unsigned int p4) { return p4 % 64u == 0u; }
+
+// The flags of a wave's trips as a bit mask, asked for once per TAIL_MASK_TRIPS trips and not once per trip.  Trip t of the wave is the
+// slot at group o0 + t * step.  From the slot at o0 on, lane l of the wave asks for ONE flag: lanes 0..31 that of the plane the slot of
+// trip l starts in, lanes 32..63 that of the plane behind it for trip l - 32 -- the second plane of a straddling slot, clamped to the last
+// plane as a slot at the end of the output has none -- and lanes whose trip lies past the end ask for nothing: their bit is clear.  The
+// wave's ballot over "flag set" is the mask: bit t the first plane of trip t, bit 32 + t its second.  One load instruction per wave
+// and refill, no flag register carried from trip to trip; the one division per lane is per refill too.
+constexpr unsigned int TAIL_MASK_TRIPS = 32;
+struct TailAsk { bool ask; unsigned int k; };               // whether the lane loads a flag, and of which output plane
+constexpr TailAsk tail_mask_ask(unsigned int o0, unsigned int lane, unsigned int step, unsigned int p4, unsigned int total4, unsigned int klast)
+{
+    // (outputs < 2^32: total4 < 2^30, and step <= POISSON_MAX_BLOCKS * 256 = 2^22 -- no sum here reaches 2^32)
+    const unsigned int o = o0 + (lane % TAIL_MASK_TRIPS) * step, k = o / p4;
+    return o < total4 ? TailAsk{true, (lane >= TAIL_MASK_TRIPS && k < klast) ? k + 1u : k} : TailAsk{false, 0u};
+}
+constexpr bool tail_mask_refill(unsigned int trip) { return trip % TAIL_MASK_TRIPS == 0u; }       // the mask is used up (or was never loaded)
+constexpr bool tail_mask_first(unsigned long long m) { return (m & 1ull) != 0ull; }               // this trip's first plane is non-empty
+constexpr bool tail_mask_second(unsigned long long m) { return ((m >> TAIL_MASK_TRIPS) & 1ull) != 0ull; }
+constexpr unsigned long long tail_mask_next(unsigned long long m) { return (m >> 1) & ~(1ull << (TAIL_MASK_TRIPS - 1u)); }   // both halves move on one trip
+// trips of the wave whose first slot starts at o0 (what the walk `for (; o0 < total4; o0 += step)` makes)
+constexpr unsigned int tail_trips(unsigned int o0, unsigned int total4, unsigned int step) { return o0 < total4 ? (total4 - o0 - 1u) / step + 1u : 0u; }
 
 }  // namespace mvsim
