@@ -1105,6 +1105,15 @@ int mvsim_get_plane_stats(mvsim_ctx* ctx, int64_t stats[3]);
  * mvsim_get_plane_stats), the convolved volume not requested, and a sampled view on the work queue; together with the third figure of
  * mvsim_get_plane_stats it says how many planes were left out.  Recorded on the host when the work is enqueued. */
 int mvsim_get_tail_path(mvsim_ctx* ctx, int64_t out[2]);
+/* PSF spectra kept by content (option "psf_cache" = MiB of device memory, default 1024; 0 switches it off; exact).  A whole single view
+ * on the hand-written FFT with the direct z pass (mvsim_simulate_view_dev and the host / async entry points on top of it) whose
+ * NORMALISED PSF and geometry the context has seen before uploads no PSF and launches neither of the PSF's two transform passes: the
+ * convolution reads the spectrum the first such view computed.  The PSF is normalised in place on every call all the same.  A lookup
+ * is a 64-bit hash and then a comparison of every tap; replacement is least recently used under the cap.  Stacked views, lanes, z
+ * slabs, rocFFT, fft_zpass=fft / inline, graph=1, conv_method 2, mvsim_convolve_dev and an iteration that returns view_psf do not use
+ * the cache.  out = {hits, misses, evictions, device bytes held} of this context; mvsim_release_caches frees the entries and keeps
+ * the three counters.  Recorded on the host when the work is enqueued. */
+int mvsim_get_psf_cache_stats(mvsim_ctx* ctx, int64_t out[4]);
 /* The work queue of the Poisson sampler (Tools.java:73-86 is one sample per voxel; here the voxels whose sample needs the divergent fp64
  * code wait in per-block segments for a second kernel): stats = {bytes of queue workspace the context holds, items one segment holds,
  * bright items (lambda >= 10) and inversion items (lambda < 10) the context's last sampled view queued -- the first view of a stacked

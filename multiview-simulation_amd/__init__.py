@@ -201,7 +201,7 @@ class Context(ContextAberrations, ContextPhantoms, ContextDeconvolution, Context
     def set_option(self, name: str, value) -> None:
         """Run-time switch of this context (mvsim_set_option): fft_zpass, fft_backend, fft_pad, fused_rotate,
         poisson_queue, poisson_queue_share, early_sum, graph, fuse_tail, psf_overlap, tail_overlap, attenuate, broadcast, view_batch,
-        view_lanes, acq_transfer, host_threads, sphere_walk, dog_pass (include/mvsim.h and DESIGN.md list them with their values)."""
+        view_lanes, acq_transfer, host_threads, sphere_walk, dog_pass, psf_cache (include/mvsim.h and DESIGN.md list them with their values)."""
         if isinstance(value, bool):
             value = "1" if value else "0"
         _lib.check(self._L.mvsim_set_option(self._h, name.encode(), str(value).encode()))
@@ -691,6 +691,13 @@ class Context(ContextAberrations, ContextPhantoms, ContextDeconvolution, Context
         st = (C.c_int64 * 2)()
         _lib.check(self._L.mvsim_get_tail_path(self._h, st))
         return int(st[0]), int(st[1])
+
+    def psf_cache_stats(self):
+        """mvsim_get_psf_cache_stats: dict(hits, misses, evictions, bytes) of the PSF spectra this context keeps by content (option
+        psf_cache, MiB; 0 = off)."""
+        st = (C.c_int64 * 4)()
+        _lib.check(self._L.mvsim_get_psf_cache_stats(self._h, st))
+        return dict(hits=int(st[0]), misses=int(st[1]), evictions=int(st[2]), bytes=int(st[3]))
 
     def queue_stats(self):
         """The Poisson work queue of the last sampled view: dict(bytes, segment_items, bright, inversion, refused, fullest_block) --

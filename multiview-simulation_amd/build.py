@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmvsim.so")
 SOURCES = ["api.cpp", "api_view.cpp", "api_host.cpp", "api_sims.cpp", "comm.cpp", "kernels.hip", "rotate.hip", "extract.hip", "extract_interval.hip", "fftconv.hip", "fft_driver.hip", "fft_passes.hip", "zconv.hip", "rotate_fft.hip", "stencil.hip", "phantom.hip", "beads.hip", "aberrations.hip", "raytrace.hip", "procedural.hip", "sphere_walk.hip", "api_decon.cpp", "deconvolve.hip", "api_detect.cpp", "detect.hip", "api_register.cpp", "register.hip", "api_fuse.cpp", "fuse.hip", "api_psf.cpp", "psf.hip"]
-HEADERS = ["common.h", "api_internal.h", "host_pool.h", "jrandom.h", "extract_plan.h", "interval_plan.h", "poisson_dev.h", "poisson_recipe.h", "fft_dev.h", "fft_host.h", "rotate_rounds.h", "row_bits.h", "rotate_dev.h", "sphere_walk.h", "aberr_dev.h", "bricks.h", "decon.h", "detect.h", "register.h", "register_dev.h", "fuse.h", "fuse_dev.h", "psf.h", "psf_dev.h", "../../include/mvsim.h"]
+HEADERS = ["common.h", "api_internal.h", "host_pool.h", "jrandom.h", "extract_plan.h", "interval_plan.h", "poisson_dev.h", "poisson_recipe.h", "fft_dev.h", "fft_host.h", "rotate_rounds.h", "row_bits.h", "rotate_dev.h", "sphere_walk.h", "aberr_dev.h", "bricks.h", "decon.h", "detect.h", "register.h", "register_dev.h", "fuse.h", "fuse_dev.h", "psf.h", "psf_dev.h", "psf_cache.h", "../../include/mvsim.h"]
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 

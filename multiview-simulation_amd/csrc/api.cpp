@@ -72,6 +72,7 @@ int parse_option(Options& o, const char* name, const char* value)
     if (n == "skip_empty") return flag(&o.skip_empty);
     if (n == "skip_rows") return flag(&o.skip_rows);
     if (n == "skip_tail") return flag(&o.skip_tail);
+    if (n == "psf_cache") return number(7, 0, 1 << 20, &o.psf_cache);                 // MiB of PSF spectra kept by content; 0: off
     if (n == "fft_pad") {
         long long a = 0, b = 0, c = 0;
         if (v == "auto" || v.empty()) { o.fft_pad[0] = o.fft_pad[1] = o.fft_pad[2] = 0; return MVSIM_OK; }
@@ -418,22 +419,76 @@ int host_threads_of(const mvsim_ctx* ctx)            // ctx may be null: the pro
     return (int)std::max(1u, std::min(16u, hw ? hw : 1u));
 }
 
-// Normalise the PSF on the host exactly as Tools.normImage does, in place (Q5), then place it in device memory.
-int psf_prepare(mvsim_ctx* ctx, float* psf_host, const int64_t kdim[3], const int64_t dim[3])
+static void* psf_cache_alloc(size_t bytes)
+{
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    return p;
+}
+static void psf_cache_free(void* p) { (void)hipFree(p); }     // (waits for the device: nothing still reads what an eviction frees)
+
+// The cache entry of this normalised PSF for the convolution that follows, or null: the view uploads into ctx->psf_dev and
+// transforms its PSF as ever.  *fresh: the entry is new, its device PSF is still to be uploaded.
+static PsfCache::Entry* psf_cache_entry(mvsim_ctx* ctx, const float* psf_host, const int64_t kdim[3], const int64_t dim[3], bool* fresh)
+{
+    const Options& o = ctx->opt;
+    *fresh = false;
+    if (o.psf_cache <= 0 || !dim) return nullptr;
+    if (o.graph) return nullptr;                                      // a captured graph holds pointers: G2 must stay ctx->cfft_g2
+    ConvPlan pl;
+    if (!conv_plan(dim, kdim, o, &pl)) return nullptr;                // rocFFT: another spectrum altogether
+    if (!pl.zdirect || o.zpass == 3 || pl.zinline_auto) return nullptr;   // the padded and the inline FFT z pass read G2 in forms of their own
+    PsfKey key{};
+    for (int d = 0; d < 3; ++d) key.kdim[d] = kdim[d];
+    key.px = pl.px; key.py = pl.py; key.pyb = pl.pyb; key.hxp = pl.hxp; key.zdirect = 1; key.tile_y = pl.tile_y; key.views = 1;
+    const size_t n = (size_t)(kdim[0] * kdim[1] * kdim[2]);
+    ctx->psf_cache.configure(psf_cache_alloc, psf_cache_free);
+    if (PsfCache::Entry* e = ctx->psf_cache.find(key, psf_host, n)) return e;
+    *fresh = true;
+    // as much of G2 as the driver reserves for one view (fft_driver.hip: custom_fft_convolve_slab)
+    return ctx->psf_cache.insert(key, psf_host, n, (size_t)pl.hxp * pl.pyb * pl.k[2] * sizeof(float2), (size_t)o.psf_cache << 20);
+}
+
+// Normalise the PSF on the host exactly as Tools.normImage does, in place (Q5), then place it in device memory -- unless the context
+// holds the spectrum of these very taps already (cacheable: the caller is a whole single view on the hand-written FFT and needs
+// ctx->psf_dev for nothing but the spectrum): then nothing is copied and nothing enqueued.
+int psf_prepare(mvsim_ctx* ctx, float* psf_host, const int64_t kdim[3], const int64_t dim[3], bool cacheable)
 {
     MVSIM_CHECK_ARG(psf_host != nullptr && kdim != nullptr, "psf is null");
     MVSIM_CHECK_ARG(kdim[0] >= 1 && kdim[1] >= 1 && kdim[2] >= 1, "psf dimensions must be >= 1");
-    (void)dim;
     const int64_t n = kdim[0] * kdim[1] * kdim[2];
     psf_normalise_host(psf_host, n);
-    MVSIM_TRY(ctx->psf_dev.reserve((size_t)n * sizeof(float)));
+    ctx->psf_entry = nullptr;
+    void* dst = nullptr;
+    PsfCache::Entry* fresh_entry = nullptr;
+    if (cacheable) {
+        bool fresh = false;
+        PsfCache::Entry* e = psf_cache_entry(ctx, psf_host, kdim, dim, &fresh);
+        if (e && !fresh) { ctx->psf_entry = e; return MVSIM_OK; }     // a hit: its taps are on the device, behind their upload in stream order
+        if (e) { dst = e->psf; fresh_entry = e; }
+    }
+    if (!dst) {
+        MVSIM_TRY(ctx->psf_dev.reserve((size_t)n * sizeof(float)));
+        dst = ctx->psf_dev.p;
+    }
+    // (a new entry that took over an evicted one's buffers: their last readers were that entry's PSF passes, joined to this stream since)
     int slot = 0;
-    MVSIM_TRY(ctx->pinned.acquire((size_t)n * sizeof(float), &slot));
-    std::memcpy(ctx->pinned.p[slot], psf_host, (size_t)n * sizeof(float));
-    MVSIM_HIP(hipMemcpyAsync(ctx->psf_dev.p, ctx->pinned.p[slot], (size_t)n * sizeof(float), hipMemcpyHostToDevice,
-                             ctx->stream));
-    MVSIM_HIP(hipEventRecord(ctx->pinned.ev[slot], ctx->stream));
-    ctx->pinned.busy[slot] = true;
+    int rc = ctx->pinned.acquire((size_t)n * sizeof(float), &slot);
+    if (rc == MVSIM_OK) {
+        std::memcpy(ctx->pinned.p[slot], psf_host, (size_t)n * sizeof(float));
+        if (hipMemcpyAsync(dst, ctx->pinned.p[slot], (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+            hipEventRecord(ctx->pinned.ev[slot], ctx->stream) != hipSuccess) {
+            set_error("PSF upload failed: %s", hipGetErrorString(hipGetLastError()));
+            rc = MVSIM_EHIP;
+        } else {
+            ctx->pinned.busy[slot] = true;
+        }
+    }
+    if (rc != MVSIM_OK) {
+        if (fresh_entry) ctx->psf_cache.discard(fresh_entry);
+        return rc;
+    }
+    ctx->psf_entry = fresh_entry;
     return MVSIM_OK;
 }
 
@@ -454,7 +509,9 @@ int convolve_with_psf(mvsim_ctx* ctx, const float* img, const int64_t dim[3], co
 int convolve_dev_impl(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const int64_t kdim[3], int method, float* out,
                       ConvTail* tail)
 {
-    return convolve_with_psf(ctx, img, dim, ctx->psf_dev.as<float>(), kdim, method, out, tail);
+    // (a cached PSF's taps live in its entry; the driver takes the entry itself from ctx->psf_entry)
+    const float* psf = ctx->psf_entry ? static_cast<const float*>(ctx->psf_entry->psf) : ctx->psf_dev.as<float>();
+    return convolve_with_psf(ctx, img, dim, psf, kdim, method, out, tail);
 }
 
 }  // namespace mvsim
@@ -528,6 +585,7 @@ int mvsim_destroy(mvsim_ctx* ctx)
     view_graphs_release(ctx);
     fft_release(ctx);                                     // plans, twiddles, weights; its workspaces are on the list like all others
     ctx->each_workspace([](DevBuf& b, int) { b.release(); });
+    ctx->psf_cache.clear();
     for (CountsStaging* c : {&ctx->sync_counts, &ctx->async_counts[0], &ctx->async_counts[1]}) c->release();
     ctx->pinned.release_all();
     if (ctx->ev_created)
@@ -581,6 +639,8 @@ int mvsim_release_caches(mvsim_ctx* ctx)
     view_graphs_release(ctx);                             // captured launches point into the workspaces released below
     fft_release(ctx);
     ctx->each_workspace([](DevBuf& b, int traits) { if (!(traits & WS_KEPT)) b.release(); });
+    ctx->psf_cache.clear();                               // (its counters of hits, misses and evictions stay)
+    ctx->psf_entry = nullptr;
     ctx->weight_dim[0] = 0;
     // the page-locked twins too, whether or not the pipelined entry points ever set their slots up
     for (CountsStaging* c : {&ctx->sync_counts, &ctx->async_counts[0], &ctx->async_counts[1]}) c->release();
@@ -746,7 +806,7 @@ int mvsim_convolve_dev(mvsim_ctx* ctx, const float* img, const int64_t dim[3], f
     MVSIM_TRY(check_dim(dim));
     MVSIM_CHECK_ARG(img && out, "null buffer");
     MVSIM_CHECK_ARG(method >= 0 && method <= 2, "method must be 0, 1 or 2");
-    MVSIM_TRY(psf_prepare(ctx, psf_host, kdim, dim));
+    MVSIM_TRY(psf_prepare(ctx, psf_host, kdim, dim, false));           // the stage operator: not a view, no PSF cache
     return convolve_dev_impl(ctx, img, dim, kdim, method, out);
 }
 
@@ -954,6 +1014,14 @@ int mvsim_get_tail_path(mvsim_ctx* ctx, int64_t out[2])
     return MVSIM_OK;
 }
 
+int mvsim_get_psf_cache_stats(mvsim_ctx* ctx, int64_t out[4])
+{
+    MVSIM_CHECK_ARG(ctx != nullptr && out != nullptr, "null pointer");
+    const PsfCache::Stats& st = ctx->psf_cache.stats();
+    out[0] = st.hits; out[1] = st.misses; out[2] = st.evictions; out[3] = st.bytes;
+    return MVSIM_OK;
+}
+
 int mvsim_fused_tail_geometry(mvsim_ctx* ctx, const int64_t dim[3], const int64_t kdim[3], int inc, int want_con, int64_t out[2])
 {
     MVSIM_CHECK_ARG(ctx != nullptr && dim && kdim && out, "null pointer");
@@ -1025,6 +1093,8 @@ int mvsim_get_timings(mvsim_ctx* ctx, mvsim_timings* t)
     float total = 0.f;
     for (int s = 0; s < ST_COUNT; ++s) {
         ms[s] = cnt[s] ? (float)(sum[s] / cnt[s]) : 0.f;
+        // views whose PSF spectrum came from the cache recorded no PSF stage: the average is over every convolution all the same
+        if (s == ST_PSF && cnt[ST_CONVOLVE] > cnt[s]) ms[s] = (float)(sum[s] / cnt[ST_CONVOLVE]);
         // a PSF spectrum that ran on the side stream overlaps passes A and B: it is part of convolve_ms, not a stage of its own
         if (s == ST_PSF && ctx->psf_on_side) ms[s] = 0.f;
         if (s < ST_PASS_A) total += ms[s];              // the passes are nested inside ST_CONVOLVE

@@ -29,10 +29,13 @@ int interval_jobs_check(const mvsim_interval_job* jobs, int n, std::vector<Inter
 int extract_intervals_enqueue(mvsim_ctx* ctx, const mvsim_interval_job* jobs, const std::vector<IntervalGeom>& geoms, float* const* out_dev);
 int host_threads_of(const mvsim_ctx* ctx);
 void psf_normalise_host(float* psf_host, int64_t n);
-int psf_prepare(mvsim_ctx* ctx, float* psf_host, const int64_t kdim[3], const int64_t dim[3]);
+// cacheable: the call is a whole single view that may take its PSF's spectrum from the context's cache (psf_cache.h) -- then a PSF the
+// context has seen is not uploaded, and ctx->psf_entry tells the convolution that follows; otherwise ctx->psf_dev receives the taps
+int psf_prepare(mvsim_ctx* ctx, float* psf_host, const int64_t kdim[3], const int64_t dim[3], bool cacheable);
 int convolve_dev_impl(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const int64_t kdim[3], int method, float* out,
                       ConvTail* tail = nullptr);
-// the same convolution with an explicit device PSF (convolve_dev_impl: the context's own); neither method caches by the PSF's address
+// the same convolution with an explicit device PSF (convolve_dev_impl: the context's own, or its cache entry's); neither method caches by
+// the PSF's ADDRESS -- the cache is keyed by the taps themselves
 int convolve_with_psf(mvsim_ctx* ctx, const float* img, const int64_t dim[3], const float* psf_dev, const int64_t kdim[3], int method,
                       float* out, ConvTail* tail = nullptr);
 void view_graphs_release(mvsim_ctx* ctx);                 // api_view.cpp

@@ -242,9 +242,9 @@ static int view_graph_launch(mvsim_ctx* ctx, const float* gt, const int64_t dim[
     return MVSIM_OK;
 }
 
-int mvsim_simulate_view_dev(mvsim_ctx* ctx, const float* gt, const int64_t dim[3], float* psf_host,
-                            const int64_t kdim[3], const mvsim_view_params* p, const mvsim_view_outputs* o,
-                            double* correction)
+// keep_psf_dev: the caller reads ctx->psf_dev behind the view (main's iteration: view_psf), so the view uploads its PSF whatever the cache holds
+static int simulate_view_dev(mvsim_ctx* ctx, const float* gt, const int64_t dim[3], float* psf_host, const int64_t kdim[3],
+                             const mvsim_view_params* p, const mvsim_view_outputs* o, double* correction, bool keep_psf_dev)
 {
     MVSIM_TRY(set_device(ctx, /*keep_tail=*/true));
     // The previous view's tail may stay in flight beside this view's first stage, and this view's tail behind the call,
@@ -261,7 +261,8 @@ int mvsim_simulate_view_dev(mvsim_ctx* ctx, const float* gt, const int64_t dim[3
     MVSIM_CHECK_ARG(p->conv_method >= 0 && p->conv_method <= 2, "conv_method must be 0, 1 or 2");
     MVSIM_CHECK_ARG(dim[0] <= dim[1], "attenuate3d: Nx > Ny walks outside the interval in the reference");
     ev_next(ctx);
-    MVSIM_TRY(psf_prepare(ctx, psf_host, kdim, dim));
+    // (conv_method 2, the stencil, has no spectrum)
+    MVSIM_TRY(psf_prepare(ctx, psf_host, kdim, dim, !keep_psf_dev && kdim && pick_method(p->conv_method, kdim) == 1));
     // a view replays from a graph when asked to, unless stage events are being recorded (they would be captured too) or
     // the convolution would go through rocFFT (library calls inside a capture are not ours to vouch for)
     int64_t P[3];
@@ -275,6 +276,13 @@ int mvsim_simulate_view_dev(mvsim_ctx* ctx, const float* gt, const int64_t dim[3
         MVSIM_HIP(hipStreamSynchronize(ctx->stream));
     }
     return MVSIM_OK;
+}
+
+int mvsim_simulate_view_dev(mvsim_ctx* ctx, const float* gt, const int64_t dim[3], float* psf_host,
+                            const int64_t kdim[3], const mvsim_view_params* p, const mvsim_view_outputs* o,
+                            double* correction)
+{
+    return simulate_view_dev(ctx, gt, dim, psf_host, kdim, p, o, correction, false);
 }
 
 // How many views of this size run side by side on LANES -- the form for views that cannot be stacked (an adjusted volume requested,
@@ -336,6 +344,7 @@ static int views_enqueue_batched(mvsim_ctx* ctx, const float* gt, const int64_t 
     const bool noise = p0.snr >= 0.0f;
     const int64_t nzo = mvsim_extract_nz(dim[2], p0.inc), plane_vox = dim[0] * dim[1];
     ev_next(ctx);
+    ctx->psf_entry = nullptr;                              // stacked views: V PSFs in one G2, no PSF cache
     // one upload for everything the views bring: [V inverse models][V extract tables][V normalised PSFs]
     const size_t tab_a = (size_t)V * sizeof(Affine), tab_e = (size_t)V * sizeof(ExtractView);
     const size_t off_e = (tab_a + 255) & ~(size_t)255, off_p = (off_e + tab_e + 255) & ~(size_t)255;
@@ -480,7 +489,7 @@ int mvsim_simulate_views_dev(mvsim_ctx* ctx, const float* gt, const int64_t dim[
     int rc = MVSIM_OK;
     for (int v = 0; v < n_views && rc == MVSIM_OK; ++v) {
         mvsim_ctx* lane = ctx->lanes[(size_t)(v % nl)];
-        rc = psf_prepare(lane, psf_host[v], kdim, dim);
+        rc = psf_prepare(lane, psf_host[v], kdim, dim, false);        // lanes: small views side by side, each lane a context of its own -- no PSF cache
         if (rc == MVSIM_OK) rc = view_enqueue(lane, gt, dim, kdim, &params[v], &outs[v], false);
         ev_rebalance(lane);
     }
@@ -500,7 +509,7 @@ int mvsim_simulate_iteration_dev(mvsim_ctx* ctx, const float* gt, const int64_t 
                                  const mvsim_iteration_outputs* more)
 {
     MVSIM_CHECK_ARG(ctx && more, "null pointer");
-    MVSIM_TRY(mvsim_simulate_view_dev(ctx, gt, dim, psf_host, kdim, p, o, nullptr));
+    MVSIM_TRY(simulate_view_dev(ctx, gt, dim, psf_host, kdim, p, o, nullptr, more->view_psf != nullptr));
     MVSIM_TRY(set_device(ctx));                            // the rest reads the acquisition: a pending tail runs first
     Affine inv;
     double m[12];
@@ -572,7 +581,7 @@ static int slab_convolve_enqueue(mvsim_ctx* ctx, const float* gt, const int64_t 
     }
     const size_t pbytes = (size_t)dim[0] * dim[1] * sizeof(float);
     MVSIM_TRY(ctx->vol_a.reserve(pbytes * (size_t)(z1 - z0)));
-    MVSIM_TRY(psf_prepare(ctx, psf_host, kdim, dim));
+    MVSIM_TRY(psf_prepare(ctx, psf_host, kdim, dim, false));          // a z slab: not a whole view, no PSF cache
     double m[12];
     Affine inv;
     axis_rotation_host(dim, p->axis, p->degrees, m);

@@ -20,6 +20,7 @@
 #include "../../include/mvsim.h"
 #include "extract_plan.h"
 #include "interval_plan.h"
+#include "psf_cache.h"
 #include "rotate_dev.h"
 #include "sphere_walk.h"
 
@@ -217,6 +218,9 @@ struct Options {
     bool    skip_empty = true;         // convolution passes skip planes the fused rotate kernel found empty (exact; option for A/B runs)
     bool    skip_rows = true;          // ... and, where those flags are in use, the rotate kernel does not store the rows without a non-zero
                                        // voxel and pass B does not read them (row_bits.h; exact; option for A/B runs)
+    int     psf_cache = 1024;          // MiB of device memory for PSF spectra kept by content (psf_cache.h): a whole single view on the direct
+                                       // z pass whose normalised PSF and geometry the context has seen uploads nothing and launches neither PSF pass
+                                       // (exact: the same G2 bytes).  0: off -- every view uploads and transforms its PSF
     bool    skip_tail = true;          // ... and pass E does not store, nor phase 1 of the queue samplers read, the planes whose dilated flag is
                                        // clear (extract_plan.h: tail_sparse_ok; exact; option for A/B runs)
     int64_t beads_pair_cap = (int64_t)1 << 28;   // bead renderer and volume injection: (brick, item) pairs one chunk may bin; larger calls run in chunks (beads.hip, aberrations.hip)
@@ -251,6 +255,9 @@ struct mvsim_ctx {
     mvsim::DevBuf vol_a, vol_b, vol_c;      // N-sized float staging for host entry points / fused path
     mvsim::DevBuf out_buf;                  // extract output staging
     mvsim::DevBuf psf_dev;                  // K^3 floats
+    mvsim::PsfCache psf_cache;              // PSF spectra by content (option psf_cache); its entries are written and read on this context's
+                                            // main and side streams only
+    mvsim::PsfCache::Entry* psf_entry = nullptr;   // the entry psf_prepare settled for the convolution that follows it (null: ctx->psf_dev)
     mvsim::DevBuf view_tab;                 // stacked views: [inverse models][extract tables][PSFs] of the current batch
     mvsim::DevBuf interval_tab;             // interval jobs of the current call: [IntervalView table][ExtractView table] (extract_interval.hip)
     mvsim::DevBuf stencil_psf;              // direct stencil: PSF reversed along x, rows zero-padded to 4 taps

@@ -449,10 +449,18 @@ static int psf_passes(mvsim_ctx* ctx, const ConvRun& r, const float* psf)
 // It depends on nothing the image passes A and B produce and is a handful of small launches, so it runs on the
 // context's side stream beside them (fork here, join before the z pass reads G2 / G: ctx->psf_on_side).
 // Only where it pays: the fork and the join cost ~10 us of cross-stream dependency, more than the spectrum of a small view.
-static int psf_spectrum(mvsim_ctx* ctx, const ConvRun& r, const float* psf)
+//
+// entry (psf_cache.h; null: no cache for this call): r.G2 is the entry's buffer.  A filled entry holds the very bytes the two passes would
+// write (same taps, same geometry, same kernels): nothing is launched, and no fork is recorded for the PSF -- only the one
+// k_plane_flags_finish needs on the side stream when this view carries flags (flags_follow).  An entry that is not filled gets the passes'
+// output instead of ctx->cfft_g2.  Its buffer may be an evicted entry's, which the PREVIOUS view's z pass may still be reading on the
+// main stream: the passes write it on the side stream behind ev_fork, recorded here on the main stream, that is behind that z pass --
+// or on the main stream itself.  Stream order protects the slot; keep the fork in front of anything that writes an entry.
+static int psf_spectrum(mvsim_ctx* ctx, const ConvRun& r, const float* psf, PsfCache::Entry* entry, bool flags_follow)
 {
     hipStream_t s = ctx->stream;
-    const bool side = ctx->opt.psf_overlap && (int64_t)r.pl.n[0] * r.pl.n[1] * r.pl.n[2] >= (int64_t)1 << 24;
+    const bool hit = entry && entry->filled;
+    const bool side = ctx->opt.psf_overlap && (int64_t)r.pl.n[0] * r.pl.n[1] * r.pl.n[2] >= (int64_t)1 << 24 && (!hit || flags_follow);
     ctx->psf_on_side = side;
     if (side) {
         if (!ctx->side_stream) {
@@ -462,11 +470,14 @@ static int psf_spectrum(mvsim_ctx* ctx, const ConvRun& r, const float* psf)
         }
         MVSIM_HIP(hipEventRecord(ctx->ev_fork, s));
         MVSIM_HIP(hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
+        if (hit) return MVSIM_OK;                       // (plane_flags_setup records the join behind its kernel)
         ctx->stream = ctx->side_stream;                 // the launch helpers enqueue on ctx->stream
     }
+    if (hit) return MVSIM_OK;
     ev_begin(ctx, ST_PSF);
     const int rc = psf_passes(ctx, r, psf);
     ev_end(ctx, ST_PSF);
+    if (entry && rc == MVSIM_OK) entry->filled = true;
     if (side) {
         // always joined, also after a failed launch: a stream capture must not end with the side stream dangling
         ctx->stream = s;
@@ -738,23 +749,31 @@ int custom_fft_convolve_slab(mvsim_ctx* ctx, const float* img, const int64_t dim
     }
     if (!x_done) MVSIM_TRY(ctx->cfft_f.reserve(cbytes));
     MVSIM_TRY(ctx->cfft_g.reserve(cbytes));
-    MVSIM_TRY(ctx->cfft_g1.reserve((size_t)r.V * pl.hxp * pl.k[1] * kz * sizeof(float2)));
-    MVSIM_TRY(ctx->cfft_g2.reserve((size_t)r.V * pl.hxp * pl.pyb * kz * sizeof(float2)));
-    MVSIM_TRY(ctx->partials.reserve(PARTIALS_BYTES));
-    MVSIM_TRY(ctx->partials_e.reserve((size_t)((rows_out_early + 3) / 4 + 16) * sizeof(double)));
-    r.scal = scal_of(ctx);
     r.zs_chunk = (pl.zdirect && r.zstride > 1 && o.zconv_strided && o.zpass != 3)
                      ? zconv_strided_chunk(slab.nz_out, kz, r.zstride, (o.exp & 2) != 0, &r.zs_frows, &r.zs_lds) : 0;
     r.zinline = pl.zdirect && !r.is_slab && r.zs_chunk == 0 && r.V == 1 && (o.zpass == 3 || pl.zinline_auto);
+    // The cache entry psf_prepare settled for this call (it is this call's alone: taken off the context here).  Used by whole single
+    // views on the direct z pass, for the very taps `psf` points at and a G2 of this plan's size; anything else -- stacked views, a z slab,
+    // the inline FFT z pass -- transforms `psf` into the context's own G2 as ever (the taps in an entry are valid device memory either way).
+    const size_t g2_bytes = (size_t)r.V * pl.hxp * pl.pyb * kz * sizeof(float2);
+    PsfCache::Entry* pe = ctx->psf_entry;
+    ctx->psf_entry = nullptr;
+    if (pe && !(r.V == 1 && !r.is_slab && pl.zdirect && !r.zinline && psf == pe->psf && pe->g2_bytes == g2_bytes)) pe = nullptr;
+    if (!(pe && pe->filled)) MVSIM_TRY(ctx->cfft_g1.reserve((size_t)r.V * pl.hxp * pl.k[1] * kz * sizeof(float2)));
+    if (!pe) MVSIM_TRY(ctx->cfft_g2.reserve(g2_bytes));
+    MVSIM_TRY(ctx->partials.reserve(PARTIALS_BYTES));
+    MVSIM_TRY(ctx->partials_e.reserve((size_t)((rows_out_early + 3) / 4 + 16) * sizeof(double)));
+    r.scal = scal_of(ctx);
     MVSIM_TRY(ensure_twiddles(ctx, pl.M, 0, &r.tw_m));
     MVSIM_TRY(ensure_twiddles(ctx, pl.px, 1, &r.tw_px));
     MVSIM_TRY(ensure_twiddles(ctx, pl.py, 0, &r.tw_py));
     if (!pl.zdirect || r.zinline) MVSIM_TRY(ensure_twiddles(ctx, pl.pz, 0, &r.tw_pz));
     r.F = ctx->cfft_f.as<float2>(); r.G = ctx->cfft_g.as<float2>();
-    r.G1 = ctx->cfft_g1.as<float2>(); r.G2 = ctx->cfft_g2.as<float2>();
+    r.G1 = ctx->cfft_g1.as<float2>(); r.G2 = pe ? static_cast<float2*>(pe->g2) : ctx->cfft_g2.as<float2>();
     hipStream_t s = ctx->stream;
 
-    MVSIM_TRY(psf_spectrum(ctx, r, psf));
+    const bool flags_follow = x_done && tail->plane_nz && !r.zinline && !r.is_slab && !fuse;   // plane_flags_setup, below
+    MVSIM_TRY(psf_spectrum(ctx, r, psf, pe, flags_follow));
 
     ev_begin(ctx, ST_CONVOLVE);
     if (x_done) {
@@ -766,7 +785,7 @@ int custom_fft_convolve_slab(mvsim_ctx* ctx, const float* img, const int64_t dim
     } else {
         MVSIM_TRY(pass_a(ctx, r, img));
     }
-    if (x_done && tail->plane_nz && !r.zinline && !r.is_slab && !fuse) MVSIM_TRY(plane_flags_setup(ctx, r, tail->plane_nz));
+    if (flags_follow) MVSIM_TRY(plane_flags_setup(ctx, r, tail->plane_nz));
     MVSIM_TRY(pass_b(ctx, r));
     if (ctx->psf_on_side) MVSIM_HIP(hipStreamWaitEvent(s, ctx->ev_join, 0));    // the z pass reads the PSF spectrum
     ev_begin(ctx, ST_PASS_C);
