@@ -1076,6 +1076,12 @@ typedef struct mvsim_timings {
  * pitch), 1 if the z pass is the direct convolution}.  A pass moves 8 * Hxp * Py * planes bytes each way (the x passes
  * 4 N on their real side).  MVSIM_EINVAL when the sizes fall outside the pass table (rocFFT path). */
 int mvsim_fft_geometry(const int64_t dim[3], const int64_t kdim[3], int64_t geometry[5]);
+/* The direct z pass of a whole view of this volume / PSF that returns its acquisition only (every inc-th plane), under the default
+ * options: out = {kernel: 0 = k_zconv, which computes every plane -- else the stride s of k_zconv_strided<s>, which computes the planes
+ * k * inc alone --; zc, the outputs of a tile along z; nch, the tiles of a z column; nkxb, the 16-column groups of a spectrum row}.
+ * The same figures hold for every view of a stacked call.  Host only, no context.  MVSIM_EINVAL: inc < 1, no hand-written FFT size, or
+ * a z pass that is not the direct convolution (more than 64 z taps, fft_zpass = fft, the inline FFT z pass of deep PSFs). */
+int mvsim_zpass_geometry(const int64_t dim[3], const int64_t kdim[3], int inc, int64_t out[4]);
 /* Geometry of the direct LDS-tiled stencil (method 2) for this PSF: {taps of one x chunk, y taps, z taps of the PSF chunk a
  * tile serves, LDS bytes per block, blocks per CU}.  Any PSF of 1..64 taps per axis is accepted (SimulateMultiViewDataset.java:579
  * loads 51^3 stacks); beyond that MVSIM_EINVAL (use the FFT method). */

@@ -41,7 +41,7 @@ from .phantoms import ContextPhantoms
 __all__ = ["AffineTransform3D", "BeadRegistration", "Context", "DeconParams", "DifferenceOfGaussian", "DogParams", "MatchParams", "MultiViewDeconvolution", "Group", "Hessian", "HypersphereCollectionRealRandomAccessible", "JavaRandom", "Lightsheet",
            "PerlinNoiseRealRandomAccessible", "PointRejectionSampling", "RayTracingTest", "Raytrace", "RefractiveIndexMap", "ClearingMap", "SimpleCalculatedRealRandomAccessible", "SimulateBeads",
            "SimulateBeads2", "SimulateMultiViewAberrations", "SimulateMultiViewDataset", "Tools", "VolumeInjection", "broadcast_plan", "default_context", "MvsimError", "MvsimNoDeviceError", "ViewParams", "shard_views",
-           "version", "ViewFusion", "FuseParams", "PsfExtraction", "PsfParams"]
+           "version", "zpass_geometry", "ViewFusion", "FuseParams", "PsfExtraction", "PsfParams"]
 
 
 def broadcast_plan(nranks: int, rank: int, root: int, count: int, pieces: int = 8):
@@ -57,6 +57,14 @@ def broadcast_plan(nranks: int, rank: int, root: int, count: int, pieces: int = 
 
 def version() -> str:
     return _lib.load().mvsim_version().decode()
+
+
+def zpass_geometry(dim_xyz, kdim_xyz, inc: int = 1):
+    """mvsim_zpass_geometry (host only): (kernel, zc, nch, nkxb) of the direct z pass of a whole view that returns every inc-th plane --
+    kernel 0 is k_zconv, otherwise the stride of k_zconv_strided --, or None where that view's z pass is not the direct convolution."""
+    g = (C.c_int64 * 4)()
+    rc = _lib.load().mvsim_zpass_geometry((C.c_int64 * 3)(*dim_xyz), (C.c_int64 * 3)(*kdim_xyz), int(inc), g)
+    return tuple(int(x) for x in g) if rc == 0 else None
 
 
 # ------------------------------------------------------------------------------------------------

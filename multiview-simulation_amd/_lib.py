@@ -252,6 +252,7 @@ SIGNATURES = {
     "mvsim_simulate_view_zslabs": (C.c_int, [_vp, C.POINTER(_vp), _i64p, C.c_int, _i64p, _vp, _i64p, C.POINTER(ViewParams),
                                              C.POINTER(_vp), _i64p, C.c_int, C.POINTER(C.c_double)]),
     "mvsim_fft_geometry": (C.c_int, [_i64p, _i64p, _i64p]),
+    "mvsim_zpass_geometry": (C.c_int, [_i64p, _i64p, C.c_int, _i64p]),
     "mvsim_rotate_around_axis_zslabs": (C.c_int, [_vp, C.POINTER(_vp), _i64p, C.c_int, _i64p, C.c_int, C.c_int, C.POINTER(_vp), _i64p, C.c_int]),
     "mvsim_attenuate3d_zslabs": (C.c_int, [_vp, C.POINTER(_vp), _i64p, C.c_int, _i64p, C.c_double, C.POINTER(_vp), _i64p, C.c_int]),
     "mvsim_convolve_zslabs": (C.c_int, [_vp, C.POINTER(_vp), _i64p, C.c_int, _i64p, _vp, _i64p, C.c_int, C.POINTER(_vp), _i64p, C.c_int]),

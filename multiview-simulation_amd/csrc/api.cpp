@@ -1048,6 +1048,18 @@ int mvsim_fft_geometry(const int64_t dim[3], const int64_t kdim[3], int64_t geom
     return MVSIM_OK;
 }
 
+int mvsim_zpass_geometry(const int64_t dim[3], const int64_t kdim[3], int inc, int64_t out[4])
+{
+    if (!dim || !kdim || !out) { set_error("invalid argument: null pointer"); return MVSIM_EINVAL; }
+    MVSIM_TRY(check_dim(dim));
+    MVSIM_CHECK_ARG(inc >= 1, "inc must be >= 1");
+    if (!custom_zpass_geometry(dim, kdim, inc, out, env_options())) {
+        set_error("this view's z pass is not the direct convolution");
+        return MVSIM_EINVAL;
+    }
+    return MVSIM_OK;
+}
+
 // ---- timings ---------------------------------------------------------------------------------------
 int mvsim_enable_timing(mvsim_ctx* ctx, int enable)
 {

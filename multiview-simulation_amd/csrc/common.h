@@ -675,6 +675,9 @@ int  custom_fft_convolve_slab(mvsim_ctx* ctx, const float* img, const int64_t di
                               const int64_t kdim[3], const SlabRange& slab, float* out, ConvTail* tail);
 void custom_fft_release(mvsim_ctx* ctx);
 bool custom_fft_geometry(const int64_t dim[3], const int64_t kdim[3], int64_t g[5], const Options& opt);
+// {kernel (0: k_zconv, else the stride of k_zconv_strided), zc, nch, nkxb} of the direct z pass of a whole view that returns every inc-th
+// plane only (mvsim_zpass_geometry); false where that view's z pass is not the direct convolution
+bool custom_zpass_geometry(const int64_t dim[3], const int64_t kdim[3], int inc, int64_t g[4], const Options& opt);
 // the plan of the fused tail (pass E adjusts, extracts and samples: blocks, items per segment, queue layout); false when the view would not be fused
 bool fused_tail_geometry(const int64_t dim[3], const int64_t kdim[3], int inc, bool con_wanted, const Options& opt, ExtractPlan* fp);
 // true when views of this geometry can run stacked through the hand-written passes (ConvTail::views > 1): direct z pass, early sum,

@@ -308,6 +308,24 @@ bool custom_fft_geometry(const int64_t dim[3], const int64_t kdim[3], int64_t g[
     return true;
 }
 
+// What custom_fft_convolve_slab settles for the z pass of a whole view whose tail asks for the planes k * inc (the same expressions:
+// ConvRun::zstride, zs_chunk, zinline; ZConvArgs::zc, and the tile counts of zconv_grid)
+bool custom_zpass_geometry(const int64_t dim[3], const int64_t kdim[3], int inc, int64_t g[4], const Options& o)
+{
+    using namespace fft;
+    ConvPlan pl;
+    if (inc < 1 || !conv_plan(dim, kdim, o, &pl) || !pl.zdirect) return false;
+    const int nz = pl.n[2], kz = pl.k[2];
+    const int zstride = (pl.early && inc > 1) ? inc : 1;
+    int frows = 0;
+    size_t lds = 0;
+    const int zs_chunk = (zstride > 1 && o.zconv_strided && o.zpass != 3) ? zconv_strided_chunk(nz, kz, zstride, (o.exp & 2) != 0, &frows, &lds) : 0;
+    if (zs_chunk == 0 && (o.zpass == 3 || pl.zinline_auto)) return false;
+    const int zc = zs_chunk > 0 ? zs_chunk : zconv_chunk(nz, kz);
+    g[0] = zs_chunk > 0 ? zstride : 0; g[1] = zc; g[2] = (nz + zc - 1) / zc; g[3] = pl.hxp / NLZ;
+    return true;
+}
+
 bool custom_fft_batchable(const mvsim_ctx* ctx, const int64_t dim[3], const int64_t kdim[3])
 {
     const Options& o = ctx->opt;
